@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — LittleGAN training-step throughput on MI355X (one process per GPU).
 
-    python bench.py --gpus 1 --steps K --warmup W [--workload c3|c2] [--no-cpu-baseline]
+    python bench.py --gpus 1 --steps K --warmup W [--workload c3|c2] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one pass of the hot path (eager_trainer.py:133-168 of the reference: G fwd, D fwd on
@@ -11,6 +11,10 @@ already resident in HBM.  Metric (BASELINE.json): 128x128 images/sec, images = b
 Workloads:  c3 (default; the config the metric is quoted on): 128^2, B=256/GPU, bf16 MFMA, G+D+Adj
             c2: 128^2, B=64/GPU, exact-f32 MFMA, G+D only (train_adj off)
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps, writes the last timed step's outputs (--dump-outputs DIR) and prints
+the line.  --full adds every other leg: per-launch HIP events in the timed region (roofline), the hipGraph-replay timing,
+the clock census, the one-GPU contention rehearsal and the CPU baseline.
 """
 import argparse
 import json
@@ -154,6 +158,76 @@ def traffic_files():
     return sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "r*_pmc_traffic.json")), key=key)
 
 
+# --full: the roofline's per-launch HIP events (two per conv-class launch, on the launch stream) are recorded in every PROF_EVERY-th
+# step of the timed region: measured in round 4 (scripts/probe/event_cost.py), events around every launch of every step cost the eager
+# step 0.27 - 0.30 ms (2.4 %); one step in four keeps >= 12 of the default 50 steps (both step kinds) at a quarter of that.
+PROF_EVERY = 4
+DUMP_MAX_ELEMS = 4 << 20   # per dumped array (16 MB of float32): two image arrays and three losses stay under 64 MB
+OUTPUT_NAMES = ("fake_image", "adj_image", "gen_loss", "disc_loss", "adj_loss")   # EagerTrainer.train_step_from_inputs' return tuple
+
+
+def dump_outputs(dirname, outs):
+    """--dump-outputs: what the timed path returned to its caller in the last timed step, as DIR/<name>.npy in float32.  An
+    array larger than DUMP_MAX_ELEMS is sampled by whole images: the indices come from a fixed seed (0) and are kept in
+    ascending order, so two runs or two builds with the same arguments write the same images.  A None output (adj_image /
+    adj_loss when the Adjuster branch is off) removes a stale file of that name."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in zip(OUTPUT_NAMES, outs):
+        path = os.path.join(dirname, name + ".npy")
+        if t is None:
+            if os.path.exists(path):
+                os.remove(path)
+            continue
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            k = max(1, DUMP_MAX_ELEMS // t[0].numel())
+            idx = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:k].sort().values
+            t = t.index_select(0, idx.to(t.device))
+        np.save(path, t.float().cpu().numpy())
+
+
+def roofline_figures(prof, a, args, world, dt, n_prof_steps):
+    """--full: the per-kernel roofline of the timed region from ops.Profile's per-launch HIP events."""
+    ms = dt / a.steps * 1e3
+    dt_name = args.mfma_dtype
+    # ops.Profile keys are "<contraction class>:<kernel template the C side launched>" (lg_last_kernel)
+    by_kernel, by_class = {}, {}
+    for key, (n_, fl_, sec_) in prof.items():
+        cls, _, kern = key.partition(":")
+        for d, k in ((by_kernel, kern or cls), (by_class, cls)):
+            r = d.setdefault(k, [0, 0.0, 0.0])
+            r[0] += n_; r[1] += fl_; r[2] += sec_
+    # dominant kernel = the kernel template with the largest measured time in the timed region
+    tag, (n, fl, sec) = max(by_kernel.items(), key=lambda kv: kv[1][2])
+    ach = fl / sec / 1e12
+    # HBM-side bytes per launch of that kernel: rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) cannot run inside this process;
+    # they are collected on this same command and committed (scripts/collect_profiles.sh -> scripts/pmc_traffic.py)
+    traffic, traffic_src = None, None
+    tfiles = traffic_files()
+    if a.workload == "c3" and dt_name == "bf16" and world == 1 and tfiles:
+        tpath = tfiles[-1]   # the newest round's counter passes
+        rec = json.load(open(tpath)).get(tag)
+        if rec:
+            traffic, traffic_src = rec["bytes_per_launch"], f"profiles/{os.path.basename(tpath)} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, offline; goes stale when the kernel changes)"
+    conv_sec = sum(v[2] for v in prof.values())
+    conv_fl = sum(v[1] for v in prof.values())
+    nsteps_prof = 5 if a.graph else max(n_prof_steps, 1)
+    return {"bound": "mfma", "kernel": tag, "achieved": round(ach, 2), "peak": PEAK[dt_name], "unit": "TFLOP/s",
+            "frac": round(ach / PEAK[dt_name], 4), "traffic": traffic, "traffic_unit": "bytes/launch",
+            "traffic_source": traffic_src,
+            "launches": n, "avg_launch_ms": round(sec / n * 1e3, 4),
+            "all_kernels": {k: {"launches": v[0], "tflops": round(v[1] / v[2] / 1e12, 2), "frac": round(v[1] / v[2] / 1e12 / PEAK[dt_name], 4),
+                                "avg_launch_ms": round(v[2] / v[0] * 1e3, 4), "ms_per_step": round(v[2] / nsteps_prof * 1e3, 3)}
+                            for k, v in sorted(by_kernel.items(), key=lambda kv: -kv[1][2])},
+            "all_conv_kernels": {k: {"launches": v[0], "tflops": round(v[1] / v[2] / 1e12, 2),
+                                     "ms_per_step": round(v[2] / nsteps_prof * 1e3, 3)} for k, v in by_class.items()},
+            "event_timed_steps": nsteps_prof, "event_sampling": ("the 5 eager steps after the graph-replayed region" if a.graph else f"every {PROF_EVERY}th step of the timed region"),
+            "conv_share_of_step": round(conv_sec / (dt / a.steps * nsteps_prof), 3),
+            "conv_tflops_overall": round(conv_fl / conv_sec / 1e12, 2),
+            "step_algorithmic_tflops": round(GFLOP_PER_IMAGE[a.workload] * args.batch_size / ms, 2)}
+
+
 def spawn_ranks(a):
     """`python bench.py --gpus N` without a launcher: start N FRESH rank processes (torch.distributed.run, one per GPU)
     before this process has touched the GPU, relay their output (rank 0 prints the JSON line) and exit with the
@@ -209,14 +283,21 @@ def main():
                          "at the three GradSync.launch points K streaming read-add-write blocks run on the side stream")
     ap.add_argument("--reserve-cus", type=int, default=None, help="CUs the persistent kernels leave free (default: 0 at N=1, dist.RESERVED_CUS_DP at N>1)")
     ap.add_argument("--wall-limit", type=int, default=900, help="seconds the self-spawned N-rank run may take before it is terminated")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-baseline-full", action="store_true", help="time the C2 CPU shape at its full batch 64 (minutes)")
-    ap.add_argument("--no-graph-leg", action="store_true", help="skip the extra hipGraph-replay timing (profilers that collect counters cannot follow a graph capture)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--cpu-baseline-full", action="store_true", help="with --full: time the C2 CPU shape at its full batch 64 (minutes)")
+    ap.add_argument("--no-graph-leg", action="store_true", help="with --full: skip the extra hipGraph-replay timing (profilers that collect counters cannot follow a graph capture)")
     ap.add_argument("--graph", action="store_true", help="time EagerTrainer.graph_step (captured HIP graphs) instead of eager launches")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help="gloo: rehearsal of the N>1 path")
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal on a one-GPU box: every rank uses cuda:0 (needs --backend gloo; RCCL refuses it)")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg beyond the headline figure: per-launch HIP events in the timed region (roofline), the hipGraph-replay "
+                         "timing, the clock census, the one-GPU contention rehearsal and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (fake_image, adj_image, the three losses) as DIR/<name>.npy, float32")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(a)  # does not return
 
@@ -270,39 +351,38 @@ def main():
     for i in range(a.warmup):
         step(b0 + i, inp)
     barrier()
-    if not a.graph:
+    events = a.full and not a.graph   # the roofline's per-launch HIP events: --full only
+    if events:
         ops.Profile.start()
     tr.sync.time_waits = world > 1
     t0 = time.perf_counter()
-    # The roofline's per-launch HIP events (two per conv-class launch, on the launch stream) are recorded in every PROF_EVERY-th step
-    # of the timed region: measured in round 4 (scripts/probe/event_cost.py), events around every launch of every step cost the eager
-    # step 0.27 - 0.30 ms (2.4 %); one step in four keeps >= 12 of the default 50 steps (both step kinds) at a quarter of that.
-    PROF_EVERY = 4
     n_prof_steps = 0
     for i in range(a.steps):
-        if not a.graph:
+        if events:
             ops.Profile.enabled = (i % PROF_EVERY == 0)
             n_prof_steps += int(ops.Profile.enabled)
-        step(b0 + a.warmup + i, inp)
-    if not a.graph:
+        outs = step(b0 + a.warmup + i, inp)
+    if events:
         ops.Profile.enabled = True
     dt_host = time.perf_counter() - t0  # host time to ENQUEUE the K steps (no synchronisation inside a step): below ms_per_step = the GPU is the bound
     torch.cuda.synchronize()
     dt_own = time.perf_counter() - t0   # this rank's own time for its K steps (before the closing barrier)
     barrier()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:    # before any later leg runs a step over the same output buffers
+        dump_outputs(a.dump_outputs, outs)
     tr.sync.time_waits = False          # only the timed region's waits count (the roofline / graph legs below add none)
     n_wait_events = len(tr.sync.wait_events)
-    if a.graph:  # per-launch HIP events cannot sit inside a replayed graph: the roofline leg times 5 eager steps afterwards
+    if a.graph and a.full:  # per-launch HIP events cannot sit inside a replayed graph: the roofline leg times 5 eager steps afterwards
         ops.Profile.start()
         for i in range(5):
             tr.train_step_from_inputs(b0 + a.warmup + a.steps + i, inp)
         torch.cuda.synchronize()
-    prof = ops.Profile.stop()
+    prof = ops.Profile.stop() if a.full else {}
     losses = {k: float(v.item()) for k, v in tr.losses.items()}  # of the last TIMED step (before the graph-replay leg below)
     graph_ms = None
     profiled = any("rocprof" in (os.environ.get(k) or "").lower() for k in ("LD_PRELOAD", "ROCP_TOOL_LIBRARIES", "HSA_TOOLS_LIB"))
-    if world == 1 and not a.graph and a.workload == "c3" and args.mfma_dtype == "bf16" and not a.no_graph_leg and not profiled:
+    if a.full and world == 1 and not a.graph and a.workload == "c3" and args.mfma_dtype == "bf16" and not a.no_graph_leg and not profiled:
         # the same steps replayed from captured HIP graphs (EagerTrainer.graph_step, bit-identical results): reported beside
         # the headline number, which stays the eager one (per-launch HIP events cannot sit inside a replayed graph)
         bg = b0 + a.warmup + a.steps
@@ -325,7 +405,7 @@ def main():
 
     b_next = b0 + a.warmup + a.steps + 100
     clock = None
-    if world == 1 and not profiled:
+    if a.full and world == 1 and not profiled:
         # Shader clock HELD under this step (after the timed region; d s_memtime / d s_memrealtime x 100 MHz):
         #  (a) IN-KERNEL census: every block of the step's dominant kernel template (conv_down3, all its forms) adds the two counters'
         #      increments over its own life (~100 us) to a buffer during 20 further steps (lg_set_clock_census) — the clock those
@@ -361,7 +441,8 @@ def main():
                                                              "method": "20-us sampling wave on the compute stream behind every conv-class launch of 5 further steps (upper bound: chip otherwise idle during the sample)"})
         b_next += 100
     contention = None
-    ks = [int(k) for k in a.dp_contention.split(",")] if a.dp_contention else ([32] if (world == 1 and a.workload == "c3" and args.mfma_dtype == "bf16" and not profiled) else [])
+    ks = [int(k) for k in a.dp_contention.split(",")] if a.dp_contention else (
+        [32] if (a.full and world == 1 and a.workload == "c3" and args.mfma_dtype == "bf16" and not profiled) else [])
     if world == 1 and ks:
         # one-GPU rehearsal of data parallelism's CU contention: K streaming read-add-write workgroups on the side
         # stream at the three GradSync.launch points, with the persistent grids at full size and with K CUs left free
@@ -405,35 +486,12 @@ def main():
         gb = args.batch_size * world
         value = gb / (dt / a.steps)
         dt_name = args.mfma_dtype
-        # ops.Profile keys are "<contraction class>:<kernel template the C side launched>" (lg_last_kernel)
-        by_kernel, by_class = {}, {}
-        for key, (n_, fl_, sec_) in prof.items():
-            cls, _, kern = key.partition(":")
-            for d, k in ((by_kernel, kern or cls), (by_class, cls)):
-                r = d.setdefault(k, [0, 0.0, 0.0])
-                r[0] += n_; r[1] += fl_; r[2] += sec_
-        # dominant kernel = the kernel template with the largest measured time in the timed region
-        tag, (n, fl, sec) = max(by_kernel.items(), key=lambda kv: kv[1][2])
-        ach = fl / sec / 1e12
-        # HBM-side bytes per launch of that kernel: rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) cannot run inside this process;
-        # they are collected on this same command and committed (scripts/collect_profiles.sh -> scripts/pmc_traffic.py)
-        traffic, traffic_src = None, None
-        import glob
-        tfiles = traffic_files()
-        if a.workload == "c3" and dt_name == "bf16" and world == 1 and tfiles:
-            tpath = tfiles[-1]   # the newest round's counter passes
-            rec = json.load(open(tpath)).get(tag)
-            if rec:
-                traffic, traffic_src = rec["bytes_per_launch"], f"profiles/{os.path.basename(tpath)} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, offline; goes stale when the kernel changes)"
-        conv_sec = sum(v[2] for v in prof.values())
-        conv_fl = sum(v[1] for v in prof.values())
-        nsteps_prof = 5 if a.graph else max(n_prof_steps, 1)
         out = {
             "metric": {"c3": "128x128 CelebA-shaped images/sec (G+D+Adj step)", "c2": "128x128 CelebA-shaped images/sec (G+D step)",
                        "c5": "256x256 CelebA-shaped images/sec (G+D+Adj step)"}[a.workload],
             "value": round(value, 2), "unit": "images/sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": round(ms, 3), "host_enqueue_ms_per_step": round(dt_host / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": dt_name, "data": "synthetic",
+            "dtype": dt_name, "data": "synthetic", "full": a.full,
             "config": {"workload": {"c3": "C3: 128x128x3 synthetic CelebA, batch 256/GPU, bf16 MFMA conv/transposed-conv + Adjuster branch" if dt_name == "bf16" else
                                           "C3 at exact f32 (not a BASELINE config; the north star's 1e-4 loss tolerance): 128x128x3 synthetic CelebA, batch 256/GPU, f32 MFMA + Adjuster branch",
                                     "c2": "C2: 128x128x3 synthetic CelebA, batch 64/GPU, exact-f32 MFMA, G+D step only",
@@ -441,19 +499,7 @@ def main():
                        "global_batch": gb, "per_gpu_batch": args.batch_size, "image": args.init_dim * 16, "cond_dim": 40,
                        "parallelism": f"dp{world}", "consumed_samples_per_step": 2 * gb,
                        "launch": "hipGraph replay (one graph per step kind)" if a.graph else "eager launches"},
-            "roofline": {"bound": "mfma", "kernel": tag, "achieved": round(ach, 2), "peak": PEAK[dt_name], "unit": "TFLOP/s",
-                         "frac": round(ach / PEAK[dt_name], 4), "traffic": traffic, "traffic_unit": "bytes/launch",
-                         "traffic_source": traffic_src,
-                         "launches": n, "avg_launch_ms": round(sec / n * 1e3, 4),
-                         "all_kernels": {k: {"launches": v[0], "tflops": round(v[1] / v[2] / 1e12, 2), "frac": round(v[1] / v[2] / 1e12 / PEAK[dt_name], 4),
-                                             "avg_launch_ms": round(v[2] / v[0] * 1e3, 4), "ms_per_step": round(v[2] / nsteps_prof * 1e3, 3)}
-                                         for k, v in sorted(by_kernel.items(), key=lambda kv: -kv[1][2])},
-                         "all_conv_kernels": {k: {"launches": v[0], "tflops": round(v[1] / v[2] / 1e12, 2),
-                                                  "ms_per_step": round(v[2] / nsteps_prof * 1e3, 3)} for k, v in by_class.items()},
-                         "event_timed_steps": nsteps_prof, "event_sampling": ("the 5 eager steps after the graph-replayed region" if a.graph else f"every {PROF_EVERY}th step of the timed region"),
-                         "conv_share_of_step": round(conv_sec / (dt / a.steps * nsteps_prof), 3),
-                         "conv_tflops_overall": round(conv_fl / conv_sec / 1e12, 2),
-                         "step_algorithmic_tflops": round(GFLOP_PER_IMAGE[a.workload] * args.batch_size / ms, 2)},
+            "roofline": roofline_figures(prof, a, args, world, dt, n_prof_steps) if a.full else None,
             "graph_replay": None if graph_ms is None else {"ms_per_step": round(graph_ms, 3), "value": round(args.batch_size / graph_ms * 1e3, 2),
                                                                "note": "same steps, one captured hipGraph per step kind, 30 timed steps after the headline region"},
             "data_parallel": dp_info,   # null at one GPU
@@ -466,7 +512,7 @@ def main():
             # the headline's precision and the price of the north star's own tolerance, side by side
             "precision": precision_note(a.workload, args.mfma_dtype),
         }
-        if not a.no_cpu_baseline and world == 1:  # reported at N=1 only (rank 0), on a bounded sample
+        if a.full and not a.no_cpu_baseline and world == 1:  # reported at N=1 only (rank 0), on a bounded sample
             out["cpu_baseline"] = cpu_baseline(a.workload, a.cpu_baseline_full)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -1,10 +1,13 @@
-"""Generates tests/golden/step_small.npz from the fp64 numpy oracle.
+"""Generates tests/golden/step_small_{W0,W4,io}.npz from the fp64 numpy oracle.
 
 The reference (TF-1.15) cannot run in this pipeline and ships no fixtures
 (SURVEY.md §8c), so these vectors pin the ORACLE's own outputs (cross-checked
 against torch autograd in tests/test_oracle.py), not TensorFlow's: parity unpinned.
 
     python tests/golden/make_golden.py
+
+The fixture is stored in three shards (initial weights, weights after the last step, step inputs / outputs) so that no
+committed file exceeds 1 MiB; load() merges them into one name -> array mapping.
 """
 import os
 import sys
@@ -17,6 +20,30 @@ from oracle import np_oracle as O  # noqa: E402
 
 CFG = dict(init_dim=2, conv_filter=(64, 32, 32, 32, 32), cond_dim=5, noise_dim=11, batch_size=2)
 STEPS = (9, 10, 11, 12)  # 10 = partition step without Adjuster, 11/12 = Adjuster branch on
+HERE = os.path.dirname(os.path.abspath(__file__))
+SHARDS = ("W0", "W4", "io")
+
+
+def shard_path(shard):
+    return os.path.join(HERE, f"step_small_{shard}.npz")
+
+
+def shard_of(key):
+    return key[:2] if key[:2] in ("W0", "W4") else "io"
+
+
+def write_shards(arrays):
+    for shard in SHARDS:
+        np.savez_compressed(shard_path(shard), **{k: v for k, v in arrays.items() if shard_of(k) == shard})
+
+
+def load():
+    """The whole fixture as one {name: array} dict (the union of the shards)."""
+    out = {}
+    for shard in SHARDS:
+        with np.load(shard_path(shard)) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 def main():
@@ -49,8 +76,8 @@ def main():
     for m in st.W:
         for i, w in enumerate(st.W[m]):
             save[f"W4_{m}_{i}"] = w.astype(np.float32)  # expected values, rounded for storage
-    np.savez_compressed(os.path.join(os.path.dirname(__file__), "step_small.npz"), **save)
-    print("wrote step_small.npz", sum(v.nbytes for v in save.values()) / 1e6, "MB raw")
+    write_shards(save)
+    print("wrote", ", ".join(os.path.basename(shard_path(s_)) for s_ in SHARDS), sum(v.nbytes for v in save.values()) / 1e6, "MB raw")
 
 
 if __name__ == "__main__":

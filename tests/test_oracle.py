@@ -2,7 +2,6 @@
 source alone, numpy-manual-backward vs torch-autograd cross-check,
 and the committed golden fixture.  Parity to TensorFlow itself is UNPINNED."""
 import math
-import os
 
 import numpy as np
 import pytest
@@ -11,7 +10,6 @@ import torch
 from oracle import np_oracle as O
 from oracle import torch_oracle as T
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden", "step_small.npz")
 
 
 def test_soft_and_rescale_known_answers():
@@ -187,8 +185,8 @@ def test_torch_trainer_matches_numpy_trainer_over_steps():
 
 
 def test_golden_fixture_reproduces():
-    from tests.golden.make_golden import CFG, STEPS
-    g = np.load(GOLD)
+    from tests.golden.make_golden import CFG, STEPS, load
+    g = load()
     cfg = O.Cfg(**CFG)
     shp = O.weight_shapes(cfg)
     W = {m: [g[f"W0_{m}_{i}"].astype(np.float64) for i in range(len(shp[m]))] for m in "GDA"}

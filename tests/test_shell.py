@@ -162,3 +162,27 @@ def test_bench_precision_note_quotes_the_other_dtype_of_the_same_workload():
     assert n["other_dtype_same_workload"]["source"].startswith("profiles/") and n["other_dtype_same_workload"]["ms_per_step"] > 30
     assert bench.precision_note("c3", "f32")["other_dtype_same_workload"]["dtype"] == "bf16"
     assert bench.precision_note("c2", "f32")["other_dtype_same_workload"] is None   # c2's plain file IS the f32 run
+
+
+def test_bench_dump_outputs_writes_a_fixed_sample(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: the last timed step's return tuple as float32 .npy files; an array above the size cap is cut
+    to whole images at seeded, ascending indices (the same images on every run), and an output the step did not produce
+    (adj_* with the Adjuster branch off) leaves no stale file behind."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 10 * 4 * 4 * 3)
+    g = torch.Generator().manual_seed(5)
+    fake, adj = torch.randn(32, 4, 4, 3, generator=g), torch.randn(8, 4, 4, 3, generator=g)
+    losses = [torch.tensor([0.5]), torch.tensor([1.5]), torch.tensor([2.5])]
+    bench.dump_outputs(str(tmp_path / "a"), (fake, adj, *losses))
+    bench.dump_outputs(str(tmp_path / "b"), (fake, adj, *losses))
+    for name in bench.OUTPUT_NAMES:
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert x.dtype == np.float32 and np.array_equal(x, y)
+    got = np.load(tmp_path / "a" / "fake_image.npy")
+    assert got.shape == (10, 4, 4, 3)
+    rows = [int(np.flatnonzero((fake.numpy() == r).all(axis=(1, 2, 3)))[0]) for r in got]
+    assert rows == sorted(rows) and len(set(rows)) == 10
+    assert np.array_equal(np.load(tmp_path / "a" / "adj_image.npy"), adj.numpy())   # under the cap: whole
+    assert np.load(tmp_path / "a" / "disc_loss.npy").tolist() == [1.5]
+    bench.dump_outputs(str(tmp_path / "a"), (fake, None, losses[0], losses[1], None))
+    assert not (tmp_path / "a" / "adj_image.npy").exists() and not (tmp_path / "a" / "adj_loss.npy").exists()

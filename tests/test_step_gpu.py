@@ -65,7 +65,6 @@ def check_emu(tr, cfg, W, b, inp, fake, adj, lg, ld, la, only=None):
     for got, key in pairs:
         assert abs(got.item() - ref[key]) < tol["loss"] * abs(ref[key]), (key, got.item(), ref[key])
     check_grads(tr, ref, sets, tol, tag=f"emu b={b}", only=only)
-GOLD = os.path.join(os.path.dirname(__file__), "golden", "step_small.npz")
 
 
 def make_args(cfg: O.Cfg, mfma_dtype="f32"):
@@ -227,8 +226,8 @@ def test_adam_order_is_immaterial(mfma):
 
 
 def test_golden_fixture_f32():
-    from tests.golden.make_golden import CFG, STEPS
-    g = np.load(GOLD)
+    from tests.golden.make_golden import CFG, STEPS, load
+    g = load()
     cfg = O.Cfg(**CFG)
     shp = O.weight_shapes(cfg)
     W = {m: [g[f"W0_{m}_{i}"].astype(np.float64) for i in range(len(shp[m]))] for m in "GDA"}
