@@ -288,6 +288,43 @@ size_t lg_fid_stats_workspace_bytes(long long N, int D);
 int lg_fid_stats(const float* act, long long N, int D, double* mu, double* sigma, void* workspace, size_t ws_bytes,
                  void* stream);
 
+/* ---- discriminator gradient penalty (use_gp / gp_weight, sample.config.json:35-36) ------------------------------------ *
+ * Replaces the NotImplementedError of eager_trainer.py:141-143 ("todo: explore how to gp on eager mode").  The reference never
+ * defined the penalty; THIS PROJECT's definition (WGAN-GP, Gulrajani et al. 2017, on D's first output) is:
+ *   x^_b = eps_b new_image_b + (1 - eps_b) fake_b (eps_b ~ U[0,1) a step input, fake a constant),  p_b = output_pr(x^_b) (the
+ *   sigmoid of model.py:71),  g_b = dp_b/dx^_b,  r_b = |g_b|_2,  gp = mean_b (r_b - 1)^2,  disc_loss += gp_weight gp.
+ * Its D weight gradients are reverse over reverse; these are the pieces that are not ordinary conv / GEMM work.
+ * InstanceNormalization notation per sample: c = z - mu, sigma, s = sigma + 1e-3, gn = LeakyReLU'(gamma c/s + beta) g. */
+/* eps[b] = (bits >> 8) / 2^24 of word (b & 3) of Philox block offset + b/4 (the step's own counter window) */
+int lg_gp_draw_eps(float* eps, int B, unsigned long long seed, unsigned long long offset, void* stream);
+/* out[B][L] = eps_b real + (1 - eps_b) fake  (L % 4 == 0) */
+int lg_gp_interp(const float* real, const float* fake, const float* eps, float* out, int B, long long L, void* stream);
+/* scratch of lg_gp_seed / lg_gp_norm_bwd / lg_gp_norm_dd for B samples of L elements */
+size_t lg_gp_workspace_bytes(int B, long long L);
+/* g[B][L] = image gradient: r[b] = |g_b|; loss (+)= w gp, gp_loss = w gp (each may be null);
+ * u0 = (2 w / B)(r_b - 1)/max(r_b, 1e-12) g_b = d(w gp)/dg */
+int lg_gp_seed(const float* g, float* u0, float* r, float* loss, float* gp_loss, float gp_weight, void* workspace,
+               size_t ws_bytes, int B, long long L, void* stream);
+/* InstanceNormalization + LeakyReLU backward (first order) of a level from its raw output z (fp32) or z16 (bf16; give one) and
+ * statistics records [B][8]: dz = (gamma/s)(gn - mean gn - c mean(gn c)/(s sigma)) + add (add may be null: the injected adjoint
+ * of the second backward); dz16 (may be null) its bf16 mirror; dgamma += sum gn c/s, dbeta += sum gn (each may be null) */
+int lg_gp_norm_bwd(const float* z, const void* z16, const float* stats, const float* gamma, const float* g, const float* add,
+                   float* dz, void* dz16, float* dgamma, float* dbeta, void* workspace, size_t ws_bytes, int B, long long L,
+                   float alpha, void* stream);
+/* double backward of the same op along the adjoint u of dz (g = the level's output gradient of the first backward):
+ * uh = m (gamma/s)(u - U/N - c P/(N s sigma)) (adjoint on g); uz2 (may be null) = the second-order adjoint on z
+ *   -gamma T1 c/(N s^2 sigma) - gamma/(s^2 sigma) [P (gn - A)/N + M (u - U/N)] + gamma M P (2/s + 1/sigma) c/(N s^2 sigma^2);
+ * dgamma (may be null) += sum_b (T1 - M P/(s sigma))/s.  A = mean gn, M = mean gn c, U = sum u, P = sum u c, T1 = sum u gn - A U */
+int lg_gp_norm_dd(const float* z, const void* z16, const float* stats, const float* gamma, const float* g, const float* u,
+                  float* uh, float* uz2, float* dgamma, void* workspace, size_t ws_bytes, int B, long long L, float alpha,
+                  void* stream);
+/* heads (p[B][1+c] of lg_heads_fwd): g[B][K] = p_b (1 - p_b) wpr = dp_b / d(heads input) */
+int lg_gp_heads_seed(const float* p, const float* wpr, float* g, int B, int K, int c, void* stream);
+/* second order at the heads, u[B][K] = adjoint on that gradient: t[b] = p(1-p)(1-2p) <wpr, u_b>, g2 = t_b wpr (the second
+ * backward's heads-input gradient); dwpr (may be null, then x too) += sum_b p_b(1-p_b) u_b + t_b x_b, dbpr (may be null) += sum t */
+int lg_gp_heads_2nd(const float* p, const float* wpr, const float* x, const float* u, float* t, float* g2, float* dwpr,
+                    float* dbpr, int B, int K, int c, void* stream);
+
 /* ---- run-time services (no reference counterpart: the reference has no distributed code and no clock to report) ---- */
 /* CU budget of the persistent kernels.  Under data parallelism RCCL's ring kernels occupy CUs on a side stream while the
  * backward convs run (littlegan_amd/dist.py); every persistent launcher sizes its grid to lg_grid_cus() = CUs - reserved

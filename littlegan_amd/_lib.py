@@ -100,6 +100,15 @@ SIGNATURES = {
     "lg_set_clock_census": (I, [P]),
     "lg_clock_sample": (I, [P, I, P]),
     "lg_augment_drawn": (I, [P, P, I, I, I, F, F, F, F, F, L, L, L, P, Z, P]),
+    # discriminator gradient penalty (gp.hip; eps draw in augment.hip)
+    "lg_gp_draw_eps": (I, [P, I, L, L, P]),
+    "lg_gp_interp": (I, [P, P, P, P, I, L, P]),
+    "lg_gp_workspace_bytes": (Z, [I, L]),
+    "lg_gp_seed": (I, [P, P, P, P, P, F, P, Z, I, L, P]),
+    "lg_gp_norm_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, Z, I, L, F, P]),
+    "lg_gp_norm_dd": (I, [P, P, P, P, P, P, P, P, P, P, Z, I, L, F, P]),
+    "lg_gp_heads_seed": (I, [P, P, P, I, I, I, P]),
+    "lg_gp_heads_2nd": (I, [P, P, P, P, P, P, P, P, I, I, I, P]),
 }
 
 

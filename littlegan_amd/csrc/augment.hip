@@ -149,6 +149,18 @@ __global__ __launch_bounds__(256) void draws_kernel(float* __restrict__ params, 
   else flip[w - 3] = u < 0.5f ? 1 : 0;
 }
 
+// eps[b] = u_b of the gradient penalty's interpolation (gp.hip): word (b & 3) of Philox block offset + b / 4, u = (bits >> 8) / 2^24
+// in [0, 1) — the resolution and mapping of the augmentation's scalar draws (draws_kernel)
+__global__ __launch_bounds__(256) void uniform_kernel(float* __restrict__ out, int n, unsigned long long seed,
+                                                      unsigned long long offset) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long c = offset + (unsigned long long)(i >> 2);
+  const u4 r = philox4x32_10(u4{(unsigned)c, (unsigned)(c >> 32), 0u, 0u}, (unsigned)seed, (unsigned)(seed >> 32));
+  const unsigned w = (i & 3) == 0 ? r.x : (i & 3) == 1 ? r.y : (i & 3) == 2 ? r.z : r.w;
+  out[i] = (float)(w >> 8) * (1.0f / 16777216.0f);
+}
+
 inline int grid_for(long long n) {
   long long b = (n + 255) / 256;
   return (int)(b < 4096 ? (b > 0 ? b : 1) : 4096);
@@ -218,5 +230,12 @@ extern "C" int lg_augment_drawn(const float* img, float* out, int B, int H, int 
   hipLaunchKernelGGL(augment_kernel, dim3(grid_for((long long)B * H * W)), dim3(256), 0, st, img, out, (const float*)means,
                      (const unsigned char*)flip, B, H, W, 0.f, 1.f, 1.f, noise_scale, seed, noise_offset, (const float*)params);
   LG_CHECK_LAUNCH("lg_augment_drawn");
+  return LG_OK;
+}
+
+extern "C" int lg_gp_draw_eps(float* eps, int B, unsigned long long seed, unsigned long long offset, void* stream) {
+  LG_CHECK_ARG(eps && B > 0, "lg_gp_draw_eps: bad arguments");
+  hipLaunchKernelGGL(uniform_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, eps, B, seed, offset);
+  LG_CHECK_LAUNCH("lg_gp_draw_eps");
   return LG_OK;
 }

@@ -55,15 +55,16 @@ class EagerTrainer:
         self.generator = generator
         self.models = [self.discriminator, self.generator, self.adjuster]
         self.device = generator.device
-        if getattr(args, "use_gp", False):  # eager_trainer.py:141-143
-            raise NotImplementedError("GP didn't implemented on eager mode")
+        # gradient penalty on the disc tape (the reference raises here, eager_trainer.py:141-143; definition: DESIGN.md §12)
+        self.use_gp = bool(getattr(args, "use_gp", False))
         self.store = ParamStore(generator, discriminator, adjuster)
         # tf.compat.v1.train.AdamOptimizer x3 (eager_trainer.py:28-30): {beta1_power, beta2_power} per optimizer
         self.opt_cfg = {"G": (args.lr, args.beta_1, args.beta_2), "D": (args.lr, args.beta_1, args.beta_2),
                         "A": (args.lr, 0.9, 0.999)}
         self.opt_state = {m: torch.tensor([b1, b2], dtype=torch.float32, device=self.device)
                           for m, (_, b1, b2) in self.opt_cfg.items()}
-        self.losses = {k: torch.zeros(1, dtype=torch.float32, device=self.device) for k in ("gen", "disc", "adj")}
+        self.losses = {k: torch.zeros(1, dtype=torch.float32, device=self.device)
+                       for k in ("gen", "disc", "adj") + (("gp",) if self.use_gp else ())}
         self.sync = GradSync(self.device)
         self.adam_order = ("D", "G", "A")   # = the launch order of the all-reduces (see train_step_from_inputs)
         self.global_epoch = 1
@@ -85,15 +86,19 @@ class EagerTrainer:
 
     # ------------------------------------------------------------------ hot path
     def train_step_from_inputs(self, batch_no: int, inp: Dict[str, torch.Tensor]):
-        """inp: real_image_1, real_cond_1, real_image_2, real_cond_2, noise, new_image (device fp32, NHWC).
-        Returns (fake_image, adj_image|None, gen_loss, disc_loss, adj_loss|None) — losses are 1-element
-        device tensors (no host sync on the hot path)."""
+        """inp: real_image_1, real_cond_1, real_image_2, real_cond_2, noise, new_image (device fp32, NHWC); with use_gp also
+        gp_eps [B] (the penalty's interpolation weights, U[0,1)).
+        Returns (fake_image, adj_image|None, gen_loss, disc_loss, adj_loss|None) — losses are 1-element device tensors
+        (no host sync on the hot path)."""
         a = self.args
         G, D, A = self.generator, self.discriminator, self.adjuster
         img1, c1, img2, c2 = inp["real_image_1"], inp["real_cond_1"], inp["real_image_2"], inp["real_cond_2"]
         noise, new_image = inp["noise"], inp["new_image"]
         B = img1.shape[0]
         c = a.cond_dim
+        gp_eps = inp.get("gp_eps") if self.use_gp else None
+        if self.use_gp and gp_eps is None:
+            raise ValueError("train_step_from_inputs: use_gp is on and inp has no 'gp_eps' ([B] fp32 device tensor, U[0,1))")
 
         # ---- forward: fake = G(noise, c2); D on the [new_image ; fake] batch (eager_trainer.py:134-137)
         ctx_g: dict = {}
@@ -123,6 +128,11 @@ class EagerTrainer:
         # weight-gradient kernels, no all-reduce, and the backward chain stops where nothing below is asked for
         rng_d = train_weight_range(a, "D", batch_no)
         D.backward(ctx_d, dz, need_wgrad=True, need_input_grad=False, train_range=rng_d)
+        if self.use_gp:
+            # disc_loss += gp_weight * mean_b (|d output_pr(x^_b) / d x^_b| - 1)^2 on x^ = eps new_image + (1 - eps) fake; its weight
+            # gradients are added to the disc tape's before the all-reduce
+            D.gradient_penalty(ops.gp_interp(new_image, fake, gp_eps), a.gp_weight, self.losses["disc"], self.losses["gp"],
+                               train_range=rng_d)
         self.sync.launch("D", self.store, *self.store.model_range("D", *rng_d))
 
         # ---- gen tape (eager_trainer.py:140,149): BCE(.98,fake_pr) + BCE(c2,fake_c) + l1*mean|img2-fake|
@@ -244,6 +254,8 @@ class EagerTrainer:
         noise, new_image = self.draw_step_inputs(real_image_1, out=d_in[:real_image_1.shape[0]])
         inp = dict(real_image_1=real_image_1, real_cond_1=real_cond_1, real_image_2=real_image_2,
                    real_cond_2=real_cond_2, noise=noise, new_image=new_image, disc_input=d_in)
+        if self.use_gp:
+            inp["gp_eps"] = self.draw_gp_eps(real_image_1.shape[0])
         fake, adj, lg, ld, la = self.train_step_from_inputs(batch_no, inp)
         return True, fake, adj, lg, ld, la
 
@@ -263,6 +275,12 @@ class EagerTrainer:
         new_image = ops.augment_drawn(real_image_1.contiguous(), 0.02, 0.75, 1.003, 0.03, 0.1 * 0.2, seed,
                                       base + (1 << 39), base + (1 << 38), out=out)
         return noise, new_image
+
+    def draw_gp_eps(self, B):
+        """The gradient penalty's interpolation weights of the step draw_step_inputs last drew for: eps [B] ~ U[0,1) from the
+        block window at 2^37 of that step's counter window (no other draw of a step uses it), on the device."""
+        seed = (int(getattr(self.args, "seed", 0)) << 20) ^ self.rank
+        return ops.gp_draw_eps(B, seed, (self._input_step << 40) + (1 << 37), device=self.device)
 
     # ------------------------------------------------------------------ eager_trainer.py:180-229
     def _interrupted(self, signum, f_name):

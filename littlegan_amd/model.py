@@ -245,6 +245,63 @@ class Encoder(_ConvStack):
                 g_h = ops.conv2d_s2_dgrad(dz, packs[i - 1], cb, self.dtype, dy16=dz16, out_bf16=(self.dtype == DT_BF16 and i > 1))
         return g_h if need_input_grad else None
 
+    # ---- gradient penalty: the data-path backward recorded, its adjoint sweep and the second backward.
+    # The penalty's own intermediates are fp32 on both operand paths; z / statistics are whatever the forward kept.
+    def backward_recorded(self, ctx, g_last):
+        """Data-path backward of the forward recorded in ctx down to the image, KEEPING each level's output gradient g_h and
+        its dz: -> (image gradient, {level: (g_h, dz)}).  No weight gradient is touched."""
+        a = self.args.leaky_alpha
+        packs = self.packs()
+        rec = {}
+        g_h = g_last
+        for i in range(4, 0, -1):
+            cb, _ = self.chans[i - 1]
+            _, z, st, _ = ctx["enc"][i - 1]
+            dz = ops.gp_norm_bwd(z, st, self._w[f"norm{i}.gamma"], g_h, a)
+            rec[i] = (g_h, dz)
+            g_h = ops.conv2d_s2_dgrad(dz, packs[i - 1], cb, self.dtype)
+        return g_h, rec
+
+    def gp_sweep(self, ctx, rec, u0, levels, lowest):
+        """Adjoint sweep upward from u0 (the adjoint on the image gradient): per level u_dz = conv(u_h below) (no bias),
+        dW += wgrad(u_h below, dz) and the norm double backward (dgamma +=) for the trained `levels`; the second-order adjoints
+        on z for the levels >= lowest.  -> (adjoint on the top map's gradient, {level: u_z2})"""
+        a = self.args.leaky_alpha
+        packs = self.packs()
+        u_h, uz2 = u0, {}
+        for i in range(1, 5):
+            _, cs = self.chans[i - 1]
+            _, z, st, _ = ctx["enc"][i - 1]
+            g_h, dz = rec[i]
+            u = ops.conv2d_s2_fwd(u_h, packs[i - 1], None, cs, self.dtype)
+            if i in levels:
+                ops.conv2d_s2_wgrad(u_h, dz, self._g[f"conv{i}.kernel"], True, self.dtype)
+            u_h, uz2[i] = ops.gp_norm_dd(z, st, self._w[f"norm{i}.gamma"], g_h, u, a,
+                                         dgamma=self._g[f"norm{i}.gamma"] if i in levels else None, want_uz2=i >= lowest)
+        return u_h, uz2
+
+    def gp_second_backward(self, ctx, g_last, uz2, levels):
+        """The disc-tape backward of the recorded forward seeded with g_last, with u_z2 added to every level's dz (fused into
+        the norm backward); every gradient of the trained `levels` ACCUMULATES onto what the disc tape wrote."""
+        a = self.args.leaky_alpha
+        packs = self.packs()
+        lowest = min(levels)
+        g_h = g_last
+        for i in range(4, lowest - 1, -1):
+            cb, _ = self.chans[i - 1]
+            x, z, st, x16 = ctx["enc"][i - 1]
+            trained = i in levels
+            dz16 = (torch.empty(z.shape, dtype=torch.bfloat16, device=z.device)
+                    if trained and self.dtype == DT_BF16 and x16 is not None else None)
+            dz = ops.gp_norm_bwd(z, st, self._w[f"norm{i}.gamma"], g_h, a, add=uz2[i],
+                                 dgamma=self._g[f"norm{i}.gamma"] if trained else None,
+                                 dbeta=self._g[f"norm{i}.beta"] if trained else None, out16=dz16)
+            if trained:
+                ops.bias_grad(dz, self._g[f"conv{i}.bias"], accumulate=True)
+                ops.conv2d_s2_wgrad(x, dz, self._g[f"conv{i}.kernel"], True, self.dtype, x16=x16, dy16=dz16)
+            if i > lowest:
+                g_h = ops.conv2d_s2_dgrad(dz, packs[i - 1], cb, self.dtype)
+
 
 class Decoder(_ConvStack):
     """model.py:30-51.  conv_i: Conv2DTranspose(conv_filter[i], 5, (2,2), 'same') -> InstanceNorm -> leaky,
@@ -586,6 +643,30 @@ class Discriminator(_Module):
         dx = ops.heads_dgrad(dz, self._w["dense_pr.kernel"], self._w["dense_cond.kernel"])
         i, f = self.args.init_dim, self.args.conv_filter[0]
         return self.encoder.backward(ctx, dx.view(-1, i, i, f), bool(levels), need_input_grad, rows, wgrad_levels=levels)
+
+    def gradient_penalty(self, image, gp_weight: float, loss=None, gp_loss=None, train_range=None):
+        """Gradient penalty of this project (the reference raises, eager_trainer.py:141-143): image = x^ [B,H,W,C],
+        p_b = output_pr(x^_b), g_b = dp_b/dx^_b, r_b = |g_b|, gp = mean_b (r_b - 1)^2.  loss (+)= gp_weight gp, gp_loss =
+        gp_weight gp (1-element device tensors, may be None).  The gradients of gp_weight gp w.r.t. Discriminator.weights[lo:hi]
+        (train_range, default all 20) are ADDED to the gradient views (the disc tape has written them); dense_cond gets
+        nothing.  Returns r [B]."""
+        lo, hi = train_range if train_range is not None else (0, 20)
+        heads = lo <= 16 and hi >= 20
+        levels = [i for i in range(1, 5) if lo <= 4 * (i - 1) and 4 * i <= hi]
+        ctx: dict = {}
+        p = self.forward_packed(image, ctx)
+        B = image.shape[0]
+        i, f = self.args.init_dim, self.args.conv_filter[0]
+        wpr = self._w["dense_pr.kernel"]
+        g_top = ops.gp_heads_seed(p, wpr)
+        g0, rec = self.encoder.backward_recorded(ctx, g_top.view(B, i, i, f))
+        u0, r = ops.gp_seed(g0, gp_weight, loss, gp_loss)
+        u4, uz2 = self.encoder.gp_sweep(ctx, rec, u0, levels, min(levels) if levels else 5)
+        _, g2 = ops.gp_heads_2nd(p, wpr, ctx["heads_x"], u4.view(B, -1), dwpr=self._g["dense_pr.kernel"] if heads else None,
+                                 dbpr=self._g["dense_pr.bias"] if heads else None)
+        if levels:
+            self.encoder.gp_second_backward(ctx, g2.view(B, i, i, f), uz2, levels)
+        return r
 
 
 class Adjuster(_Module):

@@ -949,3 +949,131 @@ def fid_stats(act):
     ws = workspace(int(lib.lg_fid_stats_workspace_bytes(N, D)), act.device, "small")
     check(lib.lg_fid_stats(_p(act), N, D, _p(mu), _p(sigma), _p(ws), ws.numel(), _stream()), "lg_fid_stats")
     return mu, sigma
+
+
+# ------------------------------------------------------------------ discriminator gradient penalty (gp.hip)
+def gp_draw_eps(B, seed, offset, device="cuda"):
+    """eps [B] ~ U[0, 1) from the counter-based generator (lg_gp_draw_eps): the interpolation weights of the penalty."""
+    out = torch.empty(B, dtype=torch.float32, device=device)
+    check(_lib.load().lg_gp_draw_eps(_p(out), int(B), _i64(seed), _i64(offset), _stream()), "lg_gp_draw_eps")
+    return out
+
+
+def gp_interp(real, fake, eps, out=None):
+    """x^ = eps_b real_b + (1 - eps_b) fake_b"""
+    _chk(real, name="real")
+    _chk(fake, real.shape, "fake")
+    B = real.shape[0]
+    _chk(eps, (B,), "eps")
+    if out is None:
+        out = torch.empty_like(real)
+    _chk(out, real.shape, "out")
+    check(_lib.load().lg_gp_interp(_p(real), _p(fake), _p(eps), _p(out), B, real.numel() // B, _stream()), "lg_gp_interp")
+    return out
+
+
+def _gp_ws(B, L, device):
+    return workspace(int(_lib.load().lg_gp_workspace_bytes(B, L)), device, "gp")
+
+
+def gp_seed(g, gp_weight, loss=None, gp_loss=None):
+    """g = the image gradient of p: -> (u0 = d(gp_weight gp)/dg, r [B]); loss (+)= gp_weight gp, gp_loss = gp_weight gp"""
+    _chk(g, name="g")
+    B = g.shape[0]
+    L = g.numel() // B
+    for t, nm in ((loss, "loss"), (gp_loss, "gp_loss")):
+        if t is not None:
+            _chk(t, (1,), nm)
+    u0 = torch.empty_like(g)
+    r = torch.empty(B, dtype=torch.float32, device=g.device)
+    ws = _gp_ws(B, L, g.device)
+    check(_lib.load().lg_gp_seed(_p(g), _p(u0), _p(r), _p(loss), _p(gp_loss), float(gp_weight), _p(ws), ws.numel(), B, L,
+                                 _stream()), "lg_gp_seed")
+    return u0, r
+
+
+def _gp_z(z, g, stats, gamma):
+    B = z.shape[0]
+    if z.dtype == torch.bfloat16:
+        _chk16(z, z, "z")
+    else:
+        _chk(z, name="z")
+    _chk(g, z.shape, "g")
+    _chk(stats, (B, NSTAT), "stats")
+    _chk(gamma, (1,), "gamma")
+    return (None, z) if z.dtype == torch.bfloat16 else (z, None)
+
+
+def gp_norm_bwd(z, stats, gamma, g, alpha, add=None, dgamma=None, dbeta=None, out16=None, want_f32=True):
+    """first-order InstanceNorm + LeakyReLU backward of a level (z: fp32 or its bf16 raw output) with an optional injected
+    adjoint `add` on dz; dgamma / dbeta (+)= when given.  Returns dz (fp32, or None with want_f32=False: only out16)."""
+    z32, z16 = _gp_z(z, g, stats, gamma)
+    B = z.shape[0]
+    L = z.numel() // B
+    if add is not None:
+        _chk(add, z.shape, "add")
+    for t, nm in ((dgamma, "dgamma"), (dbeta, "dbeta")):
+        if t is not None:
+            _chk(t, (1,), nm)
+    if out16 is not None:
+        _chk16(out16, z, "out16")
+    elif not want_f32:
+        raise ValueError("gp_norm_bwd: want_f32=False needs out16")
+    dz = torch.empty(z.shape, dtype=torch.float32, device=z.device) if want_f32 else None
+    ws = _gp_ws(B, L, z.device)
+    e0 = _pb()
+    check(_lib.load().lg_gp_norm_bwd(_p(z32), _p(z16), _p(stats), _p(gamma), _p(g), _p(add), _p(dz), _p(out16), _p(dgamma),
+                                     _p(dbeta), _p(ws), ws.numel(), B, L, float(alpha), _stream()), "lg_gp_norm_bwd")
+    _pe(e0, "gp_norm", 0.0)
+    return dz
+
+
+def gp_norm_dd(z, stats, gamma, g, u, alpha, dgamma=None, want_uz2=True):
+    """double backward of the level's InstanceNorm + LeakyReLU along the adjoint u of its dz -> (u_h, u_z2 | None)"""
+    z32, z16 = _gp_z(z, g, stats, gamma)
+    B = z.shape[0]
+    L = z.numel() // B
+    _chk(u, z.shape, "u")
+    if dgamma is not None:
+        _chk(dgamma, (1,), "dgamma")
+    uh = torch.empty(z.shape, dtype=torch.float32, device=z.device)
+    uz2 = torch.empty(z.shape, dtype=torch.float32, device=z.device) if want_uz2 else None
+    ws = _gp_ws(B, L, z.device)
+    e0 = _pb()
+    check(_lib.load().lg_gp_norm_dd(_p(z32), _p(z16), _p(stats), _p(gamma), _p(g), _p(u), _p(uh), _p(uz2), _p(dgamma), _p(ws),
+                                    ws.numel(), B, L, float(alpha), _stream()), "lg_gp_norm_dd")
+    _pe(e0, "gp_norm", 0.0)
+    return uh, uz2
+
+
+def gp_heads_seed(p, wpr):
+    """g [B, K] = p_b (1 - p_b) wpr: the gradient of output_pr on the heads input"""
+    _chk(p, name="p")
+    B, J = p.shape
+    K = wpr.shape[0]
+    _chk(wpr, (K, 1), "wpr")
+    g = torch.empty(B, K, dtype=torch.float32, device=p.device)
+    check(_lib.load().lg_gp_heads_seed(_p(p), _p(wpr), _p(g), B, K, J - 1, _stream()), "lg_gp_heads_seed")
+    return g
+
+
+def gp_heads_2nd(p, wpr, x, u, dwpr=None, dbpr=None):
+    """second order at the heads along the adjoint u [B, K] -> (t [B], g2 [B, K] = t_b wpr); dwpr / dbpr (+)= when given"""
+    _chk(p, name="p")
+    B, J = p.shape
+    K = wpr.shape[0]
+    _chk(wpr, (K, 1), "wpr")
+    _chk(u, (B, K), "u")
+    if x is not None:
+        _chk(x, (B, K), "x")
+    if dwpr is not None:
+        _chk(dwpr, (K, 1), "dwpr")
+        if x is None:
+            raise ValueError("gp_heads_2nd: dwpr needs the heads input x")
+    if dbpr is not None:
+        _chk(dbpr, (1,), "dbpr")
+    t = torch.empty(B, dtype=torch.float32, device=p.device)
+    g2 = torch.empty(B, K, dtype=torch.float32, device=p.device)
+    check(_lib.load().lg_gp_heads_2nd(_p(p), _p(wpr), _p(x), _p(u), _p(t), _p(g2), _p(dwpr), _p(dbpr), B, K, J - 1, _stream()),
+          "lg_gp_heads_2nd")
+    return t, g2
