@@ -281,6 +281,26 @@ int lg_augment_drawn(const float* img, float* out, int B, int H, int W, float db
                      float noise_scale, unsigned long long seed, unsigned long long draw_offset,
                      unsigned long long noise_offset, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- input side from a packed uint8 data set (input_u8.hip) ------------------------------------------- */
+/* src: uint8 rows of row_elems bytes (the resident data set [N][H][W][3], or a streamed [B][H][W][3] slot); idx[B]: int64 row
+ * numbers on the device, every one a valid row of src (the kernels cannot check that).
+ * out[b][e] = (float)src[idx[b]][e] / 127.5f - 1.0f  (data_rescale, utils.py:51-52; a correctly rounded division).
+ * 16-byte loads and stores when row_elems % 16 == 0 and src, out are 16-byte aligned; one element per thread otherwise. */
+int lg_rescale_u8(const unsigned char* src, const long long* idx, int B, long long row_elems, float* out, void* stream);
+/* out[b][j] = 0.96f * attr[idx[b]][cols[j]] + 0.02f  (soft, utils.py:47-48; product rounded, then the sum);
+ * attr float32 [N][A_all], cols[c] int32 column numbers on the device */
+int lg_soft_labels(const float* attr, const long long* idx, const int* cols, int B, int A_all, int c, float* out,
+                   void* stream);
+size_t lg_augment_drawn_u8_workspace_bytes(int B);
+/* lg_augment_drawn on the rows idx[B] of a uint8 [N][H][W][3] source, rescaled on load: out_aug [B][H][W][3] is bit for
+ * bit lg_augment_drawn(lg_rescale_u8(src, idx)) for the same seed and offsets, out_rescaled (may be null) is bit for bit
+ * lg_rescale_u8(src, idx); each source byte is read once by the pass that writes both.  16-byte stores when W % 4 == 0,
+ * src is 4-byte and the outputs are 16-byte aligned. */
+int lg_augment_drawn_u8(const unsigned char* src, const long long* idx, float* out_aug, float* out_rescaled, int B, int H,
+                        int W, float db_max, float c_lo, float c_hi, float dh_max, float noise_scale,
+                        unsigned long long seed, unsigned long long draw_offset, unsigned long long noise_offset,
+                        void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- FID activation statistics  fid.py:185-188 ----------------------------------------------- */
 /* mu[D] = mean over the N samples, sigma[D][D] = np.cov(act, rowvar=False) (divisor N - 1) of act[N][D] (fp32), both fp64
  * on the device; Gram matrix of the centred activations on the fp64 matrix instruction.  N >= 2. */

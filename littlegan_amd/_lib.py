@@ -109,6 +109,11 @@ SIGNATURES = {
     "lg_gp_norm_dd": (I, [P, P, P, P, P, P, P, P, P, P, Z, I, L, F, P]),
     "lg_gp_heads_seed": (I, [P, P, P, I, I, I, P]),
     "lg_gp_heads_2nd": (I, [P, P, P, P, P, P, P, P, I, I, I, P]),
+    # packed uint8 data set: gather + rescale, labels, fused augmentation (input_u8.hip)
+    "lg_rescale_u8": (I, [P, P, I, L, P, P]),
+    "lg_soft_labels": (I, [P, P, P, I, I, I, P, P]),
+    "lg_augment_drawn_u8_workspace_bytes": (Z, [I]),
+    "lg_augment_drawn_u8": (I, [P, P, P, P, I, I, I, F, F, F, F, F, L, L, L, P, Z, P]),
 }
 
 

@@ -1,6 +1,7 @@
 """Mirror of /root/reference/config.py:6-42: sample.config.json < <env>.config.json < CLI, every key an
 attribute, derived cond_dim / result_dir / gpu / prefetch.  Extra keys of this build: mfma_dtype ("f32" |
-"bf16"), synthetic (bool: use the synthetic CelebA-shaped dataset), seed."""
+"bf16"), synthetic (bool: use the synthetic CelebA-shaped dataset), seed, packed_path / data_resident / fuse_input
+(the packed uint8 data set, dataset.py)."""
 import json
 import os
 from argparse import ArgumentParser
@@ -48,9 +49,12 @@ DEFAULTS = {
     'threads': 8,
     # keys added by this build
     'mfma_dtype': 'f32', 'synthetic': False, 'seed': 0,
+    # packed uint8 data set: directory written by `main.py pack`; where its bytes live ("auto" | true | false);
+    # whether the step reads the bytes through the fused u8 input kernels
+    'packed_path': None, 'data_resident': 'auto', 'fuse_input': True,
 }
 
-MODES = ["train", "plot", "visual", "random-sample", "evaluate", "condition-sample", "evaluate-sample", "export-model"]
+MODES = ["train", "pack", "plot", "visual", "random-sample", "evaluate", "condition-sample", "evaluate-sample", "export-model"]
 
 
 class Arg:

@@ -6,7 +6,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
-SOURCES = ["capi.hip", "conv_igemm.hip", "conv_halo.hip", "conv_down3.hip", "conv_up3.hip", "n3_kernels.hip", "n3_pgemm.hip", "wgrad_igemm.hip", "pack.hip", "norm.hip", "dense.hip", "heads.hip", "loss_optim.hip", "augment.hip", "fid.hip", "wgrad_at.hip", "wgrad_at32.hip", "n3_rows.hip", "skinny_mfma.hip", "conv_up4.hip", "runtime.hip", "gp.hip"]
+SOURCES = ["capi.hip", "conv_igemm.hip", "conv_halo.hip", "conv_down3.hip", "conv_up3.hip", "n3_kernels.hip", "n3_pgemm.hip", "wgrad_igemm.hip", "pack.hip", "norm.hip", "dense.hip", "heads.hip", "loss_optim.hip", "augment.hip", "fid.hip", "wgrad_at.hip", "wgrad_at32.hip", "n3_rows.hip", "skinny_mfma.hip", "conv_up4.hip", "runtime.hip", "gp.hip", "input_u8.hip"]
 LIB = os.path.join(PKG, "liblittlegan_hip.so")
 # -packed-fp32-ops (round 5): no v_pk_{add,mul,fma}_f32 anywhere in the library.  The one kernel build that ever gave launch-to-launch
 # different results lost the low half of a packed fp32 subtraction (VGPR pair, high-register select) with a second wave on the SIMD; without
@@ -38,9 +38,11 @@ def build(force=False, verbose=True, variant=None):
         raise SystemExit("LG_EXTRA_FLAGS needs --variant NAME: ablation builds never replace the product library")
     os.makedirs(objdir, exist_ok=True)
     common_h, public_h = os.path.join(HERE, "lg_common.h"), os.path.join(os.path.dirname(PKG), "include", "littlegan_hip.h")
+    augment_h = os.path.join(HERE, "augment_core.h")
 
     def hdrs_of(path):   # the public header is a dependency of the sources that include it (capi.hip, runtime.hip), not of every kernel file
-        return [common_h] + ([public_h] if "littlegan_hip.h" in open(path).read() else [])
+        text = open(path).read()   # augment_core.h: the device code augment.hip and input_u8.hip share
+        return [common_h] + ([public_h] if "littlegan_hip.h" in text else []) + ([augment_h] if "augment_core.h" in text else [])
 
     # LG_EXTRA_FLAGS carries the ablation macros of scripts/probe/*.sh ("results wrong, timing only"): the flag set an object
     # was built with is recorded beside it, and an object (hence the library) built with OTHER flags is stale — a probe build

@@ -242,6 +242,8 @@ class EagerTrainer:
 
     # ------------------------------------------------------------------ eager_trainer.py:115-169
     def _train_step(self, batch_no, iterator):
+        if hasattr(iterator, "get_next_raw") and getattr(self.args, "fuse_input", True):
+            return self._train_step_packed(batch_no, iterator)
         try:
             real_image_1, real_cond_1 = iterator.get_next()
             real_image_2, real_cond_2 = iterator.get_next()
@@ -258,6 +260,43 @@ class EagerTrainer:
             inp["gp_eps"] = self.draw_gp_eps(real_image_1.shape[0])
         fake, adj, lg, ld, la = self.train_step_from_inputs(batch_no, inp)
         return True, fake, adj, lg, ld, la
+
+    def _train_step_packed(self, batch_no, iterator):
+        """_train_step on a packed uint8 data set: the batches arrive as row indices into bytes on the device
+        and the fused input kernels produce, bit for bit, the dict the float32 path builds."""
+        if not iterator.has_next():
+            return None,
+        raw = iterator.get_next_raw()
+        if not iterator.has_next():   # an odd batch at the end of the epoch: the float32 path draws nothing for it either
+            raw.release()
+            iterator.close()
+            return None,
+        B = raw.idx.shape[0]
+        d_in = torch.empty((2 * B,) + tuple(raw.src.shape[1:]), dtype=torch.float32, device=self.device)
+        noise, new_image, real_image_1 = self.draw_step_inputs_u8(raw.src, raw.idx, out=d_in[:B])
+        raw.release()   # batch 1's bytes are consumed: its slot may be refilled (streamed mode; at least 1 slot in the ring)
+        real_cond_1 = raw.cond
+        raw = iterator.get_next_raw()
+        real_image_2, real_cond_2 = ops.rescale_u8(raw.src, raw.idx), raw.cond
+        raw.release()
+        inp = dict(real_image_1=real_image_1, real_cond_1=real_cond_1, real_image_2=real_image_2,
+                   real_cond_2=real_cond_2, noise=noise, new_image=new_image, disc_input=d_in)
+        if self.use_gp:
+            inp["gp_eps"] = self.draw_gp_eps(B)
+        fake, adj, lg, ld, la = self.train_step_from_inputs(batch_no, inp)
+        return True, fake, adj, lg, ld, la
+
+    def draw_step_inputs_u8(self, src, idx, out=None):
+        """draw_step_inputs for a batch that is still bytes: the same step counter, seed and Philox windows; returns
+        (noise, new_image, real_image_1), the last being the plain rescaled batch the same pass writes."""
+        a = self.args
+        self._input_step += 1
+        seed = (int(getattr(a, "seed", 0)) << 20) ^ self.rank
+        base = self._input_step << 40
+        noise = ops.randn((a.batch_size, a.noise_dim), seed, base, device=self.device)
+        new_image, real_image_1 = ops.augment_drawn_u8(src, idx, 0.02, 0.75, 1.003, 0.03, 0.1 * 0.2, seed, base + (1 << 39),
+                                                       base + (1 << 38), out=out)
+        return noise, new_image, real_image_1
 
     def draw_step_inputs(self, real_image_1, out=None):
         """eager_trainer.py:125-131 on the device: noise ~ N(0,1) and the augmented copy of the first real batch.  All

@@ -937,6 +937,65 @@ def augment_drawn(img, db_max, c_lo, c_hi, dh_max, noise_scale, seed, draw_offse
     return out
 
 
+
+# ------------------------------------------------------------------ packed uint8 data set (input_u8.hip)
+def _chk_rows(src, idx, name):
+    """src: contiguous uint8 CUDA tensor [N, ...]; idx: contiguous int64 CUDA vector of row numbers (the kernels trust them)"""
+    if not (src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() >= 2):
+        raise ValueError(f"{name}: src must be a contiguous uint8 CUDA tensor [N, ...], got {src.dtype} {src.device}")
+    if not (idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous() and idx.dim() == 1 and idx.numel() > 0):
+        raise ValueError(f"{name}: idx must be a non-empty contiguous int64 CUDA vector, got {idx.dtype} {idx.device}")
+
+
+def rescale_u8(src, idx, out=None):
+    """lg_rescale_u8: out[b] = data_rescale(src[idx[b]]) as float32, shape [B, *src.shape[1:]]."""
+    _chk_rows(src, idx, "rescale_u8")
+    B, row = idx.numel(), src[0].numel()
+    if out is None:
+        out = torch.empty((B,) + tuple(src.shape[1:]), dtype=torch.float32, device=src.device)
+    _chk(out, (B,) + tuple(src.shape[1:]), "out")
+    check(_lib.load().lg_rescale_u8(_p(src), _p(idx), B, row, _p(out), _stream()), "lg_rescale_u8")
+    return out
+
+
+def soft_labels(attr, idx, cols, out=None):
+    """lg_soft_labels: out[b][j] = soft(attr[idx[b]][cols[j]]); attr fp32 [N, A_all], cols int32 [c], both on the device."""
+    _chk(attr, name="attr")
+    if not (idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous() and idx.dim() == 1 and idx.numel() > 0):
+        raise ValueError("soft_labels: idx must be a non-empty contiguous int64 CUDA vector")
+    if not (cols.is_cuda and cols.dtype == torch.int32 and cols.is_contiguous() and cols.dim() == 1 and cols.numel() > 0):
+        raise ValueError("soft_labels: cols must be a non-empty contiguous int32 CUDA vector")
+    B, c = idx.numel(), cols.numel()
+    if out is None:
+        out = torch.empty((B, c), dtype=torch.float32, device=attr.device)
+    _chk(out, (B, c), "out")
+    check(_lib.load().lg_soft_labels(_p(attr), _p(idx), _p(cols), B, attr.shape[1], c, _p(out), _stream()), "lg_soft_labels")
+    return out
+
+
+def augment_drawn_u8(src, idx, db_max, c_lo, c_hi, dh_max, noise_scale, seed, draw_offset, noise_offset, out=None,
+                     out_rescaled=None, want_rescaled=True):
+    """lg_augment_drawn_u8: (augment_drawn(rescale_u8(src, idx)), rescale_u8(src, idx)) from one read of the bytes; the
+    second is None when want_rescaled is false.  src uint8 [N, H, W, 3]."""
+    _chk_rows(src, idx, "augment_drawn_u8")
+    if src.dim() != 4 or src.shape[3] != 3:
+        raise ValueError("augment_drawn_u8: 3-channel [N, H, W, 3] images only")
+    B, (H, W) = idx.numel(), src.shape[1:3]
+    if out is None:
+        out = torch.empty((B, H, W, 3), dtype=torch.float32, device=src.device)
+    _chk(out, (B, H, W, 3), "out")
+    if want_rescaled and out_rescaled is None:
+        out_rescaled = torch.empty((B, H, W, 3), dtype=torch.float32, device=src.device)
+    if out_rescaled is not None:
+        _chk(out_rescaled, (B, H, W, 3), "out_rescaled")
+    lib = _lib.load()
+    ws = workspace(int(lib.lg_augment_drawn_u8_workspace_bytes(B)), src.device, "small")
+    check(lib.lg_augment_drawn_u8(_p(src), _p(idx), _p(out), _p(out_rescaled), B, H, W, float(db_max), float(c_lo), float(c_hi),
+                                  float(dh_max), float(noise_scale), _i64(seed), _i64(draw_offset), _i64(noise_offset), _p(ws),
+                                  ws.numel(), _stream()), "lg_augment_drawn_u8")
+    return out, out_rescaled
+
+
 def fid_stats(act):
     """fid.py:185-188 on the device: (mu [D], sigma [D, D]) fp64 tensors of act [N, D] (fp32 CUDA)."""
     if act.dim() != 2 or act.shape[0] < 2:

@@ -1,5 +1,5 @@
 """CLI mirror of /root/reference/main.py on the HIP hot path:  python main.py <mode> <exp_name> [-e env] [-g gpus] [--debug]
-Modes kept: train, random-sample, condition-sample, evaluate-sample, evaluate, export-model.  `evaluate` runs the FID
+Modes kept: train, pack (decode the image folder once into the uint8 pack `packed_path` names), random-sample, condition-sample, evaluate-sample, evaluate, export-model.  `evaluate` runs the FID
 arithmetic (main.py:82-104 -> evaluate.py calc) on SAVED Inception activations of the evaluate-sample images: the frozen
 Inception graph the reference downloads cannot be obtained here.  `visual` (tensorboard) and `plot` (pydot) are UI tooling
 outside the hot path."""
@@ -14,6 +14,13 @@ from littlegan_amd.config import Arg
 # configuration files are looked up next to this script (the reference reads them from the working directory);
 # LITTLEGAN_CONFIG_DIR points somewhere else (tests)
 args = Arg(config_dir=os.environ.get("LITTLEGAN_CONFIG_DIR", os.path.dirname(os.path.abspath(__file__))))
+
+if args.mode == "pack":  # host only: decode image_path once into the uint8 pack at packed_path (no GPU, no networks)
+    from littlegan_amd.dataset import pack_dataset
+    if not args.packed_path:
+        raise SystemExit("pack: set packed_path (the directory the pack is written to) in the configuration")
+    print("packed %d images into %s" % (pack_dataset(args, args.packed_path), args.packed_path))
+    raise SystemExit(0)
 
 from littlegan_amd.dataset import CelebA
 from littlegan_amd.eager_trainer import EagerTrainer
