@@ -14,10 +14,14 @@ parser.add_argument("stats_path")
 parser.add_argument("model_path")
 parser.add_argument("output_file", nargs="?", default=None)
 parser.add_argument("--gpu", default="")
+parser.add_argument("--chunk-rows", type=int, default=None,
+                    help="stream the activations in blocks of this many rows (ActivationAccumulator) instead of loading them whole")
+parser.add_argument("--device-sqrt", action="store_true",
+                    help="tr sqrt(S1 S2) by the fp64 Newton-Schulz iteration (on the GPU when there is one) instead of scipy's sqrtm")
 args = parser.parse_args()
 if args.mode == "pre-calculate":
-    fid.pre_calculate(args.image_path, args.stats_path)
+    fid.pre_calculate(args.image_path, args.stats_path, chunk_rows=args.chunk_rows, device_sqrt=args.device_sqrt)
 else:
     if args.output_file is None:
         parser.error("calc needs an output log file")
-    fid.calc(args.image_path, args.stats_path, args.output_file)
+    fid.calc(args.image_path, args.stats_path, args.output_file, chunk_rows=args.chunk_rows, device_sqrt=args.device_sqrt)

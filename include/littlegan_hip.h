@@ -308,6 +308,35 @@ size_t lg_fid_stats_workspace_bytes(long long N, int D);
 int lg_fid_stats(const float* act, long long N, int D, double* mu, double* sigma, void* workspace, size_t ws_bytes,
                  void* stream);
 
+/* ---- streaming, mergeable FID statistics  fid.py:185-188 batch by batch / rank by rank ------------------ */
+/* State (fp64, device, zero before the first batch): sum[D] = S (x - shift), gram = S (x - shift)(x - shift)^T kept as PACKED
+ * upper-triangular 64 x 64 tiles: with nt = ceil(D / 64), tile (ti <= tj) is number ti nt - ti (ti - 1) / 2 + (tj - ti) and holds
+ * 4096 doubles [row in tile][column in tile]; nt (nt + 1) / 2 * 4096 doubles in all, entries past D stay 0.  Every field is a plain
+ * sum over samples: two states with the same shift merge by addition (one all-reduce SUM over ranks).  One block owns one tile and
+ * adds into it, no atomics: bit-reproducible for a given sequence of batches.  n >= 1; shift (may be null = zeros) is fixed for the
+ * life of the state.  Replaces np.mean / np.cov of the whole activation matrix (fid.py:185-188). */
+int lg_fid_accum(const float* act, long long n, int D, const double* shift /* may be null */,
+                 double* sum, double* gram, void* stream);
+/* mu[D] = shift + sum / N, sigma[D][D] = (gram - sum sum^T / N) / (N - 1), the lower triangle the mirror of the upper
+ * (sigma == sigma^T bit for bit, as lg_fid_stats).  N >= 2 = samples accumulated.  Replaces fid.py:185-188. */
+int lg_fid_finalize(const double* sum, const double* gram, const double* shift /* may be null */,
+                    long long N, int D, double* mu, double* sigma, void* stream);
+
+/* ---- Frechet distance on the device  replaces the host sqrtm of fid.py:144-163 ------------------------------- */
+/* c = alpha_beta[0] a b + alpha_beta[1] I: D x D row-major fp64 on the device (any D >= 1; c must not alias a or b), on the fp64
+ * matrix instruction; alpha_beta points to 2 doubles in HOST memory. */
+int lg_fid_gemm(const double* a, const double* b, double* c, int D, const double* alpha_beta /* host [2] */, void* stream);
+/* d2 = |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr sqrt(S1 S2) (fid.py:112-163), the trace of the root by the coupled Newton-Schulz
+ * iteration in fp64 (c = |S1 S2|_F, Y0 = S1 S2 / c, Z0 = I, T = (3 I - Z Y) / 2, Y <- Y T, Z <- T Z, t_k = sqrt(c) tr Y_k).  Stops
+ * with t_k when |t_k - t_{k-1}| <= 1e-12 |t_k|; with t_{k-1} when the step has stopped shrinking while <= 1e-5 |t_k| (the rounding
+ * floor of a rank-deficient product).  status 0 = converged; 1 = t_k not finite or max_iter reached (the call still returns LG_OK,
+ * the caller falls back to the host root).  mu / sigma on the device, result_host 4 doubles in HOST memory.
+ * THE CALL SYNCHRONISES THE STREAM after every iteration (the driver loop decides on the host): it cannot be captured in a graph. */
+size_t lg_fid_distance_workspace_bytes(int D);
+int lg_fid_distance(const double* mu1, const double* sigma1, const double* mu2, const double* sigma2,
+                    int D, int max_iter, double* result_host /* [4]: d2, tr_sqrt, iterations, status */,
+                    void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- discriminator gradient penalty (use_gp / gp_weight, sample.config.json:35-36) ------------------------------------ *
  * Replaces the NotImplementedError of eager_trainer.py:141-143 ("todo: explore how to gp on eager mode").  The reference never
  * defined the penalty; THIS PROJECT's definition (WGAN-GP, Gulrajani et al. 2017, on D's first output) is:

@@ -92,6 +92,12 @@ SIGNATURES = {
     "lg_augment": (I, [P, P, I, I, I, P, F, F, F, F, L, L, P, Z, P]),
     "lg_fid_stats_workspace_bytes": (Z, [L, I]),
     "lg_fid_stats": (I, [P, L, I, P, P, P, Z, P]),
+    # streaming statistics + the Frechet distance on the device (fid.hip, fid_sqrt.hip); replace fid.py:185-188 / :144-163
+    "lg_fid_accum": (I, [P, L, I, P, P, P, P]),
+    "lg_fid_finalize": (I, [P, P, P, L, I, P, P, P]),
+    "lg_fid_gemm": (I, [P, P, P, I, P, P]),
+    "lg_fid_distance_workspace_bytes": (Z, [I]),
+    "lg_fid_distance": (I, [P, P, P, P, I, I, P, P, Z, P]),
     "lg_augment_drawn_workspace_bytes": (Z, [I]),
     "lg_device_cus": (I, []),
     "lg_set_reserved_cus": (I, [I]),

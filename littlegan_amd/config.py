@@ -1,7 +1,7 @@
 """Mirror of /root/reference/config.py:6-42: sample.config.json < <env>.config.json < CLI, every key an
 attribute, derived cond_dim / result_dir / gpu / prefetch.  Extra keys of this build: mfma_dtype ("f32" |
 "bf16"), synthetic (bool: use the synthetic CelebA-shaped dataset), seed, packed_path / data_resident / fuse_input
-(the packed uint8 data set, dataset.py)."""
+(the packed uint8 data set, dataset.py), fid_chunk_rows / fid_device_sqrt (streamed FID statistics, device square root, fid.py)."""
 import json
 import os
 from argparse import ArgumentParser
@@ -52,6 +52,9 @@ DEFAULTS = {
     # packed uint8 data set: directory written by `main.py pack`; where its bytes live ("auto" | true | false);
     # whether the step reads the bytes through the fused u8 input kernels
     'packed_path': None, 'data_resident': 'auto', 'fuse_input': True,
+    # FID pass: rows per streamed block of activations (null: the whole matrix at once, the present path); whether
+    # tr sqrt(S1 S2) is taken on the device by the fp64 Newton-Schulz iteration instead of scipy's sqrtm
+    'fid_chunk_rows': None, 'fid_device_sqrt': False,
 }
 
 MODES = ["train", "pack", "plot", "visual", "random-sample", "evaluate", "condition-sample", "evaluate-sample", "export-model"]

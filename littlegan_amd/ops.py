@@ -1010,6 +1010,80 @@ def fid_stats(act):
     return mu, sigma
 
 
+def fid_gram_elems(D):
+    """doubles in the packed upper-triangular 64 x 64 tile image of a D x D Gram matrix (lg_fid_accum)"""
+    nt = (int(D) + 63) // 64
+    return nt * (nt + 1) // 2 * 4096
+
+
+def _chk64(t, shape, name):
+    if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()) or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: need a contiguous fp64 CUDA tensor of shape {tuple(shape)}, got {t.dtype} {t.device} {tuple(t.shape)}")
+    return t
+
+
+def fid_accum(act, sum, gram, shift=None):
+    """fid.py:185-188 batch by batch: sum [D] += S (x - shift), gram [fid_gram_elems(D)] += S (x - shift)(x - shift)^T (packed
+    upper-triangular tiles) over the rows of act [n >= 1, D] (fp32 CUDA).  sum / gram: fp64, zero before the first batch."""
+    if act.dim() != 2 or act.shape[0] < 1:
+        raise ValueError("fid_accum: need an [n >= 1, D] matrix")
+    _chk(act, name="act")
+    n, D = act.shape
+    _chk64(sum, (D,), "sum")
+    _chk64(gram, (fid_gram_elems(D),), "gram")
+    if shift is not None:
+        _chk64(shift, (D,), "shift")
+    check(_lib.load().lg_fid_accum(_p(act), n, D, _p(shift), _p(sum), _p(gram), _stream()), "lg_fid_accum")
+
+
+def fid_finalize(sum, gram, count, shift=None):
+    """(mu [D], sigma [D, D]) fp64 from the accumulated state of `count` >= 2 samples; sigma is exactly symmetric."""
+    if sum.dim() != 1 or int(count) < 2:
+        raise ValueError("fid_finalize: need a [D] sum and at least 2 samples")
+    D = sum.shape[0]
+    _chk64(sum, (D,), "sum")
+    _chk64(gram, (fid_gram_elems(D),), "gram")
+    if shift is not None:
+        _chk64(shift, (D,), "shift")
+    mu = torch.empty(D, dtype=torch.float64, device=sum.device)
+    sigma = torch.empty(D, D, dtype=torch.float64, device=sum.device)
+    check(_lib.load().lg_fid_finalize(_p(sum), _p(gram), _p(shift), int(count), D, _p(mu), _p(sigma), _stream()), "lg_fid_finalize")
+    return mu, sigma
+
+
+def fid_gemm(a, b, alpha=1.0, beta=0.0):
+    """alpha a b + beta I of two [D, D] fp64 CUDA matrices on the fp64 matrix instruction (the GEMM of lg_fid_distance; tests, bench)."""
+    if a.dim() != 2 or a.shape[0] != a.shape[1]:
+        raise ValueError("fid_gemm: need square matrices")
+    D = a.shape[0]
+    _chk64(a, (D, D), "a")
+    _chk64(b, (D, D), "b")
+    import ctypes
+    c = torch.empty_like(a)
+    ab = (ctypes.c_double * 2)(float(alpha), float(beta))
+    check(_lib.load().lg_fid_gemm(_p(a), _p(b), _p(c), D, ctypes.addressof(ab), _stream()), "lg_fid_gemm")
+    return c
+
+
+def fid_distance(mu1, s1, mu2, s2, max_iter=100):
+    """Frechet distance (fid.py:112-163) with tr sqrt(S1 S2) by the coupled Newton-Schulz iteration on the device, fp64.
+    -> (d2, tr_sqrt, iterations, status); status 1 = not converged.  Synchronises the stream; not capturable in a graph."""
+    if mu1.dim() != 1 or int(max_iter) < 1:
+        raise ValueError("fid_distance: need [D] means and max_iter >= 1")
+    D = mu1.shape[0]
+    _chk64(mu1, (D,), "mu1")
+    _chk64(mu2, (D,), "mu2")
+    _chk64(s1, (D, D), "sigma1")
+    _chk64(s2, (D, D), "sigma2")
+    import ctypes
+    lib = _lib.load()
+    ws = workspace(int(lib.lg_fid_distance_workspace_bytes(D)), mu1.device, "fid_sqrt")
+    res = (ctypes.c_double * 4)()
+    check(lib.lg_fid_distance(_p(mu1), _p(s1), _p(mu2), _p(s2), D, int(max_iter), ctypes.addressof(res), _p(ws), ws.numel(), _stream()),
+          "lg_fid_distance")
+    return float(res[0]), float(res[1]), int(res[2]), int(res[3])
+
+
 # ------------------------------------------------------------------ discriminator gradient penalty (gp.hip, DESIGN.md §12)
 def gp_draw_eps(B, seed, offset, device="cuda"):
     """eps [B] ~ U[0, 1) from the counter-based generator (lg_gp_draw_eps): the interpolation weights of the penalty."""

@@ -91,7 +91,8 @@ elif args.mode == "evaluate":
     for kind in ["gen"] + (["adj"] if args.train_adj else []):
         print("Running: \"evaluate calc %s\"" % kind)
         fid.calc(path.join(args.result_dir, "evaluate", kind), path.join(args.test_data_dir, args.evaluate_pre_calculated),
-                 path.join(args.result_dir, "evaluate", "fid-%s.log" % kind))
+                 path.join(args.result_dir, "evaluate", "fid-%s.log" % kind),
+                 chunk_rows=args.fid_chunk_rows, device_sqrt=args.fid_device_sqrt)   # under torchrun: each rank its share, all-reduced
 elif args.mode == "condition-sample":
     args.reuse = True
     model = EagerTrainer(args, generator, discriminator, adjuster, None)
