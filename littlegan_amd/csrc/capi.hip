@@ -44,10 +44,10 @@ extern "C" int lg_n3_s1_dgrad_p16_try(const float* dpre, const float* w, float* 
 extern "C" int lg_n3_rows_supported(int H, int W, int C);
 extern "C" int lg_n3_s1t_fwd_rows_try(const void* x16, const float* stats, float alpha, const float* w, const float* bias, float* y,
                                       int B, int H, int W, int C, void* stream);
-static bool n3_enabled() {
+extern "C" int lg_n3_enabled(void) {
   static int v = -1;
-  if (v < 0) v = lg_env_flag("LG_NO_N3") ? 0 : 1;  // A/B switch
-  return v == 1;
+  if (v < 0) v = lg_env_flag("LG_NO_N3") ? 0 : 1;  // kill switch of the 3-channel kernels (cached: per-launch path)
+  return v;
 }
 static inline const float* raw_pack(const void* pack, int cb, int cs, int dtype) {
   return (const float*)((const char*)pack + lg_conv_pack_raw_offset(cb, cs, dtype));
@@ -70,8 +70,8 @@ extern "C" int lg_n3_conv1_p16_supported(int H, int W, int N);
 // The bf16 activation path asks BEFORE the call, because only then may the conv write its result as bf16 alone.
 extern "C" int lg_conv_fwd_stats_fused(int up, int dtype, int B, int Hs, int Ws, int cb, int cs) {
   if (B <= 0 || Hs <= 0 || Ws <= 0) return 0;
-  if (cb == 3) return (!up && dtype == LG_DT_BF16 && n3_enabled() && lg_n3_conv1_p16_supported(Hs, Ws, cs)) ? 1 : 0;
-  if (lg_env_flag("LG_NO_HALO")) return 0;
+  if (cb == 3) return (!up && dtype == LG_DT_BF16 && lg_n3_enabled() && lg_n3_conv1_p16_supported(Hs, Ws, cs)) ? 1 : 0;
+  if (!lg_halo_enabled()) return 0;
   if ((long long)Hs * Ws < 128 && !(Hs == 8 && Ws == 8)) return 0;  // > 2 samples per 128-row tile: no per-sample record
   return up ? lg_conv_halo_supported(1, dtype, B, Hs, Ws, cs, cb) : lg_conv_halo_supported(0, dtype, B, Hs, Ws, cb, cs);
 }
@@ -85,7 +85,7 @@ static int run_down(const float* big, const void* pack, const float* bias, float
 // "up": small [B,Hs,Ws,cs] -> big [B,2Hs,2Ws,cb]
 static int run_up(const float* small, const void* pack, const float* bias, float* big, int B, int Hs, int Ws, int cb,
                   int cs, int dtype, void* stream) {
-  if (cb == 3 && !bias && n3_enabled()) {  // image-side data gradient: VALU kernel, exact f32 in both dtypes
+  if (cb == 3 && !bias && lg_n3_enabled()) {  // image-side data gradient: VALU kernel, exact f32 in both dtypes
     const int rc = lg_n3_up_try(small, raw_pack(pack, cb, cs, dtype), big, B, Hs, Ws, cs, stream);
     if (rc != LG_ERR_UNSUPPORTED) return rc;
   }
@@ -107,7 +107,7 @@ extern "C" int lg_conv2d_s2_fwd_stats(const float* x, const void* x16, const voi
   if (nparts) *nparts = 0;
   LG_CHECK_ARG(!y16 || dtype == LG_DT_BF16, "lg_conv2d_s2_fwd_stats: a bf16 result needs dtype bf16");
   if (cb == 3) {
-    if (dtype == LG_DT_BF16 && n3_enabled()) {  // bf16 path: patch kernel with coalesced row stores + fused moments
+    if (dtype == LG_DT_BF16 && lg_n3_enabled()) {  // bf16 path: patch kernel with coalesced row stores + fused moments
       const int rc = lg_n3_conv1_fwd_p16_try(x, raw_pack(pack, cb, cs, dtype), bias, y16 ? nullptr : y, y16, B, Hs, Ws, cs,
                                              spart, spart_bytes, nparts, stream);
       if (rc != LG_ERR_UNSUPPORTED) return rc;
@@ -127,7 +127,7 @@ extern "C" int lg_conv_down3_zn_supported(int B, int Hm, int Wm, int Cs, int N);
 extern "C" int lg_conv_down3_zn_try(const void* z16, const float* zstats, float alpha, const void* wpack, const float* bias, void* out16,
                                     int B, int Hm, int Wm, int Cs, int N, void* spart, size_t spart_bytes, int* nparts_out, void* stream);
 extern "C" int lg_conv2d_s2_fwd_stats_zn_supported(int B, int Hs, int Ws, int cb, int cs, int dtype) {
-  return (dtype == LG_DT_BF16 && cb != 3 && !lg_env_flag("LG_NO_HALO") && lg_conv_down3_zn_supported(B, Hs, Ws, cb, cs)) ? 1 : 0;
+  return (dtype == LG_DT_BF16 && cb != 3 && lg_halo_enabled() && lg_conv_down3_zn_supported(B, Hs, Ws, cb, cs)) ? 1 : 0;
 }
 extern "C" int lg_conv2d_s2_fwd_stats_zn(const void* z16, const float* zstats, float alpha, const void* pack, const float* bias,
                                          void* y16, int B, int Hs, int Ws, int cb, int cs, int dtype, void* spart,
@@ -151,7 +151,7 @@ extern "C" int lg_conv2d_s2_dgrad_m16(const float* dy, const void* dy16, const v
                                       int Hs, int Ws, int cb, int cs, int dtype, void* stream) {
   if (cb == 3) {
     LG_CHECK_ARG(dx && !dx16, "lg_conv2d_s2_dgrad_m16: the 3-channel image gradient is fp32 only");
-    if (dtype == LG_DT_BF16 && dy16 && n3_enabled()) {  // bf16 path: tap-product GEMM straight from the bf16 mirror
+    if (dtype == LG_DT_BF16 && dy16 && lg_n3_enabled()) {  // bf16 path: tap-product GEMM straight from the bf16 mirror
       const int rc = lg_n3_up_p16_try(dy16, raw_pack(pack, cb, cs, dtype), dx, B, Hs, Ws, cs, stream);
       if (rc != LG_ERR_UNSUPPORTED) return rc;
     }
@@ -192,7 +192,7 @@ extern "C" int lg_conv2d_s2_dgrad_nf(const void* dy16, const void* pack, void* d
                                      int* nparts, void* stream) {
   LG_CHECK_ARG(dy16 && pack && dx16 && nparts, "lg_conv2d_s2_dgrad_nf: null pointer");
   *nparts = 0;
-  if (cb != 3 && z16 && stats && part && n3_enabled()) {
+  if (cb != 3 && z16 && stats && part && lg_n3_enabled()) {
     LgNormFuse nf{(const __bf16*)z16, stats, (double*)part, alpha, 0};
     int rc = lg_conv_up3_nf_try(dy16, up_pack(pack, cb, cs, LG_DT_BF16), nullptr, dx16, B, Hs, Ws, cs, cb, nullptr, 0, nparts,
                                 &nf, part_bytes, stream);
@@ -271,7 +271,7 @@ extern "C" int lg_convT_s2_wgrad(const float* x, const float* dy, float* dw, voi
 
 // 1 if the 3-channel layers of this shape run from the bf16 mirror alone in the bf16 path (no fp32 operand needed)
 extern "C" int lg_n3_m16_supported(int H, int W, int cb, int cs, int dtype) {
-  return (dtype == LG_DT_BF16 && cb == 3 && n3_enabled() && lg_n3_p16_supported(H, W, cs)) ? 1 : 0;
+  return (dtype == LG_DT_BF16 && cb == 3 && lg_n3_enabled() && lg_n3_p16_supported(H, W, cs)) ? 1 : 0;
 }
 
 extern "C" int lg_convT_s1_tanh_fwd_m16(const float* x, const void* x16, const void* pack, const float* bias, float* y,
@@ -288,7 +288,7 @@ extern "C" int lg_convT_s1_tanh_fwd_m16(const float* x, const void* x16, const v
 
 // 1 if lg_convT_s1_tanh_fwd_z16 runs this shape (InstanceNorm + LeakyReLU of the input applied while it is staged)
 extern "C" int lg_convT_s1_tanh_fwd_z16_supported(int H, int W, int cb, int cs, int dtype) {
-  return (dtype == LG_DT_BF16 && cb == 3 && n3_enabled() && !lg_env_flag("LG_NO_ROWS") && lg_n3_rows_supported(H, W, cs)) ? 1 : 0;
+  return (dtype == LG_DT_BF16 && cb == 3 && lg_n3_enabled() && lg_n3_rows_supported(H, W, cs)) ? 1 : 0;
 }
 
 // y = tanh(convT_s1(h) + bias) with h = bf16(LeakyReLU_alpha(a*((z - mu) - mu_lo) + beta)) formed on the fly from the raw
@@ -303,7 +303,7 @@ extern "C" int lg_convT_s1_tanh_fwd_z16(const void* z16, const float* stats, flo
 
 extern "C" int lg_convT_s1_tanh_fwd(const float* x, const void* pack, const float* bias, float* y, int B, int H, int W,
                                     int cb, int cs, int dtype, void* stream) {
-  if (cb == 3 && n3_enabled()) {
+  if (cb == 3 && lg_n3_enabled()) {
     const int rc = lg_n3_s1t_fwd_try(x, raw_pack(pack, cb, cs, dtype), bias, y, B, H, W, cs, stream);
     if (rc != LG_ERR_UNSUPPORTED) return rc;
   }
@@ -393,7 +393,7 @@ static int s1_tanh_bwd_impl(const float* x, const void* x16, const float* dpre, 
   int rc;
   if (dx || dx16) {  // dx[i,ci] = sum_k,co dpre[i+k-2,co] W[k,co,ci]  -> patch conv, stride 1, pad 2
     rc = LG_ERR_UNSUPPORTED;
-    if (dtype == LG_DT_BF16 && n3_enabled())
+    if (dtype == LG_DT_BF16 && lg_n3_enabled())
       rc = lg_n3_s1_dgrad_p16_nf_try(dpre, raw_pack(pack, cb, cs, dtype), dx, dx16, B, H, W, cs, nf, nf_bytes, nparts, stream);
     if (rc == LG_ERR_UNSUPPORTED) rc = lg_conv_igemm_ex(MODE_PATCH, dtype, dpre, nullptr, pack, nullptr, dx, dx16, B, H, W, 3, cs, 0, 1, 2, nullptr, 0,
                           nullptr, stream);

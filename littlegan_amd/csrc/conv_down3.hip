@@ -20,7 +20,6 @@
 //     with 8-byte LDS writes and reaches HBM as whole 256-B pixel rows, 16 B per lane;
 //   * the InstanceNormalization moments of the tile ({count, mean, M2}, instance.py:114-115) come out of the same
 //     registers, so no pass re-reads the output.
-#include <stdlib.h>
 #include <type_traits>
 #include "lg_common.h"
 
@@ -54,18 +53,11 @@ struct D3L {
 #define LG_D3_DBG 0   // compile-time ablation bits (timing only, results wrong): 1 no MFMA, 2 no fragment loads, 4 no halo staging, 8 no epilogue
 #endif
 constexpr int DBG = LG_D3_DBG;
-#ifndef LG_D3_RING
-#define LG_D3_RING 10   // weight-fragment look-ahead in taps (5: one instantiation of the slice body; 10: two, ring offsets 0 / 5)
-#endif
-#ifndef LG_D3_SCHED
-#define LG_D3_SCHED 1   // 0: tap body in three pinned groups (A reads | MFMAs | ring refill); 1: interleaved by sched_group_barrier
-#endif
-#ifndef LG_D3_HALO_AUX
-#define LG_D3_HALO_AUX 0   // cache policy bits of the halo loads (2 = nt: streamed-once activations; A/B builds)
-#endif
-#ifndef LG_D3_ADEPTH
-#define LG_D3_ADEPTH 2  // A-fragment buffers: 2 = requested one tap ahead, 3 = two taps ahead
-#endif
+// Tuned constants (measurements: DESIGN 10 / 11; the switches that swept them live in the commits that measured them)
+constexpr int RING = 10;        // weight-fragment look-ahead in taps: two copies of the slice body, ring offsets 0 / 5 (5 = one copy: slower)
+constexpr int ADEPTH = 2;       // A-fragment buffers: requested one tap ahead (3 = two taps ahead: no gain)
+constexpr int STAGGER = 6;      // start delay of the odd-slot block in ~1024-cycle units (about one epilogue)
+constexpr int BLOCKS_PER_CU = 2;   // persistent blocks per CU: one wave of each per SIMD
 
 struct D3Params {
   const __bf16* src;   // [B][Hs][Ws][Cs] bf16
@@ -81,12 +73,6 @@ struct D3Params {
   const __bf16* gsrc;  // NORM = 2 (BWDNORM): src is the raw output z of THIS level, gsrc the gradient g w.r.t. its normalised + activated
   const float* bcoef;  //   map, bcoef the per-sample records of lg_instnorm_bwd_coef: the operand dz is formed while the halo is staged
   unsigned long long* clk;  // clock census (runtime.hip: lg_set_clock_census) or null
-  int lists;           // item lists (LG_D3_LISTS): 0 rounds with a balanced partial round (default), 1 the round-2 lists, 2 one contiguous range per XCD
-  int slice_major;     // experiment (round 5, LG_D3_SLICE_MAJOR): the source is [B][Cs/16][Hs][Ws][16] (channel-slice-major) instead of NHWC
-  int lds_order;       // 1: halo pieces dealt to the threads in LDS order (the round-2 map; LG_D3_LDS_ORDER, A/B), 0: in memory order
-  int stagger;         // start delay of the odd-slot block in ~1024-cycle units
-  unsigned long long* stamps;  // diagnostic build only (LG_D3_STAMPS): [block][64] s_memtime stamps of wave 0
-  int stamp_lite;              // only the block's first / last stamp (the per-phase stamps cost ~11 % and change the clock)
 };
 
 __device__ __forceinline__ int pix32(int r) {  // MFMA row -> tile pixel inside its 32-pixel group (see conv_halo.hip)
@@ -118,15 +104,15 @@ constexpr int toff_bytes(int t) {  // tap t = ky*5+kx: LDS byte offset of its so
 // norm-backward apply pass and its dz tensor disappear (6 B per element of HBM traffic less; the piece loads double).  For tapes that
 // ask the level for no weight gradient: the Adjuster's decoder chain at 2B (eager_trainer.py:158-163), partition steps of the
 // Generator.  Bit-identical to bwd_apply16 + conv (tests/test_launch_shapes_gpu.py).
-// Measured in the C3 step (round 4, same box, A/B by LG_NO_BWDNORM): the N = 64 level (convT4's data gradient at 2B = 512: apply pass
+// Measured in the C3 step (round 4, same box, A/B by the model-level switch of commit cfe9bb0): the N = 64 level (convT4's data gradient at 2B = 512: apply pass
 // 303 us + conv 321 us -> 552 us) gains 72 us per launch; the N = 128 level (convT3: 150 + 222 -> 395 us) LOSES 23 — 17 VALU
 // operations per element, 1.3 x the elements (halo), land on a kernel that was matrix-bound, not HBM-bound — and is not instantiated.
 // Two facts from the way: (1) the staging arithmetic must be pinned behind the tap loop (see commit below); (2) the per-item
 // coefficient record is read through the constant address space (lg_as_const, lg_common.h: as a plain load hipcc made it a VECTOR
 // load inside the item loop, `s_waitcnt vmcnt(0)` at every item boundary) AND every field is made wave-uniform explicitly
-// (lg_uniform), so that the staging arithmetic takes scalar operands.  The vector-load build (-DLG_D3_COEF_PLAIN at commit 43a08f2) was
+// (lg_uniform), so that the staging arithmetic takes scalar operands.  The vector-load build (commit 43a08f2) was
 // NOT deterministic with two blocks per CU: hipcc kept the record as per-lane copies paired in 64-bit registers and formed g' - m1 as
-// a packed fp32 subtraction selecting the pair's HIGH register; read back through one-hot weights (tests/diagnostics/bwdnorm_probe.py)
+// a packed fp32 subtraction selecting the pair's HIGH register; read back through one-hot weights (tests/diagnostics/bwdnorm_probe.py at commit cfe9bb0)
 // every wrong operand element — 82 of 82 — was the LOW result of that instruction, bit-equal to the value with m1 not subtracted.
 // No wait, barrier or scheduling hole is involved (full waits in front of every instruction leave it in place); round-5 analysis in
 // DESIGN 11a.  tests/test_launch_shapes_gpu.py::test_persistent_kernels_are_deterministic launches this form at B = 512.
@@ -155,19 +141,15 @@ __global__ __launch_bounds__(256, 2) void conv_down3_kernel(const D3Params p) {
   // count as the stride.  The round-2 lists (items lb, lb + G, ... with lb the XCD-major block rank) gave the remainder of
   // nitems / G to the LOWEST ranks = the first XCDs: at 768 items on 512 blocks (the 8 x 8 level at 2B) every block of XCDs 0-3 ran
   // two items and every block of XCDs 4-7 one — half the chip idle for the second half of the launch.
-  // Two balanced forms (p.lists, LG_D3_LISTS): 2 = the contiguous range per XCD just described; 0 (default) = ROUNDS — the whole chip sweeps the map
-  // front to back in rounds of G items as in round 2 (the producer of the map has just written it and its front is what the caches still hold), and only
-  // the LAST, partial round is dealt out as one contiguous sub-range per XCD.  1 = the round-2 lists (A/B).
+  // Adopted: ROUNDS — the whole chip sweeps the map front to back in rounds of G items as in round 2 (the producer of the map has just written
+  // it and its front is what the caches still hold), and only the LAST, partial round is dealt out as one contiguous sub-range per XCD
+  // (one contiguous range per XCD for the whole launch: measured, not adopted).
   const int nx = G < 8 ? G : 8, xcd = (int)blockIdx.x % nx, xidx = (int)blockIdx.x / nx;
-  const bool ranges = p.lists == 2;
-  const int nbx = ranges ? (G - xcd + nx - 1) / nx : G;                      // stride of a block's list
-  const int icnt = (p.nitems - xcd + nx - 1) / nx;                           // ranges: items of this XCD (>= nbx: grid <= nitems)
-  const int istart = xcd * (p.nitems / nx) + (xcd < p.nitems % nx ? xcd : p.nitems % nx);
-  const int lb = ranges ? istart + xidx : lg_xcd_remap(blockIdx.x, G);       // first item; then lb + nbx, lb + 2 nbx, ...
+  const int lb = lg_xcd_remap(blockIdx.x, G);                                // first item; then lb + G, lb + 2 G, ...
   const int nfull = p.nitems / G, nrem = p.nitems - nfull * G;               // rounds: full rounds, items of the partial one
   const int rcnt = (nrem - xcd + nx - 1) / nx;                               // ... of which this XCD takes rcnt, from rstart on
   const int rstart = nfull * G + xcd * (nrem / nx) + (xcd < nrem % nx ? xcd : nrem % nx);
-  const int nmine = ranges ? (icnt - xidx + nbx - 1) / nbx : p.lists == 1 ? (p.nitems - lb + G - 1) / G : nfull + (xidx < rcnt ? 1 : 0);
+  const int nmine = nfull + (xidx < rcnt ? 1 : 0);
   const int total = nmine * nchunk;
   const unsigned long long clk_t0 = __builtin_amdgcn_s_memtime(), clk_r0 = __builtin_amdgcn_s_memrealtime();   // clock census (see the end)
   // ---- the (up to) 6 halo pieces this thread stages in every slice: LDS offset and position inside the halo ----------
@@ -175,34 +157,28 @@ __global__ __launch_bounds__(256, 2) void conv_down3_kernel(const D3Params p) {
 #pragma unroll
   for (int u = 0; u < PPT; ++u) {
     const int q = tid + u * 256;
-    pl[u] = -1; pyx[u] = 0;
-    if (q < NPIECE) {
-      const int row = q >> 1, hy = row / HWP, hxp = row - hy * HWP;
-      pl[u] = row * ROWB + (q & 1) * 16;
-      if constexpr (PAIR) {  // slots 0..19: sample 0 (even 0..9, odd 10..19), 20..23 unused, 24..42: sample 1 (even, odd)
+    if constexpr (PAIR) {  // LDS-order pieces; slots 0..19: sample 0 (even 0..9, odd 10..19), 20..23 unused, 24..42: sample 1 (even, odd)
+      pl[u] = -1; pyx[u] = 0;
+      if (q < NPIECE) {
+        const int row = q >> 1, hy = row / HWP, hxp = row - hy * HWP;
+        pl[u] = row * ROWB + (q & 1) * 16;
         const int sm = hxp >= 24, j2 = hxp - 24 * sm, odd = j2 >= HWH, hx = 2 * (j2 - odd * HWH) + odd;
         pyx[u] = (hxp < 20 || hxp >= 24) && hx < 2 * 8 + 3 ? (hy << 8) | (sm << 7) | hx : (0x7fff << 8);
-      } else {
-        const int hx = hxp < HWH ? 2 * hxp : 2 * (hxp - HWH) + 1;
-        pyx[u] = hx < 2 * TW + 3 ? (hy << 8) | hx : (0x7fff << 8);  // the 36th slot of a row is padding: never valid
       }
-    }
-    if constexpr (!PAIR) {
-      // GLOBAL-ORDER pieces (round 4; p.lds_order = 1 restores the LDS-order map above for A/B): consecutive lanes take consecutive
+    } else {
+      // GLOBAL-ORDER pieces (round 4; the PAIR form above keeps the LDS-order map of round 2, which lost here): consecutive lanes take consecutive
       // 16-B pieces of the source in MEMORY order — (pixel x, half 0), (x, half 1), (x + 1, half 0), ... along a halo row — and write
       // them to their de-interleaved LDS slots.  In LDS order a wave's 64 pieces are 32 pixels two columns apart: for the 32-channel
       // source of the N = 64 level (64 B per pixel) every load instruction touched 32 cache lines and used a quarter of each; in
       // memory order it touches 16 and uses half (the other half is the next slice).  The padding slot of a row is never read
       // (largest slot a tap reaches: 34) and no longer written.
-      if (!p.lds_order) {
-        constexpr int PPROW = 2 * (2 * TW + 3);   // 70 real pieces per halo row
-        pl[u] = -1; pyx[u] = (0x7fff << 8);
-        if (q < HH * PPROW) {
-          const int hy = q / PPROW, rem = q - hy * PPROW, hx = rem >> 1;
-          const int hxp = (hx & 1) ? HWH + (hx >> 1) : (hx >> 1);
-          pl[u] = (hy * HWP + hxp) * ROWB + (rem & 1) * 16;
-          pyx[u] = (hy << 8) | hx;
-        }
+      constexpr int PPROW = 2 * (2 * TW + 3);   // 70 real pieces per halo row
+      pl[u] = -1; pyx[u] = (0x7fff << 8);
+      if (q < HH * PPROW) {
+        const int hy = q / PPROW, rem = q - hy * PPROW, hx = rem >> 1;
+        const int hxp = (hx & 1) ? HWH + (hx >> 1) : (hx >> 1);
+        pl[u] = (hy * HWP + hxp) * ROWB + (rem & 1) * 16;
+        pyx[u] = (hy << 8) | hx;
       }
     }
   }
@@ -219,7 +195,7 @@ __global__ __launch_bounds__(256, 2) void conv_down3_kernel(const D3Params p) {
 
   struct Item { int n, y0, x0, tn; };
   auto decode = [&](int k) {
-    const int item = (p.lists == 0 && k == nfull) ? rstart + xidx : lb + k * nbx;
+    const int item = k == nfull ? rstart + xidx : lb + k * G;
     Item it;
     it.tn = item % p.ntn;
     const int tm = item / p.ntn;
@@ -247,42 +223,32 @@ __global__ __launch_bounds__(256, 2) void conv_down3_kernel(const D3Params p) {
       nmu0 = lg_uniform(sp[0]); nna0 = lg_uniform(sp[2]); nnb0 = lg_uniform(sp[3]); nml0 = lg_uniform(sp[4]);   // SGPRs whatever the load (lg_common.h)
     }
     if constexpr (NORM == 2) {
-#ifdef LG_D3_COEF_PLAIN   // diagnostic build: the round-4 form whose BWDNORM instantiation was not deterministic
-      const float* sp = p.bcoef + (long long)it.n * 8;
-#else
       const lg_const_f32p sp = lg_as_const(p.bcoef + (long long)it.n * 8);    // uniform + constant space: one 32-byte scalar load
-#endif
-#ifdef LG_D3_COEF_PLAIN
-      bco.mu = sp[0]; bco.mul = sp[1]; bco.a = sp[2]; bco.b = sp[3]; bco.m1 = sp[4]; bco.m2 = sp[5]; bco.m1l = sp[6]; bco.m2l = sp[7];
-#else   // explicitly wave-uniform: the staging arithmetic takes SCALAR operands whatever load the compiler emits (lg_common.h)
+      // explicitly wave-uniform: the staging arithmetic takes SCALAR operands whatever load the compiler emits (lg_common.h)
       bco.mu = lg_uniform(sp[0]); bco.mul = lg_uniform(sp[1]); bco.a = lg_uniform(sp[2]); bco.b = lg_uniform(sp[3]);
       bco.m1 = lg_uniform(sp[4]); bco.m2 = lg_uniform(sp[5]); bco.m1l = lg_uniform(sp[6]); bco.m2l = lg_uniform(sp[7]);
-#endif
     }
 #pragma unroll
     for (int u = 0; u < PPT; ++u) {
       const int sy = 2 * it.y0 - 1 + (pyx[u] >> 8), sx = 2 * it.x0 - 1 + (pyx[u] & (PAIR ? 127 : 255));
       const int sl = PAIR ? (pyx[u] >> 7) & 1 : 0;   // PAIR: second sample of the tile
       const bool ok = pl[u] >= 0 && (unsigned)sy < (unsigned)p.Hs && (unsigned)sx < (unsigned)p.Ws;
-      // slice-major source: a pixel of a slice is 32 contiguous bytes, a slice a plane of Hs x Ws x 32 B (the channel offset c0 of issue() is
-      // rescaled there); NHWC: the pixel's Cs x 2 bytes, 32 of them used per slice
-      hoff[u] = ok ? (p.slice_major ? (unsigned)(sl * p.Hs * p.Ws * p.Cs * 2 + ((sy * p.Ws + sx) * KC + half8) * 2)
-                                    : (unsigned)((((sl * p.Hs + sy) * p.Ws + sx) * p.Cs + half8) * 2)) : OOB;   // (+ 2 c0 < 2^31 keeps OOB out of range)
+      // NHWC: the pixel's Cs x 2 bytes, 32 of them used per slice (a channel-slice-major source: measured, not adopted — DESIGN 11c)
+      hoff[u] = ok ? (unsigned)((((sl * p.Hs + sy) * p.Ws + sx) * p.Cs + half8) * 2) : OOB;   // (+ 2 c0 < 2^31 keeps OOB out of range)
     }
   };
-  const unsigned cmul = p.slice_major ? (unsigned)(p.Hs * p.Ws * 2) : 2u;   // bytes per channel step of the slice offset: c0 * cmul
   auto issue = [&](const Item& it, int c0, u32x4 (&v)[PPT]) __attribute__((always_inline)) {
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<__bf16*>(p.src + (long long)it.n * sample_elems), 0, (PAIR ? 2 : 1) * sample_elems * 2, 0x00027000);
 #pragma unroll
-    for (int u = 0; u < PPT; ++u) v[u] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, hoff[u] + (unsigned)c0 * cmul, 0, LG_D3_HALO_AUX));
+    for (int u = 0; u < PPT; ++u) v[u] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, hoff[u] + (unsigned)c0 * 2u, 0, 0));
   };
   auto issue_g = [&](const Item& it, int c0, u32x4 (&v)[NORM == 2 ? PPT : 1]) __attribute__((always_inline)) {   // BWDNORM: the same pieces of g
     if constexpr (NORM == 2) {
       const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
           const_cast<__bf16*>(p.gsrc + (long long)it.n * sample_elems), 0, sample_elems * 2, 0x00027000);
 #pragma unroll
-      for (int u = 0; u < PPT; ++u) v[u] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, hoff[u] + (unsigned)c0 * cmul, 0, LG_D3_HALO_AUX));
+      for (int u = 0; u < PPT; ++u) v[u] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, hoff[u] + (unsigned)c0 * 2u, 0, 0));
     }
   };
   u32x4 gv[NORM == 2 ? PPT : 1];
@@ -336,8 +302,8 @@ __global__ __launch_bounds__(256, 2) void conv_down3_kernel(const D3Params p) {
   // Weight-fragment ring: RING fragments (= taps) ahead of the MFMAs.  25 taps per slice and RING = 10 -> the ring
   // position of tap 0 alternates between 0 and 5 from one slice to the next: the slice body exists in two copies
   // (OFF = 0 / 5) so that every ring access is a compile-time register.
-  constexpr int RING = LG_D3_RING;
-  constexpr int AD = LG_D3_ADEPTH;
+  static_assert(NTAP % RING != 0, "the slice body is instantiated for the two ring offsets 0 and NTAP % RING");
+  constexpr int AD = ADEPTH;
   u32x4 bf[RING];
   u32x4 hv[PPT];
 
@@ -351,20 +317,6 @@ __global__ __launch_bounds__(256, 2) void conv_down3_kernel(const D3Params p) {
   commit(smem, hv);
   __syncthreads();
 
-#ifdef LG_D3_STAMPS
-  int nst = 0;
-#define D3_STAMP() do { if (p.stamps && !p.stamp_lite && wid == 0 && nst < 60) { unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (lane == 0) p.stamps[(long long)blockIdx.x * 64 + nst] = t_; ++nst; } } while (0)
-  // residency census (diagnostic build only): where and when this block started — slot 61 = HW_ID | XCC_ID << 32, 62 / 63 = the
-  // chip-wide 100 MHz clock (s_memrealtime) at the block's start / end, comparable ACROSS blocks (s_memtime is per XCD)
-  if (p.stamps && wid == 0 && lane == 0) {
-    const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-    p.stamps[(long long)blockIdx.x * 64 + 61] = (unsigned long long)hw | ((unsigned long long)xcc << 32);
-    p.stamps[(long long)blockIdx.x * 64 + 62] = __builtin_amdgcn_s_memrealtime();
-    p.stamps[(long long)blockIdx.x * 64 + 59] = __builtin_amdgcn_s_memtime();
-  }
-#else
-#define D3_STAMP() do {} while (0)
-#endif
   // bias of this wave's 32 channels in accumulator order (reloaded only when the column tile changes) and the shift of
   // the one-pass moments
   float* sbias = reinterpret_cast<float*>(smem + SBIAS_OFF);
@@ -377,11 +329,10 @@ __global__ __launch_bounds__(256, 2) void conv_down3_kernel(const D3Params p) {
      // the odd wave slot starts about one epilogue late, so that one block's epilogue / barrier falls into the other's
      // tap phase (MI355X_MICROARCH, two waves per SIMD, item 9).  Speed only; bounded.
     // (the dispatcher deals one block to every CU before any CU gets its second: the late half = the upper half of the grid)
-    if (p.stagger && (int)blockIdx.x >= (G + 1) / 2)
-      for (int i = 0; i < p.stagger; ++i) __builtin_amdgcn_s_sleep(16);  // ~1024 cycles each
+    if ((int)blockIdx.x >= (G + 1) / 2)
+      for (int i = 0; i < STAGGER; ++i) __builtin_amdgcn_s_sleep(16);  // ~1024 cycles each
   }
   int k = 0, c = 0;  // item index in this block's list, slice index
-  D3_STAMP();
   // (Round 3, measured and removed: the two blocks of a CU finish 16 us apart — at equal priority the older wave wins the matrix-pipe
   //  arbitration.  Dealing the items out dynamically, alternating s_setprio per item, and a per-CU progress board that gives the
   //  block that is behind priority 1 all CLOSE the gap (to 5 / 8 / 3 us) and none shortens the kernel: with forced turns both blocks
@@ -416,38 +367,31 @@ __global__ __launch_bounds__(256, 2) void conv_down3_kernel(const D3Params p) {
         for (int i = 0; i < NI; ++i)
           a[(t + AD - 1) % AD][i] = *reinterpret_cast<const bf16x8*>(hbuf + abase[i] + toff_bytes<PAIR>(t + AD - 1 < NTAP ? t + AD - 1 : 0));
       }
-      if constexpr (LG_D3_SCHED == 0) __builtin_amdgcn_sched_barrier(0);
       const int slot = (t + OFF) % RING;
 #pragma unroll
       for (int i = 0; i < NI; ++i)  // transposed product: rows = this wave's 32 output channels, columns = 32 pixels
         if constexpr (!(DBG & 1)) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bf[slot]), a[t % AD][i], acc[i], 0, 0, 0);
-      if constexpr (LG_D3_SCHED == 0) __builtin_amdgcn_sched_barrier(0);
       // the slot is free: request the fragment RING taps ahead (this slice, or the next one)
       if constexpr (!(DBG & 2)) {
         if (t + RING < NTAP) bf[slot] = wfrag(wcur, t + RING);
         else bf[slot] = wfrag(wnxt, t + RING - NTAP);
       }
-      if constexpr (LG_D3_SCHED == 0) {
-        __builtin_amdgcn_sched_barrier(0);
-      } else {
-        // one MFMA, then one LDS read in its shadow (an MFMA holds the vector issue port for 8 of its 32 cycles), ..., the
-        // ring refill behind the last MFMA: the wave never leaves the MFMA pipe idle to issue its loads
+      // one MFMA, then one LDS read in its shadow (an MFMA holds the vector issue port for 8 of its 32 cycles), ..., the
+      // ring refill behind the last MFMA: the wave never leaves the MFMA pipe idle to issue its loads (three pinned groups
+      // A reads | MFMAs | ring refill: measured slower)
 #pragma unroll
-        for (int i = 0; i < NI; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
-        }
-        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);     // VMEM read
+      for (int i = 0; i < NI; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
       }
+      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);     // VMEM read
     }
-    D3_STAMP();   // taps done
     // NORM forms: the staging arithmetic stays BEHIND the tap loop.  Left free, hipcc hoists its first unpacking shifts into the first
     // taps of the slice, and with them an `s_waitcnt vmcnt(2)` for the halo pieces requested a few instructions earlier: every slice
     // then opens by sitting out the HBM latency of its own prefetch (seen in the .s of the BWDNORM form, round 4).
     if constexpr (NORM != 0) __builtin_amdgcn_sched_barrier(0);
     commit(smem + ((s + 1) & 1) * HB, hv);
     __syncthreads();  // slice s consumed by every wave, slice s+1 complete
-    D3_STAMP();   // barrier passed
 
     if (last_c && !(DBG & 8)) {
       // ---- epilogue of item `cur`: acc[i][e] = channel (e&3) + 8*(e>>2) + 4*h of pixel i*32 + pix32(r) ---------------
@@ -578,18 +522,13 @@ __global__ __launch_bounds__(256, 2) void conv_down3_kernel(const D3Params p) {
         for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
       if (more && nxt.tn != cur.tn) load_bias(nxt.tn);
       ++k;
-      D3_STAMP();  // epilogue done
     }
     cur = nxt;
     c = c2;
   };
-  if constexpr (NTAP % RING == 0) {
-    for (int s = 0; s < total; ++s) slice(std::integral_constant<int, 0>{}, s);  // ONE instantiation of the slice body
-  } else {
-    for (int s = 0; s < total; s += 2) {
-      slice(std::integral_constant<int, 0>{}, s);
-      if (s + 1 < total) slice(std::integral_constant<int, NTAP % RING>{}, s + 1);
-    }
+  for (int s = 0; s < total; s += 2) {
+    slice(std::integral_constant<int, 0>{}, s);
+    if (s + 1 < total) slice(std::integral_constant<int, NTAP % RING>{}, s + 1);
   }
   if (p.clk && wid == 0 && lane == 0) {   // one lane per block: three no-return adds at the end of a ~100-us block life
     const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
@@ -597,74 +536,42 @@ __global__ __launch_bounds__(256, 2) void conv_down3_kernel(const D3Params p) {
       atomicAdd(p.clk, t1 - clk_t0); atomicAdd(p.clk + 1, r1 - clk_r0); atomicAdd(p.clk + 2, 1ull);
     }
   }
-#ifdef LG_D3_STAMPS
-  if (p.stamps && wid == 0 && lane == 0) {
-    p.stamps[(long long)blockIdx.x * 64 + 60] = __builtin_amdgcn_s_memtime();
-    p.stamps[(long long)blockIdx.x * 64 + 63] = __builtin_amdgcn_s_memrealtime();
-  }
-#endif
 }
 
 }  // namespace
 
-// LG_OK: launched.  LG_ERR_UNSUPPORTED: the caller falls back to the halo-tile kernel of conv_halo.hip.
-extern "C" int lg_conv_down3_nf_try(const void* src16, const void* wpack, const float* bias, void* out16, int B, int Hm, int Wm,
-                                    int Cs, int N, void* spart, size_t spart_bytes, int* nparts_out, const LgNormFuse* nf,
-                                    size_t nf_bytes, void* stream);
-extern "C" int lg_conv_down3_try(const void* src16, const void* wpack, const float* bias, void* out16, int B, int Hm, int Wm,
-                                 int Cs, int N, void* spart, size_t spart_bytes, int* nparts_out, void* stream) {
-  return lg_conv_down3_nf_try(src16, wpack, bias, out16, B, Hm, Wm, Cs, N, spart, spart_bytes, nparts_out, nullptr, 0, stream);
+// The one shape predicate of this file: which tiling the kernel takes for a shape, D3_NONE = not covered (the dispatch chain goes on
+// to the halo-tile kernel of conv_halo.hip).  Kill switch and descriptor bound included; the queries and the launcher all ask here.
+enum D3Tiling { D3_NONE = 0, D3_PLAIN, D3_PAIR, D3_N64 };
+static D3Tiling down3_tiling(int B, int Hm, int Wm, int Cs, int N) {
+  static int off = -1;
+  if (off < 0) off = lg_env_flag("LG_NO_DOWN3") ? 1 : 0;   // kill switch (cached: per-launch path, the table lookup takes a mutex)
+  if (off || B <= 0 || Cs % KC) return D3_NONE;
+  if ((long long)4 * Hm * Wm * Cs * 2 * 2 >= (1ll << 31)) return D3_NONE;  // buffer descriptor: two samples below the OOB offset
+  const bool pair = Hm == 8 && Wm == 8 && B % 2 == 0;  // 8 x 8 maps: a tile = two samples side by side
+  if (!pair && (Hm % TH || Wm % TW)) return D3_NONE;
+  if (N % 128 == 0) return pair ? D3_PAIR : D3_PLAIN;
+  return (N % 64 == 0 && !pair) ? D3_N64 : D3_NONE;  // 64-column tiles (2 x 2 waves)
 }
+extern "C" int lg_conv_down3_supported(int B, int Hm, int Wm, int Cs, int N) { return down3_tiling(B, Hm, Wm, Cs, N) != D3_NONE ? 1 : 0; }
+// NORM form: the forward passes on 8 x 16 tiles of 128 columns
+extern "C" int lg_conv_down3_zn_supported(int B, int Hm, int Wm, int Cs, int N) {
+  return (!lg_env_flag("LG_NO_D3_NORM") && down3_tiling(B, Hm, Wm, Cs, N) == D3_PLAIN) ? 1 : 0;
+}
+// BWDNORM form.  N = 64 only: at N = 128 the form was built and measured slower than apply pass + conv (kernel header); with more than
+// one column tile every tile would redo the dz arithmetic of the halo it shares
+extern "C" int lg_conv_down3_bn_supported(int B, int Hm, int Wm, int Cs, int N) {
+  return (!lg_env_flag("LG_NO_D3_BWDNORM") && N == 64 && down3_tiling(B, Hm, Wm, Cs, N) == D3_N64) ? 1 : 0;
+}
+
 // nf (optional; data-gradient use): also the norm-backward sums of the produced gradient ([B][*nparts_out][2] doubles)
 static int down3_launch(const void* src16, const void* wpack, const float* bias, void* out16, int B, int Hm, int Wm, int Cs, int N,
                         void* spart, size_t spart_bytes, int* nparts_out, const LgNormFuse* nf, size_t nf_bytes,
-                        const float* nstats, float nalpha, void* stream, const void* g16 = nullptr, const float* bcoef = nullptr);
-extern "C" int lg_conv_down3_supported(int B, int Hm, int Wm, int Cs, int N);
-extern "C" int lg_conv_down3_nf_try(const void* src16, const void* wpack, const float* bias, void* out16, int B, int Hm, int Wm,
-                                    int Cs, int N, void* spart, size_t spart_bytes, int* nparts_out, const LgNormFuse* nf,
-                                    size_t nf_bytes, void* stream) {
-  return down3_launch(src16, wpack, bias, out16, B, Hm, Wm, Cs, N, spart, spart_bytes, nparts_out, nf, nf_bytes, nullptr, 0.f, stream);
-}
-// The forward pass fed with the RAW bf16 output z16 of the layer below and its statistics records (NORM form of the kernel):
-// moments of the produced map are always fused (spart must hold them) — LG_ERR_UNSUPPORTED otherwise and outside the kernel's tiling.
-extern "C" int lg_conv_down3_zn_try(const void* z16, const float* zstats, float alpha, const void* wpack, const float* bias, void* out16,
-                                    int B, int Hm, int Wm, int Cs, int N, void* spart, size_t spart_bytes, int* nparts_out, void* stream) {
+                        const float* nstats, float nalpha, void* stream, const void* g16 = nullptr, const float* bcoef = nullptr) {
   if (nparts_out) *nparts_out = 0;
-  if (!zstats || !spart || !nparts_out || N % 128 != 0 || lg_env_flag("LG_NO_D3_NORM")) return LG_ERR_UNSUPPORTED;
-  return down3_launch(z16, wpack, bias, out16, B, Hm, Wm, Cs, N, spart, spart_bytes, nparts_out, nullptr, 0, zstats, alpha, stream);
-}
-extern "C" int lg_conv_down3_zn_supported(int B, int Hm, int Wm, int Cs, int N) {
-  return (!lg_env_flag("LG_NO_D3_NORM") && N % 128 == 0 && Hm % TH == 0 && Wm % TW == 0 && lg_conv_down3_supported(B, Hm, Wm, Cs, N)) ? 1 : 0;
-}
-// BWDNORM form (NORM = 2): the data gradient of a transposed conv fed with (z16, g16, coef) of its level instead of dz16 — the
-// sums of the NEXT level's norm backward are always fused (nf), 8 x 16 tiles only; LG_ERR_UNSUPPORTED otherwise.
-extern "C" int lg_conv_down3_bn_supported(int B, int Hm, int Wm, int Cs, int N) {
-  const bool pair = Hm == 8 && Wm == 8 && B % 2 == 0;
-  // N = 64 only: at N = 128 the form was built and measured slower than apply pass + conv (kernel header); with more than one column
-  // tile every tile would redo the dz arithmetic of the halo it shares
-  return (!lg_env_flag("LG_NO_D3_BWDNORM") && !pair && Hm % TH == 0 && Wm % TW == 0 && N == 64 &&
-          lg_conv_down3_supported(B, Hm, Wm, Cs, N)) ? 1 : 0;
-}
-extern "C" int lg_conv_down3_bn_try(const void* z16, const void* g16, const float* bcoef, float alpha, const void* wpack, void* out16,
-                                    int B, int Hm, int Wm, int Cs, int N, int* nparts_out, const LgNormFuse* nf, size_t nf_bytes,
-                                    void* stream) {
-  if (nparts_out) *nparts_out = 0;
-  if (!g16 || !bcoef || !nf || !nparts_out || !lg_conv_down3_bn_supported(B, Hm, Wm, Cs, N)) return LG_ERR_UNSUPPORTED;
-  return down3_launch(z16, wpack, nullptr, out16, B, Hm, Wm, Cs, N, nullptr, 0, nparts_out, nf, nf_bytes, nullptr, alpha, stream, g16, bcoef);
-}
-static int down3_launch(const void* src16, const void* wpack, const float* bias, void* out16, int B, int Hm, int Wm, int Cs, int N,
-                        void* spart, size_t spart_bytes, int* nparts_out, const LgNormFuse* nf, size_t nf_bytes,
-                        const float* nstats, float nalpha, void* stream, const void* g16, const float* bcoef) {
-  if (nparts_out) *nparts_out = 0;
-  static int off = -1;
-  if (off < 0) off = lg_env_flag("LG_NO_DOWN3") ? 1 : 0;  // A/B switch
-  if (off || !src16 || !wpack || !out16) return LG_ERR_UNSUPPORTED;
-  const bool pair = Hm == 8 && Wm == 8 && B % 2 == 0;  // 8 x 8 maps: a tile = two samples side by side
-  static int no64 = -1;
-  if (no64 < 0) no64 = lg_env_flag("LG_NO_DOWN3_N64") ? 1 : 0;
-  const bool n64 = N % 128 != 0 && N % 64 == 0 && !pair && !no64;  // 64-column tiles (2 x 2 waves)
-  if (((Hm % TH || Wm % TW) && !pair) || Cs % KC || (N % 128 && !n64) || B <= 0) return LG_ERR_UNSUPPORTED;
-  if ((long long)4 * Hm * Wm * Cs * 2 * 2 >= (1ll << 31)) return LG_ERR_UNSUPPORTED;  // buffer descriptor: two samples below the OOB offset
+  const D3Tiling tiling = down3_tiling(B, Hm, Wm, Cs, N);
+  if (tiling == D3_NONE || !src16 || !wpack || !out16) return LG_ERR_UNSUPPORTED;
+  const bool pair = tiling == D3_PAIR, n64 = tiling == D3_N64;
   D3Params p{};
   p.src = (const __bf16*)src16; p.wp = (const char*)wpack; p.bias = bias; p.out = (__bf16*)out16;
   p.B = B; p.Hm = Hm; p.Wm = Wm; p.Hs = 2 * Hm; p.Ws = 2 * Wm; p.Cs = Cs; p.N = N; p.N32 = N / 32; p.KB = Cs / 16;
@@ -672,7 +579,6 @@ static int down3_launch(const void* src16, const void* wpack, const float* bias,
   const long long nitems = (long long)(pair ? B / 2 : B) * p.tpi * p.ntn;
   if (nitems <= 0 || nitems >= (1ll << 30)) return LG_ERR_UNSUPPORTED;
   p.nitems = (int)nitems; p.nparts = p.tpi * p.ntn;
-  { static int stg = -1; if (stg < 0) { const char* e = getenv("LG_D3_STAGGER"); stg = e ? atoi(e) : 6; } p.stagger = stg; }
   const bool fuse = nf && nf->z && nf->stats && nf->part && nparts_out && (size_t)B * p.nparts * 2 * sizeof(double) <= nf_bytes;
   const bool stats = !fuse && spart && nparts_out && (size_t)B * p.nparts * 3 * sizeof(double) <= spart_bytes;
   // moments asked for (the caller may then write z as bf16 ONLY) but the workspace cannot hold this tiling's records: decline, so
@@ -685,13 +591,9 @@ static int down3_launch(const void* src16, const void* wpack, const float* bias,
   p.nstats = nstats; p.nalpha = nalpha;
   p.gsrc = (const __bf16*)g16; p.bcoef = bcoef;
   p.clk = lg_clock_census();
-  { static int lo = -1; if (lo < 0) lo = lg_env_flag("LG_D3_LDS_ORDER") ? 1 : 0; p.lds_order = lo; }   // (cached per call site)
-  { static int ol = -1; if (ol < 0) { const char* e = getenv("LG_D3_LISTS"); ol = (e && *e >= '0' && *e <= '2') ? *e - '0' : 0; } p.lists = ol; }
-  { static int sm = -1; if (sm < 0) sm = lg_env_flag("LG_D3_SLICE_MAJOR") ? 1 : 0; p.slice_major = (sm && !pair && !nstats && !g16) ? 1 : 0; }   // layout experiment
-  static int bpc = 0;   // resident blocks per CU
-  if (!bpc) {
-    bpc = 2;
-    if (const char* e = getenv("LG_D3_BLOCKS_PER_CU")) bpc = atoi(e) > 0 ? atoi(e) : 2;  // probe: 1 = a lone wave per SIMD
+  static bool attr_set = false;
+  if (!attr_set) {
+    attr_set = true;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_down3_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, D3L<false>::LDS_BYTES);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_down3_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, D3L<false>::LDS_BYTES);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>((conv_down3_kernel<false, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, D3L<false>::LDS_BYTES);
@@ -704,7 +606,7 @@ static int down3_launch(const void* src16, const void* wpack, const float* bias,
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>((conv_down3_kernel<true, false, false, 128, 1>)), hipFuncAttributeMaxDynamicSharedMemorySize, D3L<false>::LDS_BYTES);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>((conv_down3_kernel<false, true, false, 64, 2>)), hipFuncAttributeMaxDynamicSharedMemorySize, D3L<false>::LDS_BYTES);
   }
-  const int nblk = bpc * lg_grid_cus();   // every block resident from the start, also beside communication kernels (runtime.hip)
+  const int nblk = BLOCKS_PER_CU * lg_grid_cus();   // every block resident from the start, also beside communication kernels (runtime.hip)
   const int grid = p.nitems < nblk ? p.nitems : nblk;
   hipStream_t st = (hipStream_t)stream;
   constexpr int LDS0 = D3L<false>::LDS_BYTES, LDS1 = D3L<true>::LDS_BYTES;
@@ -729,8 +631,30 @@ static int down3_launch(const void* src16, const void* wpack, const float* bias,
   return LG_OK;
 }
 
-extern "C" int lg_conv_down3_supported(int B, int Hm, int Wm, int Cs, int N) {
-  const bool pair = Hm == 8 && Wm == 8 && B % 2 == 0;
-  const bool n64 = N % 128 != 0 && N % 64 == 0 && !pair && !lg_env_flag("LG_NO_DOWN3_N64");
-  return (!lg_env_flag("LG_NO_DOWN3") && B > 0 && ((Hm % TH == 0 && Wm % TW == 0) || pair) && Cs % KC == 0 && (N % 128 == 0 || n64)) ? 1 : 0;
+// LG_OK: launched.  LG_ERR_UNSUPPORTED: the caller falls back to the halo-tile kernel of conv_halo.hip.
+extern "C" int lg_conv_down3_nf_try(const void* src16, const void* wpack, const float* bias, void* out16, int B, int Hm, int Wm,
+                                    int Cs, int N, void* spart, size_t spart_bytes, int* nparts_out, const LgNormFuse* nf,
+                                    size_t nf_bytes, void* stream) {
+  return down3_launch(src16, wpack, bias, out16, B, Hm, Wm, Cs, N, spart, spart_bytes, nparts_out, nf, nf_bytes, nullptr, 0.f, stream);
+}
+extern "C" int lg_conv_down3_try(const void* src16, const void* wpack, const float* bias, void* out16, int B, int Hm, int Wm,
+                                 int Cs, int N, void* spart, size_t spart_bytes, int* nparts_out, void* stream) {
+  return lg_conv_down3_nf_try(src16, wpack, bias, out16, B, Hm, Wm, Cs, N, spart, spart_bytes, nparts_out, nullptr, 0, stream);
+}
+// The forward pass fed with the RAW bf16 output z16 of the layer below and its statistics records (NORM form of the kernel):
+// moments of the produced map are always fused (spart must hold them) — LG_ERR_UNSUPPORTED otherwise and outside the kernel's tiling.
+extern "C" int lg_conv_down3_zn_try(const void* z16, const float* zstats, float alpha, const void* wpack, const float* bias, void* out16,
+                                    int B, int Hm, int Wm, int Cs, int N, void* spart, size_t spart_bytes, int* nparts_out, void* stream) {
+  if (nparts_out) *nparts_out = 0;
+  if (!zstats || !spart || !nparts_out || !lg_conv_down3_zn_supported(B, Hm, Wm, Cs, N)) return LG_ERR_UNSUPPORTED;
+  return down3_launch(z16, wpack, bias, out16, B, Hm, Wm, Cs, N, spart, spart_bytes, nparts_out, nullptr, 0, zstats, alpha, stream);
+}
+// BWDNORM form (NORM = 2): the data gradient of a transposed conv fed with (z16, g16, coef) of its level instead of dz16 — the
+// sums of the NEXT level's norm backward are always fused (nf), 8 x 16 tiles only; LG_ERR_UNSUPPORTED otherwise.
+extern "C" int lg_conv_down3_bn_try(const void* z16, const void* g16, const float* bcoef, float alpha, const void* wpack, void* out16,
+                                    int B, int Hm, int Wm, int Cs, int N, int* nparts_out, const LgNormFuse* nf, size_t nf_bytes,
+                                    void* stream) {
+  if (nparts_out) *nparts_out = 0;
+  if (!g16 || !bcoef || !nf || !nparts_out || !lg_conv_down3_bn_supported(B, Hm, Wm, Cs, N)) return LG_ERR_UNSUPPORTED;
+  return down3_launch(z16, wpack, nullptr, out16, B, Hm, Wm, Cs, N, nullptr, 0, nparts_out, nf, nf_bytes, nullptr, alpha, stream, g16, bcoef);
 }

@@ -11,7 +11,6 @@
 // operand of an MFMA with one coalesced global_load_dwordx4 per lane, two taps ahead, and the tap loop has NO
 // barrier — the only block-wide synchronisation is the halo restage once per channel chunk.
 // Falls back (LG_ERR_UNSUPPORTED) to the per-tap gather kernel for shapes the tiling does not cover.
-#include <stdlib.h>
 #include "lg_common.h"
 
 extern "C" int lg_device_cus(void);
@@ -47,12 +46,9 @@ struct HaloParams {
   int TH, TW, NI, tpi_x, tpi;  // tile geometry: tiles per image along x, tiles per image
   int HH, HW, HROWS, nrows;    // halo geometry (per image) and total halo rows
   int HWH, HWP;                // W3 / DOWN: half and full pitch (pixels) of a de-interleaved halo pixel row
-  int dbg;                     // ablation switches for scripts/bench_layer.py (LG_DBG env; 0 in production)
   double* spart;               // fused InstanceNorm moments: [B][nparts][3] = {count, mean, M2} per block, or null
   int nparts;
   int dry;                     // 1: only answer whether this kernel covers the shape (no launch)
-  int res_budget;              // LDS bytes the resident-halo (RES) variant may use; 0 = variant off
-  int cfg;                     // tile-shape switches (LG_CFG env, A/B)
   int* nparts_host;            // host-side: receives nparts of the launched tiling (moments epilogue on)
   int epi_rows;                // rows per pass of the LDS-transposed epilogue (0 = straight from the accumulators)
   int ksplit;                  // 1, or 2: blockIdx.z takes one half of the channel chunks and ADDS its tile into the zeroed output (see launch)
@@ -100,13 +96,10 @@ __device__ __forceinline__ void tap_info(int mode, int cls, int t, int& dy, int&
 // RES ("resident"): UP mode from the bf16 mirror with the halo of ALL Cs channels staged once; the block then runs the
 // four parity classes one after the other out of that image (grid.y == 1): a quarter of the source traffic and no
 // barrier at all inside the (class, chunk, tap) loops.
-template <typename T, int MODE, int KCH, bool DBUF, bool SRC16, bool RES, int WAVES_M, int WAVES_N, int MT, int NT, bool W3 = false>
-#ifndef LG_EXP_W3OCC
-#define LG_EXP_W3OCC 3
-#endif
-__global__ __launch_bounds__(256, (W3 ? LG_EXP_W3OCC : 2)) void conv_halo_kernel(const HaloParams p) {
+template <typename T, int MODE, int KCH, bool SRC16, bool RES, int WAVES_M, int WAVES_N, int MT, int NT, bool W3 = false>
+__global__ __launch_bounds__(256, (W3 ? 3 : 2)) void conv_halo_kernel(const HaloParams p) {
   static_assert(!W3 || halo_w3_ok<T, MODE, KCH, SRC16, RES, WAVES_M, MT, NT>(), "W3: DOWN, 32-channel chunks, bf16 mirror, 128x32 / 64x32 wave tiles");
-  static_assert(!SRC16 || (sizeof(T) == 2 && !DBUF), "bf16 source only with bf16 MFMA, single-buffered halo");
+  static_assert(!SRC16 || sizeof(T) == 2, "bf16 source only with bf16 MFMA");
   static_assert(!RES || (MODE == MODE_UP && (SRC16 || sizeof(T) == 4)), "resident halo: UP mode, from the bf16 mirror or (round 5) exact f32");
   constexpr int ESZ = DT<T>::ESZ;
   constexpr int BM = WAVES_M * MT * 32, BN = WAVES_N * NT * 32;
@@ -123,8 +116,7 @@ __global__ __launch_bounds__(256, (W3 ? LG_EXP_W3OCC : 2)) void conv_halo_kernel
   constexpr int NCLS = RES ? 4 : 1;
   int* s_out = reinterpret_cast<int*>(smem);          // [NCLS][128] output pixel per M row (RES: per class)
   int* s_hoff = s_out + NCLS * BM;                    // [nrows] source pixel index or -1
-  char* sH = smem + ((NCLS * BM + p.nrows) * 4 + 15) / 16 * 16;   // [DBUF ? 2 : 1][nrows][ROWB]
-  const int HBYTES = p.nrows * ROWB;
+  char* sH = smem + ((NCLS * BM + p.nrows) * 4 + 15) / 16 * 16;   // [nrows][ROWB]
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wid = tid >> 6;
@@ -203,7 +195,6 @@ __global__ __launch_bounds__(256, (W3 ? LG_EXP_W3OCC : 2)) void conv_halo_kernel
   int ntaps;
   if (MODE == MODE_UP) ntaps = (py ? 3 : 2) * (px ? 3 : 2);
   else ntaps = 25;
-  if (p.dbg & 8) ntaps = 1;  // ablation: one tap per chunk -> fixed per-block cost (timing only)
   // ksplit == 2 (exact-f32 DOWN on the 8 x 8 maps): this block contracts chunks [c_lo, c_lo + nchunk) only
   const int nchunk_all = p.Cs / KC;
   const int c_lo = p.ksplit > 1 ? (int)blockIdx.z * nchunk_all / p.ksplit : 0;
@@ -215,11 +206,7 @@ __global__ __launch_bounds__(256, (W3 ? LG_EXP_W3OCC : 2)) void conv_halo_kernel
   constexpr int NB = NT * KCH;  // B fragments (1 KiB each, 16 B per lane) of one tap for this wave's NT column tiles
   // NSETS register sets of B fragments = the prefetch distance in taps; ~96 VGPRs of fragments in flight whatever the
   // tap's size, so that the distance covers the L2 latency also for the short taps of KCH == 2 (8 MFMAs per tap)
-#ifdef LG_EXP_NSETS
-  constexpr int NSETS = (W3 && MODE == MODE_DOWN) ? LG_EXP_NSETS : ((W3 && MODE == MODE_UP) ? 2 : ((MT * NT == 4 && NB == 4) ? 6 : 3));
-#else
   constexpr int NSETS = (W3 && MODE == MODE_UP) ? 2 : ((MT * NT == 4 && NB == 4) ? 6 : 3);  // deeper only where registers allow
-#endif
   u32x4 fb[NSETS][NB];
 
   int nit = nchunk * ntaps;  // flat (chunk, tap) iteration space
@@ -325,67 +312,16 @@ __global__ __launch_bounds__(256, (W3 ? LG_EXP_W3OCC : 2)) void conv_halo_kernel
       }
     }
   };
-  // Interleaved halo prefetch (DBUF): while the taps of chunk c run out of halo buffer `hcur`, the halo of chunk c+1
-  // is fetched in `upt` row-units per tap (registers for one tap, then into the other buffer) -> no exposed staging.
-  constexpr int UMAX = 4;
-  const int NU = (p.nrows + RPP - 1) / RPP;                                   // row units (one float4 per thread each)
-  const int upt = ntaps > 1 ? (NU + ntaps - 2) / (ntaps - 1) : NU;            // issued during taps 0 .. ntaps-2
-  f32x4 hreg[UMAX];
-  auto halo_issue = [&](int c0, int u0) {
-#pragma unroll
-    for (int u = 0; u < UMAX; ++u) {
-      if (u < upt) {
-        const int hr = (u0 + u) * RPP + arow;
-        hreg[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (hr < p.nrows) {
-          const int o = s_hoff[hr];
-          if (o >= 0) hreg[u] = *reinterpret_cast<const f32x4*>(p.src + (long long)o * p.Cs + c0 + alc * 4);
-        }
-      }
-    }
-  };
-  auto halo_commit = [&](char* dst, int u0) {
-#pragma unroll
-    for (int u = 0; u < UMAX; ++u) {
-      if (u < upt) {
-        const int hr = (u0 + u) * RPP + arow;
-        if (hr < p.nrows) {
-          if constexpr (ESZ == 4) {
-            *reinterpret_cast<f32x4*>(dst + hr * ROWB + alc * 16) = hreg[u];
-          } else {
-            bf16x4 w;
-            w[0] = (__bf16)hreg[u][0]; w[1] = (__bf16)hreg[u][1]; w[2] = (__bf16)hreg[u][2]; w[3] = (__bf16)hreg[u][3];
-            *reinterpret_cast<bf16x4*>(dst + hr * ROWB + alc * 8) = w;
-          }
-        }
-      }
-    }
-  };
-
   // one tap: MFMAs out of `cur`, then refill `cur` with the fragments of tap it+NSETS (its MFMAs have been issued, in
   // order, so the registers are free).  Chunk boundary: every wave must be done with the old halo (barrier).
-  int hsel = 0;
   auto iteration = [&](int it, u32x4 (&cur)[NB]) {
     const int cc = it / ntaps, t = it - cc * ntaps;
-    char* hcur = sH + hsel * HBYTES;
-    if constexpr (DBUF) {
-      if (cc + 1 < nchunk && !(p.dbg & 4)) {
-        char* hnext = sH + (hsel ^ 1) * HBYTES;
-        if (t > 0) halo_commit(hnext, (t - 1) * upt);
-        if (t + 1 < ntaps || ntaps == 1) halo_issue((c_lo + cc + 1) * KC, t * upt);
-        if (ntaps == 1) halo_commit(hnext, 0);
-      }
-    }
-    if (!(p.dbg & 1)) compute(it, cur, hcur);
-    if (it + NSETS < nit && !(p.dbg & 2)) load_frags(cur, it + NSETS);
-    if (!RES && t + 1 == ntaps && it + 1 < nit && !(p.dbg & 4)) {
+    compute(it, cur, sH);
+    if (it + NSETS < nit) load_frags(cur, it + NSETS);
+    if (!RES && t + 1 == ntaps && it + 1 < nit) {
       __syncthreads();
-      if constexpr (DBUF) {
-        hsel ^= 1;
-      } else {
-        stage_halo((c_lo + cc + 1) * KC, sH);
-        __syncthreads();
-      }
+      stage_halo((c_lo + cc + 1) * KC, sH);
+      __syncthreads();
     }
   };
 
@@ -400,7 +336,6 @@ __global__ __launch_bounds__(256, (W3 ? LG_EXP_W3OCC : 2)) void conv_halo_kernel
     if constexpr (RES) {
       cls = 3 - pass; py = cls >> 1; px = cls & 1;
       ntaps = (py ? 3 : 2) * (px ? 3 : 2);
-      if (p.dbg & 8) ntaps = 1;
       nit = nchunk * ntaps;
     }
     const int* so = s_out + (RES ? cls * BM : 0);
@@ -427,7 +362,7 @@ __global__ __launch_bounds__(256, (W3 ? LG_EXP_W3OCC : 2)) void conv_halo_kernel
     // TEPI: the block's waves own column slices of the same pixel rows, so straight from the accumulators a pixel row
     // (N x 4 B) would leave as WAVES_N separate 128-B pieces at different times.  The finished tile goes through the
     // (now dead) halo region of LDS instead, epi_rows rows at a time, and leaves as whole rows, 16 B per lane.
-    constexpr bool TEPI = WAVES_N > 1 && !DBUF;  // RES: the halo stays live across the classes -> its own C region behind it
+    constexpr bool TEPI = WAVES_N > 1;  // RES: the halo stays live across the classes -> its own C region behind it
     bool tepi_done = false;
     if constexpr (TEPI) {
       if (p.epi_rows > 0 && p.ksplit <= 1) {
@@ -458,7 +393,7 @@ __global__ __launch_bounds__(256, (W3 ? LG_EXP_W3OCC : 2)) void conv_halo_kernel
           for (int idx = tid; idx < RP * (BN / 4); idx += 256) {
             const int row = idx / (BN / 4), c4 = idx - row * (BN / 4);
             const int o = so[pass * RP + row], col = n0 + c4 * 4;
-            if (o >= 0 && col < p.N && !(p.dbg & 16)) {
+            if (o >= 0 && col < p.N) {
               const f32x4 v = *reinterpret_cast<const f32x4*>(C + row * CP + c4 * 4);
               if (p.out16) {
                 bf16x4 w;
@@ -472,7 +407,7 @@ __global__ __launch_bounds__(256, (W3 ? LG_EXP_W3OCC : 2)) void conv_halo_kernel
         }
       }
     }
-    if constexpr (sizeof(T) == 4 && !RES && !DBUF) {
+    if constexpr (sizeof(T) == 4 && !RES) {
       // ksplit: the two halves of the contraction meet in the output, which the launcher zeroed: 0 + a + b and 0 + b + a are the same
       // float (IEEE addition commutes; with THREE summands it would not), so the result does not depend on which block comes first.
       // Bias rides with half 0; no activation, no fused moments (launch() declines both).
@@ -489,7 +424,7 @@ __global__ __launch_bounds__(256, (W3 ? LG_EXP_W3OCC : 2)) void conv_halo_kernel
             for (int e = 0; e < 16; ++e) {
               const int row = (wm * MT + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
               const int o = so[row];
-              if (cok && o >= 0 && !(p.dbg & 16)) unsafeAtomicAdd(p.out + (long long)o * p.N + col, acc[i][j][e] + bv);
+              if (cok && o >= 0) unsafeAtomicAdd(p.out + (long long)o * p.N + col, acc[i][j][e] + bv);
             }
           }
         }
@@ -507,7 +442,7 @@ __global__ __launch_bounds__(256, (W3 ? LG_EXP_W3OCC : 2)) void conv_halo_kernel
         for (int e = 0; e < 16; ++e) {
           const int row = (wm * MT + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
           const int o = so[row];
-          if (cok && o >= 0 && !(p.dbg & 16)) {
+          if (cok && o >= 0) {
             float v = acc[i][j][e] + bv;
             if (p.act == 1) v = tanhf(v);
             if (p.out16) p.out16[(long long)o * p.N + col] = (__bf16)v;
@@ -520,7 +455,7 @@ __global__ __launch_bounds__(256, (W3 ? LG_EXP_W3OCC : 2)) void conv_halo_kernel
     // ---- fused InstanceNormalization moments of this block's output tile (one sample per block: NI == 1) ----------
     // {count, mean, M2 about the block mean}, merged per sample with Chan's formula by stats_final_kernel (norm.hip):
     // the separate pass that re-read the whole conv output for its moments is gone.
-    if (p.spart && !(p.dbg & 32) && p.NI == 2) {
+    if (p.spart && p.NI == 2) {
       // two samples per block (8 x 8 maps): 32-row fragment f = wm*MT + i belongs to sample f >> 1; one record per sample
       float s2[2] = {0.f, 0.f};
 #pragma unroll
@@ -573,7 +508,7 @@ __global__ __launch_bounds__(256, (W3 ? LG_EXP_W3OCC : 2)) void conv_halo_kernel
       }
       if constexpr (RES) __syncthreads();
     } else
-    if (p.spart && !(p.dbg & 32)) {
+    if (p.spart) {
       float s = 0.f;
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
@@ -623,8 +558,9 @@ __global__ __launch_bounds__(256, (W3 ? LG_EXP_W3OCC : 2)) void conv_halo_kernel
 }
 
 constexpr int LDS_BUDGET = 80 * 1024;  // two blocks per CU (160 KiB)
+constexpr int RES_BUDGET = 52 * 1024;  // LDS the resident-halo (RES) UP variant may use: three blocks per CU
 
-template <typename T, int MODE, int KCH, bool DBUF, bool SRC16, bool RES, int WAVES_M, int WAVES_N, int MT, int NT, bool W3 = false>
+template <typename T, int MODE, int KCH, bool SRC16, bool RES, int WAVES_M, int WAVES_N, int MT, int NT, bool W3 = false>
 int launch(HaloParams p, hipStream_t st) {
   constexpr int BN = WAVES_N * NT * 32;
   if (W3 && MODE == MODE_DOWN) {  // de-interleaved halo pixel rows (even columns, then odd columns)
@@ -632,20 +568,15 @@ int launch(HaloParams p, hipStream_t st) {
     p.HROWS = p.HH * p.HWP; p.nrows = p.NI * p.HROWS;
   }
   const int ROWB = RES ? p.Cs * DT<T>::ESZ + 16 : ((W3 && MODE == MODE_DOWN) ? KCH * 32 : KCH * 32 + 16);
-  size_t lds = (((RES ? 4 : 1) * 128 + p.nrows) * 4 + 15) / 16 * 16 + (size_t)p.nrows * ROWB * (DBUF ? 2 : 1);
-  if (lds > (size_t)(RES ? p.res_budget : LDS_BUDGET)) return LG_ERR_UNSUPPORTED;
-  const bool res_epi = RES && WAVES_N > 1 && p.N % 4 == 0 && (p.cfg & 128);  // transposed epilogue for RES too: 32 rows x (BN + 4) floats of extra LDS
+  size_t lds = (((RES ? 4 : 1) * 128 + p.nrows) * 4 + 15) / 16 * 16 + (size_t)p.nrows * ROWB;
+  if (lds > (size_t)(RES ? RES_BUDGET : LDS_BUDGET)) return LG_ERR_UNSUPPORTED;
+  const bool res_epi = RES && WAVES_N > 1 && p.N % 4 == 0;  // transposed epilogue for RES too: 32 rows x (BN + 4) floats of extra LDS
   if (res_epi) lds = (lds + 15) / 16 * 16 + (size_t)32 * (BN + 4) * 4;
-  if (DBUF) {  // the interleaved prefetch must fit its register window: ceil(NU/(ntaps-1)) <= 4 with the fewest taps
-    constexpr int KC = KCH * 32 / DT<T>::ESZ, RPP = 256 / (SRC16 ? KC / 8 : KC / 4);
-    const int NU = (p.nrows + RPP - 1) / RPP, min_taps = MODE == MODE_UP ? 4 : 25;
-    if ((NU + min_taps - 2) / (min_taps - 1) > 4) return LG_ERR_UNSUPPORTED;
-  }
   p.ntn = p.Npad / BN;
   {  // LDS-transposed epilogue: needs N % 4 == 0 and epi_rows x (BN + 4) floats inside the halo region
     const size_t halo_bytes = (size_t)p.nrows * ROWB;
     p.epi_rows = 0;
-    if (WAVES_N > 1 && !DBUF && !RES && p.N % 4 == 0 && !(p.cfg & 64)) {
+    if (WAVES_N > 1 && !RES && p.N % 4 == 0) {
       if (halo_bytes >= (size_t)64 * (BN + 4) * 4) p.epi_rows = 64;
       else if (halo_bytes >= (size_t)32 * (BN + 4) * 4) p.epi_rows = 32;
     }
@@ -656,18 +587,9 @@ int launch(HaloParams p, hipStream_t st) {
   const int ntm = p.NI == 1 ? p.B * p.tpi : lg_cdiv(p.B, p.NI);
   dim3 grid(ntm * p.ntn, (MODE == MODE_UP && !RES) ? 4 : 1, p.ksplit > 1 ? p.ksplit : 1);
   p.ntm = ntm;
-  {
-    static int mf = -1;
-    if (mf < 0) { const char* e = getenv("LG_HALO_MFAST"); mf = e ? atoi(e) : 0; }   // 0 never, 1 where the weights exceed 2 MB, 2 always
-    const size_t wbytes = (size_t)(MODE == MODE_UP ? 25 : 25) * p.Cs * p.Npad * DT<T>::ESZ;
-    p.mfast = (p.mfast || mf == 2 || (mf == 1 && wbytes > (2u << 20))) && p.ntn > 1 ? 1 : 0;
-  }
-  {
-    static int co = -1;
-    if (co < 0) co = lg_env_flag("LG_NO_UP_CLSORDER") ? 0 : 1;
-    p.clsorder = co && MODE == MODE_UP && !RES && (int)grid.x * 4 <= 2 * lg_device_cus();   // one round only: over several rounds the lightest class should come last (convT3 forward at B = 64, 2048 blocks: 269 us in the order 9, 6, 6, 4 taps, 281 with the 4-tap class third)
-  }
-  auto kern = conv_halo_kernel<T, MODE, KCH, DBUF, SRC16, RES, WAVES_M, WAVES_N, MT, NT, W3>;
+  p.mfast = p.mfast && p.ntn > 1 ? 1 : 0;   // only where the caller asks for it (the split f32 DOWN tiles below)
+  p.clsorder = MODE == MODE_UP && !RES && (int)grid.x * 4 <= 2 * lg_device_cus();   // one round only: over several rounds the lightest class should come last (convT3 forward at B = 64, 2048 blocks: 269 us in the order 9, 6, 6, 4 taps, 281 with the 4-tap class third)
+  auto kern = conv_halo_kernel<T, MODE, KCH, SRC16, RES, WAVES_M, WAVES_N, MT, NT, W3>;
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, RES ? 160 * 1024 : LDS_BUDGET);
@@ -685,18 +607,16 @@ int launch(HaloParams p, hipStream_t st) {
   return LG_OK;
 }
 
-template <typename T, int MODE, int KCH, bool DBUF, bool SRC16, bool RES = false>
+template <typename T, int MODE, int KCH, bool SRC16, bool RES = false>
 int dispatch_bn2(const HaloParams& p, hipStream_t st) {
   // exact-f32 path, 8 x 8 maps (two samples per row tile): at B = 64 that is 32 row tiles x 3 column tiles of 128 = 96 blocks for 256
   // CUs (measured: conv4 forward takes the same 535 us at B = 64 and B = 128): 64-column tiles double the blocks.  An fp32 MFMA is 64
   // cycles for two operand registers, so the narrower tile costs little operand traffic per matrix cycle.  (The choice depends on the
   // map, not on the batch: a launch and its 32-image chunks must take the same tiling — the moment partials are compared bit for bit.)
   bool narrow = false;
-  if constexpr (sizeof(T) == 4 && !DBUF && !RES) {
-    static int off = -1;
-    if (off < 0) off = lg_env_flag("LG_NO_F32_NARROW") ? 1 : 0;
-    narrow = !off && p.NI > 1 && p.Npad % 64 == 0;
-    // Round 5, the 8 x 8 maps at the C2 batches (scripts/probe/f32_ablate.sh, f32_tiling_ab.sh, f32_mfast_ab.sh).  These grids are
+  if constexpr (sizeof(T) == 4 && !RES) {
+    narrow = p.NI > 1 && p.Npad % 64 == 0;
+    // Round 5, the 8 x 8 maps at the C2 batches.  These grids are
     // ONE round of at most 512 blocks, every block in the same phase at the same time, so what counts is how evenly that round covers the
     // 1024 SIMDs.  Measured per launch (us), conv4 forward (DOWN, 25 x 256 deep, N = 384) | convT1 forward (UP, 384 -> 256):
     //     B = 64 : 64-column tiles 349 (192 blocks) , split 32-column 308-327, split 64-column 285, + row-tile-fastest 269 | 64-col 220, 128-col 274
@@ -711,68 +631,51 @@ int dispatch_bn2(const HaloParams& p, hipStream_t st) {
     // the difference instead: tests/test_launch_shapes_gpu.py, test_f32_8x8_level_tilings_that_depend_on_the_batch).
     const int ntm2 = lg_cdiv(p.B, p.NI > 0 ? p.NI : 1);
     if constexpr (MODE == MODE_DOWN) {
-      static int ks = -1;
-      if (ks < 0) ks = lg_env_flag("LG_NO_F32_KSPLIT") ? 0 : 1;
       constexpr int KC = KCH * 32 / 4;
-      if (ks && narrow && p.act == 0 && !p.out16 && (p.Cs / KC) % 2 == 0 && (p.Cs / KC) >= 4 && ntm2 * (p.Npad / 64) <= 256) {
+      if (narrow && p.act == 0 && !p.out16 && (p.Cs / KC) % 2 == 0 && (p.Cs / KC) >= 4 && ntm2 * (p.Npad / 64) <= 256) {
         HaloParams q = p;
         q.ksplit = 2; q.spart = nullptr; q.mfast = 1;
-        return launch<T, MODE, KCH, DBUF, SRC16, RES, 2, 2, 2, 1>(q, st);
+        return launch<T, MODE, KCH, SRC16, RES, 2, 2, 2, 1>(q, st);
       }
     }
     if constexpr (MODE == MODE_UP) {
-      static int wide = -1;
-      if (wide < 0) wide = lg_env_flag("LG_NO_F32_UPWIDE") ? 0 : 1;
-      if (wide && narrow && p.Npad % 128 == 0 && 4 * ntm2 * (p.Npad / 128) >= 512) narrow = false;
+      if (narrow && p.Npad % 128 == 0 && 4 * ntm2 * (p.Npad / 128) >= 512) narrow = false;
     }
   }
-  if constexpr (!DBUF && !RES) if (!narrow) {  // tall wave tiles (128 rows x 64/32 cols): half the weight-fragment traffic per MFMA
-    if (p.Npad % 256 == 0 && (p.cfg & 1)) return launch<T, MODE, KCH, DBUF, SRC16, RES, 1, 4, 4, 2>(p, st);
-    if (p.Npad % 128 == 0 && (p.cfg & 2) && (!(MODE == MODE_DOWN && p.NI > 1) || (halo_w3_ok<T, MODE, KCH, SRC16, RES, 1, 4, 1>() && (p.cfg & 8)))) {
-      if constexpr (halo_w3_ok<T, MODE, KCH, SRC16, RES, 1, 4, 1>()) {
-        // three resident blocks per CU: measured better on the whole step than a rounds-of-the-grid heuristic (LG_CFG bit 2 = off)
-        if (!(p.cfg & 4) && (MODE == MODE_DOWN || (p.cfg & 32))) return launch<T, MODE, KCH, DBUF, SRC16, RES, 1, 4, 4, 1, true>(p, st);
-      }
-      return launch<T, MODE, KCH, DBUF, SRC16, RES, 1, 4, 4, 1>(p, st);
+  if constexpr (!RES) if (!narrow) {  // tall wave tiles (128 rows x 32 cols): half the weight-fragment traffic per MFMA (128 x 64: measured, not adopted)
+    constexpr bool w3 = halo_w3_ok<T, MODE, KCH, SRC16, RES, 1, 4, 1>();   // small DOWN maps take the tall tile only in its W3 form
+    if (p.Npad % 128 == 0 && (!(MODE == MODE_DOWN && p.NI > 1) || w3)) {
+      // W3, three resident blocks per CU, wherever it is compiled: measured better on the whole step than a rounds-of-the-grid heuristic
+      return launch<T, MODE, KCH, SRC16, RES, 1, 4, 4, 1, w3>(p, st);
     }
   }
-  if (p.Npad % 128 == 0 && !narrow) return launch<T, MODE, KCH, DBUF, SRC16, RES, 2, 2, 2, 2>(p, st);
+  if (p.Npad % 128 == 0 && !narrow) return launch<T, MODE, KCH, SRC16, RES, 2, 2, 2, 2>(p, st);
   if (p.Npad % 64 == 0) {   // (32-column tiles for the f32 8 x 8 level: conv4 forward 330 -> 305 us at B = 64, but the C2 step 9.08 -> 9.19 ms)
-    if constexpr (!DBUF && halo_w3_ok<T, MODE, KCH, SRC16, RES, 2, 2, 1>()) {
-      if (!(p.cfg & 16)) return launch<T, MODE, KCH, DBUF, SRC16, RES, 2, 2, 2, 1, true>(p, st);
-    }
-    return launch<T, MODE, KCH, DBUF, SRC16, RES, 2, 2, 2, 1>(p, st);
+    return launch<T, MODE, KCH, SRC16, RES, 2, 2, 2, 1, halo_w3_ok<T, MODE, KCH, SRC16, RES, 2, 2, 1>()>(p, st);
   }
-  return launch<T, MODE, KCH, DBUF, SRC16, RES, 4, 1, 1, 1>(p, st);
+  return launch<T, MODE, KCH, SRC16, RES, 4, 1, 1, 1>(p, st);
 }
 template <typename T, int MODE, int KCH>
 int dispatch_bn(const HaloParams& p, hipStream_t st) {
-  int rc = LG_ERR_UNSUPPORTED;
   if constexpr (sizeof(T) == 2) {
     if (p.src16) {  // bf16 mirror of the source available
       if constexpr (MODE == MODE_UP && KCH == 4) {  // all channels resident, the four classes in one block
-        if (p.res_budget > 0) {
-          const int rc = dispatch_bn2<T, MODE, KCH, false, true, true>(p, st);
-          if (rc != LG_ERR_UNSUPPORTED) return rc;
-        }
+        const int rc = dispatch_bn2<T, MODE, KCH, true, true>(p, st);
+        if (rc != LG_ERR_UNSUPPORTED) return rc;
       }
-      return dispatch_bn2<T, MODE, KCH, false, true>(p, st);
+      return dispatch_bn2<T, MODE, KCH, true>(p, st);
     }
   }
   if constexpr (sizeof(T) == 4 && MODE == MODE_UP && KCH == 4) {
     // Round 5: the resident form for the exact-f32 N = 32 level (convT4 forward: 64 channels x 4 B = 49 KB of halo).  K-sliced, that layer is
     // 8192 blocks of 32 x 32-pixel-by-column wave tiles, each a prologue (tables, halo, first fragments) for 64 .. 288 MFMAs per wave; resident,
-    // one block stages the tile once and runs the four classes' 800 MFMAs per wave behind it.  LG_NO_F32_RES=1 = before.
-    static int res32 = -1;
-    if (res32 < 0) res32 = lg_env_flag("LG_NO_F32_RES") ? 0 : 1;
-    if (res32 && p.res_budget > 0 && p.Npad == 32 && p.NI == 1 && p.Cs % 4 == 0 && 256 % (p.Cs / 4) == 0) {
-      rc = launch<T, MODE, KCH, false, false, true, 4, 1, 1, 1>(p, st);
+    // one block stages the tile once and runs the four classes' 800 MFMAs per wave behind it.
+    if (p.Npad == 32 && p.NI == 1 && p.Cs % 4 == 0 && 256 % (p.Cs / 4) == 0) {
+      const int rc = launch<T, MODE, KCH, false, true, 4, 1, 1, 1>(p, st);
       if (rc != LG_ERR_UNSUPPORTED) return rc;
     }
   }
-  if ((p.dbg & 64) && p.Cs / (KCH * 32 / DT<T>::ESZ) > 1) rc = dispatch_bn2<T, MODE, KCH, true, false>(p, st);  // double-buffered halo: measured slower, opt-in
-  if (rc == LG_ERR_UNSUPPORTED) rc = dispatch_bn2<T, MODE, KCH, false, false>(p, st);
-  return rc;
+  return dispatch_bn2<T, MODE, KCH, false>(p, st);   // (a double-buffered halo: measured slower, not adopted)
 }
 
 template <int MODE>
@@ -818,17 +721,6 @@ extern "C" int lg_conv_halo_try(int mode, int dtype, const float* src, const voi
   p.B = B; p.Cs = Cs; p.Hm = Hm; p.Wm = Wm; p.N = N; p.Npad = lg_npad(N); p.act = act;
   p.Hs = ss * Hm; p.Ws = ss * Wm;
   p.Ho = mode == MODE_UP ? 2 * Hm : Hm; p.Wo = mode == MODE_UP ? 2 * Wm : Wm;
-  {
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = getenv("LG_DBG"); dbg = e ? atoi(e) : 0; }
-    p.dbg = dbg;
-    static int resb = -1;  // LG_RES_KB: LDS budget (KiB) of the resident-halo UP variant; 0 switches it off (A/B)
-    if (resb < 0) { const char* e = getenv("LG_RES_KB"); resb = (e ? atoi(e) : 52) * 1024; }
-    p.res_budget = resb;
-    static int cfg = -1;
-    if (cfg < 0) { const char* e = getenv("LG_CFG"); cfg = e ? atoi(e) : 170; }  // measured: bits 1 (128x32 wave tiles), 3 (also for small maps with W3), 5 (W3 for UP), 7 (RES: transposed epilogue) on
-    p.cfg = cfg;
-  }
   int nparts = 0;  // set by launch<> to the partial records per sample of the tiling it chose
   if (spart && nparts_out && (p.NI == 1 || (p.NI == 2 && p.TH * p.TW == 64)) && act == 0) {
     const int worst = (mode == MODE_UP ? 4 : 1) * p.tpi * (p.Npad / 32);  // narrowest column tile

@@ -333,10 +333,10 @@ extern "C" int lg_conv_halo_try(int mode, int dtype, const float* src, const voi
                                 const float* bias, float* out, void* out16, int B, int Hm, int Wm, int Cs, int N, int act, void* spart,
                                 size_t spart_bytes, int* nparts_out, void* stream);
 
-static bool halo_enabled() {
+extern "C" int lg_halo_enabled(void) {
   static int v = -1;
-  if (v < 0) v = lg_env_flag("LG_NO_HALO") ? 0 : 1;  // A/B switch: LG_NO_HALO=1 forces the per-tap gather kernel
-  return v == 1;
+  if (v < 0) v = lg_env_flag("LG_NO_HALO") ? 0 : 1;  // kill switch: LG_NO_HALO=1 forces the per-tap gather kernel (cached: per-launch path)
+  return v;
 }
 
 extern "C" int lg_npad(int n) {
@@ -387,12 +387,12 @@ extern "C" int lg_conv_igemm_ex(int mode, int dtype, const float* src, const voi
   p.pstride = pstride; p.ppad = ppad;
   hipStream_t st = (hipStream_t)stream;
   int rc;
-  if (mode == MODE_DOWN && dtype == LG_DT_BF16 && src16 && out16 && act == 0 && halo_enabled()) {
+  if (mode == MODE_DOWN && dtype == LG_DT_BF16 && src16 && out16 && act == 0 && lg_halo_enabled()) {
     // software-pipelined persistent kernel (conv_down3.hip) for the bf16 activation path where its tiling applies
     rc = lg_conv_down3_try(src16, wpack, bias, out16, B, Hm, Wm, Cs, N, spart, spart_bytes, nparts_out, stream);
     if (rc != LG_ERR_UNSUPPORTED) return rc;
   }
-  if (mode == MODE_UP && dtype == LG_DT_BF16 && src16 && out16 && act == 0 && halo_enabled()) {
+  if (mode == MODE_UP && dtype == LG_DT_BF16 && src16 && out16 && act == 0 && lg_halo_enabled()) {
     // resident-halo persistent kernel with the four parity classes on concurrent waves (conv_up3.hip): small-N layers
     rc = lg_conv_up3_try(src16, wpack, bias, out16, B, Hm, Wm, Cs, N, spart, spart_bytes, nparts_out, stream);
     if (rc != LG_ERR_UNSUPPORTED) return rc;
@@ -400,7 +400,7 @@ extern "C" int lg_conv_igemm_ex(int mode, int dtype, const float* src, const voi
     rc = lg_conv_up4_try(src16, wpack, bias, out16, B, Hm, Wm, Cs, N, spart, spart_bytes, nparts_out, stream);
     if (rc != LG_ERR_UNSUPPORTED) return rc;
   }
-  if (mode != MODE_PATCH && halo_enabled()) {  // LDS halo-tile kernel where the tiling covers the shape
+  if (mode != MODE_PATCH && lg_halo_enabled()) {  // LDS halo-tile kernel where the tiling covers the shape
     rc = lg_conv_halo_try(mode, dtype, src, src16, wpack, bias, out, out16, B, Hm, Wm, Cs, N, act, spart, spart_bytes,
                           nparts_out, stream);
     if (rc != LG_ERR_UNSUPPORTED) return rc;

@@ -21,21 +21,16 @@
 //   * the InstanceNormalization moments of the tile come out of the same registers (one pass about a shift);
 //   * (round 3, forward forms) the staged tile's rows do not get a phase of their own: they leave INSIDE the next tile's MFMA
 //     stream, one ds_read_b128 + one buffer store per second fragment (see DEFERRED ROW SWEEP below).  Measured A/B on one box
-//     (LG_U3_NO_DEFER=1 variant): convT3 forward 113.4 -> 111.3 us, conv2 data gradient 124 -> 120.5 us, convT4 forward within noise
+//     (against the round-2 order, rows in a phase of their own): convT3 forward 113.4 -> 111.3 us, conv2 data gradient 124 -> 120.5 us, convT4 forward within noise
 //     (172-178 both ways): the row phase was the small part of the non-MFMA share (staging + the two barriers stay).
 //   * (round 4, measured and removed) convT4 forward WITHOUT the staging area: double-buffered halo, one barrier per step, every wave
 //     storing its accumulators as 8-byte buffer stores (two lanes = 16 contiguous bytes of a pixel's 64-byte row): correct, and 192 us
 //     against 137 — sixteen scattered 16-byte-segment stores per wave and step are what the staging area exists to avoid.  Also
 //     without effect on that layer: the halo requested / committed by the three waves that leave their class loop early (153.5 vs
 //     153.6 us), a start delay of the second workgroup of a CU (141.6 / 143.2 / 143.0 / 145.1 us for 0 / 5 / 9 / 13 k cycles).
-#include <stdlib.h>
 #include <type_traits>
 #include <utility>
 #include "lg_common.h"
-
-#ifndef LG_U3_NO_DEFER
-#define LG_U3_NO_DEFER 0
-#endif
 
 namespace {
 
@@ -46,9 +41,6 @@ __device__ __forceinline__ void lg_static_for(Fn&& fn) { lg_static_for_(std::mak
 
 constexpr int TH = 8, TW = 16, HHT = TH + 2, HWT = TW + 2, NPX = HHT * HWT;  // 10 x 18 = 180 halo pixels
 constexpr int RING = 8;
-#ifndef LG_U3_SCHED
-#define LG_U3_SCHED 1   // 0: fragment step in three pinned groups; 1: interleaved by sched_group_barrier (MFMA, LDS read, ...)
-#endif
 
 // NTT = tiles per workgroup step.  Waves = NTT * WN * 4 classes: 8 (one workgroup per CU) or, for N = 32 with ONE tile per step,
 // 4 (TWO independent workgroups per CU, 58 KB of LDS each: one's staging / row-store / barrier phases fall into the other's
@@ -83,8 +75,6 @@ struct U3Params {
   double* spart;       // [B][tpi][3] or null
   int B, Hs, Ws, tpi_x, tpi, nitems;
   LgNormFuse nf;       // FUSE instantiation: norm-backward sums of the produced gradient (lg_common.h)
-  unsigned long long* stamps;  // diagnostic build (LG_U3_STAMPS): [block][8 waves][32]
-  int rotoff;          // 4-wave form: class-rotation offset of the SECOND workgroup of a CU (see ROT below)
 };
 
 __device__ __forceinline__ int pix32(int r) {
@@ -118,14 +108,13 @@ __global__ __launch_bounds__((Cfg<CS, N, NTT>::THREADS), 2) void conv_up3_kernel
   const int cls_fixed = C::WN == 2 ? (slot == 0 ? 3 : slot == 1 ? 1 : slot == 2 ? 0 : 2)
                                    : (tsel == 0 ? (slot == 0 ? 3 : slot == 1 ? 1 : slot == 2 ? 2 : 0) : (slot == 0 ? 0 : slot == 1 ? 2 : slot == 2 ? 1 : 3));
   const int G = gridDim.x;
-  // ROT: class of step s = rot_class(wid + s + rsh).  The two workgroups of a CU put one wave each on every SIMD and run the same
+  // ROT: class of step s = rot_class(wid + s).  The two workgroups of a CU put one wave each on every SIMD and run the same
   // program from the same start: in phase, a SIMD holds two 9-tap waves while another holds two 4-tap ones (18 : 8 taps).  The
-  // second workgroup of a CU (the upper half of the grid) can start its rotation rsh places on (LG_U3_ROTOFF; 2: its wave w runs the class
+  // second workgroup of a CU (the upper half of the grid) could start its rotation some places on (2: its wave w runs the class
   // that COMPLEMENTS the first workgroup's — (3, 0), (1, 2), (0, 3), (2, 1): 13 / 12 taps per SIMD and step).  Measured in round 5
-  // (scripts/probe/u3_rotoff_ab.sh, convT4 forward at B = 256): 145.3 / 143.1 us in phase, 141.4 (offset 1), 142.7 / 143.8 (offset 2) —
-  // the matrix pipe's balance is not what bounds this layer; default 0.
-  const int rsh = (C::ROT && (int)blockIdx.x >= (G + 1) / 2) ? p.rotoff : 0;
-  int cls = C::ROT ? rot_class(wid + rsh) : cls_fixed;
+  // (convT4 forward at B = 256): 145.3 / 143.1 us in phase, 141.4 (offset 1), 142.7 / 143.8 (offset 2) —
+  // the matrix pipe's balance is not what bounds this layer: no offset.
+  int cls = C::ROT ? rot_class(wid) : cls_fixed;
   const int lb = lg_xcd_remap(blockIdx.x, G);
   const int nsteps_all = (p.nitems + C::NT - 1) / C::NT;       // steps (NT tiles each) over the whole problem
   const int nmine = (nsteps_all - lb + G - 1) / G;
@@ -238,7 +227,7 @@ __global__ __launch_bounds__((Cfg<CS, N, NTT>::THREADS), 2) void conv_up3_kernel
   // | BARRIER (halo and staging area free) | stage | halo commit | BARRIER | moments of this tile.  The stores go through a buffer
   // descriptor over the whole output: a tile that does not exist (step 0's "previous" tile, the odd tail) gets an out-of-range
   // offset and its stores are dropped — no branch in the loop.
-  constexpr bool DEFER = !FUSE && !LG_U3_NO_DEFER;   // (LG_U3_NO_DEFER=1: the round-2 order, rows in a phase of their own — A/B builds)
+  constexpr bool DEFER = !FUSE;
   constexpr int PPO_ = C::CROW / 16, TOT_ = C::NT * C::OPX * PPO_, NPC = TOT_ / NTH;   // pieces per thread and step (8)
   // Piece q8 of thread tid is output pixel o = tid / PPO + q8 * (NTH / PPO) of tile (q8 * (NTH / PPO)) / OPX, 16-byte column tid % PPO:
   // ONE LDS address and ONE global offset per thread (the swizzle term does not depend on q8), everything else is an immediate or
@@ -292,17 +281,13 @@ __global__ __launch_bounds__((Cfg<CS, N, NTT>::THREADS), 2) void conv_up3_kernel
 #pragma unroll
         for (int i = 0; i < 4; ++i) a[(f + 1) & 1][i] = *reinterpret_cast<const bf16x8*>(smem + abase[i] + a_off(f + 1 < F ? f + 1 : 0));
       }
-      if constexpr (LG_U3_SCHED == 0) __builtin_amdgcn_sched_barrier(0);
       const int sl = (f + OFF) % RING;
 #pragma unroll
       for (int i = 0; i < 4; ++i)
         acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bf[sl]), a[f & 1][i], acc[i], 0, 0, 0);
-      if constexpr (LG_U3_SCHED == 0) __builtin_amdgcn_sched_barrier(0);
       // the stream wraps: the same class every step — or (ROT) runs on into the first fragments of the wave's NEXT class
-#ifndef LG_U3_NO_WLOAD   // ablation (round 5, scripts/probe/u3_nowload.sh): the ring is primed once and never refilled — results wrong, timing only
       if constexpr (f + RING < F) bf[sl] = *reinterpret_cast<const u32x4*>(frag_ptr(cls_c, f + RING));
       else bf[sl] = *reinterpret_cast<const u32x4*>(frag_ptr(next_c, f + RING - F));
-#endif
       // deferred row sweep of the previous tile: piece q is read from the staging area at fragment 1 + q STEP and stored one STEP later
       constexpr int STEP = F >= 2 * NPC + 2 ? 2 : 1;
       static_assert(!DEFER || F >= NPC * STEP + 2, "class loop too short for the deferred row sweep");
@@ -315,30 +300,20 @@ __global__ __launch_bounds__((Cfg<CS, N, NTT>::THREADS), 2) void conv_up3_kernel
       if constexpr (ST) piece_store((f - 1 - STEP) / STEP, rv);   // one register: piece q leaves, piece q + 1 is read behind it
       if constexpr (RD) rv = piece_lds((f - 1) / STEP);
       if constexpr (ST || RD) __builtin_amdgcn_sched_barrier(0);
-      if constexpr (LG_U3_SCHED == 0) {
-        __builtin_amdgcn_sched_barrier(0);
-      } else {  // one MFMA, one LDS read in its shadow, ..., the ring refill behind the last MFMA (see conv_down3.hip)
+      // one MFMA, one LDS read in its shadow, ..., the ring refill behind the last MFMA (see conv_down3.hip)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+      for (int i = 0; i < 4; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
       }
+      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
     });
   };
 
-#ifdef LG_U3_STAMPS
-  int nst = 0;
-#define U3_STAMP() do { if (p.stamps && nst < 32) { unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (lane == 0) p.stamps[((long long)blockIdx.x * NWV + wid) * 32 + nst] = t_; ++nst; } } while (0)
-#else
-#define U3_STAMP() do {} while (0)
-#endif
   int roff = 0;  // ring position at the start of this wave's class (toggles 0 / 4 when F % RING == 4)
   for (int s = 0; s < nmine; ++s) {
     const bool more = s + 1 < nmine;
     int n, y0, x0;
-    U3_STAMP();  // item start
     const bool live = tile_of(s, tsel, n, y0, x0);  // (N = 32: the second tile of the last step may not exist: computed, not stored)
 
     using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
@@ -359,7 +334,6 @@ __global__ __launch_bounds__((Cfg<CS, N, NTT>::THREADS), 2) void conv_up3_kernel
     else if (cls == 1) run_class(I1{}, I0{}, I1{});
     else run_class(I0{}, I0{}, I0{});
 
-    U3_STAMP();  // class computed
     // The next step's halo is requested HERE, behind the MFMA stream, and lands under the staging pass and the barrier below.
     // (vmcnt retires in order: requested at the top of the step, these HBM loads sat in front of the weight ring's refills and
     //  every ring wait of the first fragments also waited for them.)  Last step: the current halo again — valid addresses, result
@@ -400,7 +374,6 @@ __global__ __launch_bounds__((Cfg<CS, N, NTT>::THREADS), 2) void conv_up3_kernel
       }
       if constexpr (STATS) sstat[tid] = f32x2{s1v[0] + s1v[1], s2v[0] + s2v[1]};  // reduced by ONE wave per tile behind the barrier
     }
-    U3_STAMP();  // staged
     int tns[C::NT], ty0s[C::NT], tx0s[C::NT];
     bool tlive[C::NT];
 #pragma unroll
@@ -425,7 +398,6 @@ __global__ __launch_bounds__((Cfg<CS, N, NTT>::THREADS), 2) void conv_up3_kernel
       }
     }
     if constexpr (!DEFER) __syncthreads();  // every class of the tile(s) is staged, every halo read is done
-    U3_STAMP();  // barrier 1 passed
 
     if (more) commit(hv);
     if constexpr (DEFER) {
@@ -506,8 +478,7 @@ __global__ __launch_bounds__((Cfg<CS, N, NTT>::THREADS), 2) void conv_up3_kernel
       }
     }
     (void)live;
-    U3_STAMP();  // rows out
-    if constexpr (C::ROT) cls = rot_class(wid + rsh + s + 1);
+    if constexpr (C::ROT) cls = rot_class(wid + s + 1);
     if constexpr (!DEFER) __syncthreads();  // next halo complete, staging area free again
   }
   if constexpr (DEFER) {  // the last tile's rows
@@ -537,9 +508,18 @@ int launch_up3(U3Params p, bool stats, hipStream_t st, bool fuse = false) {
 
 }  // namespace
 
-extern "C" int lg_conv_up3_supported(int B, int Hm, int Wm, int Cs, int N) {
-  return (!lg_env_flag("LG_NO_UP3") && B > 0 && Hm % TH == 0 && Wm % TW == 0 && ((Cs == 128 && N == 64) || (Cs == 64 && N == 32))) ? 1 : 0;
+// The one shape predicate of this file: the form the kernel takes for a shape, U3_NONE = not covered (conv_halo.hip takes it).
+// Kill switch and descriptor bounds included; lg_conv_up3_supported and the launcher both ask here.
+enum U3Tiling { U3_NONE = 0, U3_N64, U3_N32 };   // 128 -> 64 channels: one 8-wave workgroup per CU; 64 -> 32: two 4-wave ones
+static U3Tiling up3_tiling(int B, int Hm, int Wm, int Cs, int N) {
+  static int off = -1;
+  if (off < 0) off = lg_env_flag("LG_NO_UP3") ? 1 : 0;   // kill switch (cached: per-launch path, the table lookup takes a mutex)
+  if (off || B <= 0 || Hm % TH || Wm % TW) return U3_NONE;
+  if ((long long)Hm * Wm * Cs * 2 * 2 >= (1ll << 31)) return U3_NONE;  // buffer descriptor: two samples below the OOB offset
+  if ((long long)B * 4 * Hm * Wm * N * 2 >= 0xffffff00ll) return U3_NONE;   // the row stores: one descriptor over the whole output
+  return (Cs == 128 && N == 64) ? U3_N64 : (Cs == 64 && N == 32) ? U3_N32 : U3_NONE;
 }
+extern "C" int lg_conv_up3_supported(int B, int Hm, int Wm, int Cs, int N) { return up3_tiling(B, Hm, Wm, Cs, N) != U3_NONE ? 1 : 0; }
 
 // LG_OK: launched.  LG_ERR_UNSUPPORTED: the caller falls back to conv_halo.hip.  *nparts_out = records per sample (tiles).
 extern "C" int lg_conv_up3_nf_try(const void* src16, const void* wpack_up, const float* bias, void* out16, int B, int Hm, int Wm,
@@ -555,26 +535,18 @@ extern "C" int lg_conv_up3_nf_try(const void* src16, const void* wpack_up, const
                                   int Cs, int N, void* spart, size_t spart_bytes, int* nparts_out, const LgNormFuse* nf,
                                   size_t nf_bytes, void* stream) {
   if (nparts_out) *nparts_out = 0;
-  if (!src16 || !wpack_up || !out16 || !lg_conv_up3_supported(B, Hm, Wm, Cs, N)) return LG_ERR_UNSUPPORTED;
-  if ((long long)Hm * Wm * Cs * 2 * 2 >= (1ll << 31)) return LG_ERR_UNSUPPORTED;  // buffer descriptor: two samples below the OOB offset
-  if ((long long)B * 4 * Hm * Wm * N * 2 >= 0xffffff00ll) return LG_ERR_UNSUPPORTED;   // the row stores: one descriptor over the whole output
+  const U3Tiling tiling = up3_tiling(B, Hm, Wm, Cs, N);
+  if (tiling == U3_NONE || !src16 || !wpack_up || !out16) return LG_ERR_UNSUPPORTED;
   U3Params p{};
   p.src = (const __bf16*)src16; p.wp = (const char*)wpack_up; p.bias = bias; p.out = (__bf16*)out16;
   p.B = B; p.Hs = Hm; p.Ws = Wm; p.tpi_x = Wm / TW; p.tpi = p.tpi_x * (Hm / TH);
   const long long nitems = (long long)B * p.tpi;
   if (nitems <= 0 || nitems >= (1ll << 30)) return LG_ERR_UNSUPPORTED;
   p.nitems = (int)nitems;
-#ifdef LG_U3_STAMPS
-  { const char* e = getenv("LG_U3_STAMPBUF"); p.stamps = e ? (unsigned long long*)strtoull(e, nullptr, 0) : nullptr; }
-#endif
-  // N = 32: two independent 4-wave workgroups per CU, one tile per step (LG_U3_T4_8W=1: the round-2 form, one 8-wave workgroup
-  // with two tiles per step)
-  static int t4_8w = -1;
-  if (t4_8w < 0) t4_8w = lg_env_flag("LG_U3_T4_8W") ? 1 : 0;
-  { static int ro = -1; if (ro < 0) { const char* e = getenv("LG_U3_ROTOFF"); ro = e ? (atoi(e) & 3) : 0; } p.rotoff = ro; }   // A/B (round 5, measured: 141 - 145 us for offsets 0 / 1 / 2 — no effect, default 0)
-  // the norm-backward sums are produced by the one-tile-per-step forms only: with two tiles per step a thread's row sweep covers
-  // both tiles, i.e. possibly two samples, and the per-thread sums would mix them (no layer of the step asks for that form)
-  const bool fuse = (Cs == 128 || !t4_8w) && nf && nf->z && nf->stats && nf->part && nparts_out && (size_t)B * p.tpi * 2 * sizeof(double) <= nf_bytes;
+  // N = 32: two independent 4-wave workgroups per CU, one tile per step (the round-2 form — one 8-wave workgroup with two tiles per
+  // step — lost: 49 % of its step was not MFMA time and nothing overlapped it).  The norm-backward sums need one tile per step: with
+  // two a thread's row sweep would cover two tiles, i.e. possibly two samples.
+  const bool fuse = nf && nf->z && nf->stats && nf->part && nparts_out && (size_t)B * p.tpi * 2 * sizeof(double) <= nf_bytes;
   const bool stats = !fuse && spart && nparts_out && (size_t)B * p.tpi * 3 * sizeof(double) <= spart_bytes;
   // moments asked for (the caller may then write z as bf16 ONLY) but the workspace cannot hold this tiling's records: decline, so
   // that the dispatch chain tries the next kernel instead of launching without them (lg_conv_fwd_stats_fused's promise)
@@ -582,11 +554,10 @@ extern "C" int lg_conv_up3_nf_try(const void* src16, const void* wpack_up, const
   p.spart = stats ? (double*)spart : nullptr;
   if (fuse) p.nf = *nf;
   hipStream_t st = (hipStream_t)stream;
-  if (Cs == 128) launch_up3<128, 64>(p, stats, st, fuse);
-  else if (t4_8w) launch_up3<64, 32>(p, stats, st, fuse);
+  if (tiling == U3_N64) launch_up3<128, 64>(p, stats, st, fuse);
   else launch_up3<64, 32, 1>(p, stats, st, fuse);
   LG_CHECK_LAUNCH("lg_conv_up3");
-  lg_note_kernel(Cs == 128 ? "conv_up3_kernel<128,64>" : t4_8w ? "conv_up3_kernel<64,32>" : "conv_up3_kernel<64,32,4w>");
+  lg_note_kernel(tiling == U3_N64 ? "conv_up3_kernel<128,64>" : "conv_up3_kernel<64,32,4w>");
   if (stats || fuse) *nparts_out = p.tpi;
   return LG_OK;
 }

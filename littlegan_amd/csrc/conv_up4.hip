@@ -10,7 +10,7 @@
 //   * an item is (8 x 16 source tile, PARITY CLASS, 128-column tile): the four classes of a tile are four items — a class
 //     is a stride-1 contraction over the 10 x 18 halo with 4 / 6 / 6 / 9 taps, and with N >= 128 an output pixel is a
 //     256-B run by itself, so the classes need no common staging area (conv_up3.hip needs one for N = 32 / 64);
-//   * a BLOCK is bound to one class for its whole life (the grid is split 9 : 6 : 6 : 4 between the classes, the tap counts):
+//   * a BLOCK is bound to one class PAIR for its whole life and runs the two classes one after the other (see the kernel):
 //     the slice body then exists ONCE inside each persistent loop.  (Switching the class per item put four to eight
 //     instantiations of the body inside one loop: 256 VGPRs + ~100 spills, among them the per-lane LDS bases, and every
 //     reload in the tap loop was a scratch_load + s_waitcnt vmcnt(0) that also drained the weight ring — 162 us against
@@ -18,7 +18,6 @@
 //   * a slice is 64 channels (4 k-steps per tap): 16 .. 36 fragments = 64 .. 144 MFMAs per wave between two barriers;
 //   * the ring holds 8 fragments (12 for the 9-tap class, whose 36 fragments per slice are not a multiple of 8), so the ring
 //     position of a fragment is a compile-time register.
-#include <stdlib.h>
 #include <type_traits>
 #include "lg_common.h"
 
@@ -50,10 +49,7 @@ struct U4Params {
   double* spart;       // [B][nparts][3] or null
   int B, Hs, Ws, Cs, N, N32, KB;
   int tpi_x, tpi, ntn, nper, nparts;   // nper = items per class
-  int gend[4];         // block ranges: class rank rk (taps 9, 6, 6, 4) owns blocks [gend[rk-1], gend[rk])
-  int xcdmajor;        // class-pair mode: XCD-major block ranks inside a type (LG_U4_XCD; see the kernel)
-  int mfast, ntm;      // mfast: item -> (row tile fastest, column tile); ntm = row tiles (LG_U4_MFAST, with xcdmajor: an XCD's blocks share ONE column tile's weights)
-  int pairmode;        // 1 (default): blocks [0, gend[0]) run classes 3 then 0, blocks [gend[0], gend[1]) classes 1 then 2 (see the kernel)
+  int ga, gb;          // blocks [0, ga) run classes 3 then 0 (9 + 4 taps), blocks [ga, ga + gb) classes 1 then 2 (6 + 6) (see the kernel)
   LgNormFuse nf;
 };
 
@@ -118,8 +114,8 @@ __device__ __forceinline__ void up4_run(const U4Params& p, char* smem, int lb, i
   auto decode = [&](int k) {
     const int rest = lb + k * G;
     Item it;
-    it.tn = p.mfast ? rest / p.ntm : rest % p.ntn;
-    const int tm = p.mfast ? rest - it.tn * p.ntm : rest / p.ntn;
+    it.tn = rest % p.ntn;
+    const int tm = rest / p.ntn;
     if constexpr (PAIR) { it.n = 2 * tm; it.y0 = 0; it.x0 = 0; return it; }
     it.n = tm / p.tpi;
     const int tt = tm - it.n * p.tpi;
@@ -366,44 +362,39 @@ template <bool STATS, bool FUSE, bool PAIR = false>
 __global__ __launch_bounds__(256, 2) void conv_up4_kernel(const U4Params p) {
   static_assert(!(STATS && FUSE), "forward moments and backward sums are never needed together");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int b = blockIdx.x;  // (uniform) class of this block: rank 0..3 = classes 3, 1, 2, 0
+  const int b = blockIdx.x;  // (uniform)
   // CLASS PAIRS (round 4): with one class per block the four classes' item counts are equal but their lengths are 9 : 6 : 6 : 4 taps,
   // and whole items cannot be dealt 9 : 6 : 6 : 4 over 512 slots — at B = 256 the 8 x 8 level has 256 items per class: the 9-tap
   // blocks take 2 items (18 tap units) or 1, the 6-tap ones 3 or 2, the 4-tap ones 4 or 3, and the launch lasts 18 units against a
   // mean of 12.5 (16 x 16 level: 30 against 25).  A block bound to the class PAIR (3, 0) or (1, 2) runs two persistent loops back to
   // back — still ONE slice body per loop, so no register growth — and a pair is 13 or 12 tap units: 256 + 256 blocks take exactly
-  // one item of each of their classes.  Measured: see DESIGN 10.
-  if (p.pairmode) {
-    // xcdmajor (round 5, LG_U4_XCD): a block's rank inside its type is XCD-major (lg_xcd_remap) — consecutive items, i.e. the column tiles of
-    // one source tile and neighbouring tiles, then run on ONE XCD and share its L2 (with the plain rank they are dealt round-robin over
-    // the eight L2s).  Valid while the hardware deals blocks to XCDs by blockIdx & 7 and gend[0] is a multiple of 8 (checked on the host).
-    const int ga = p.gend[0], gb = p.gend[1] - p.gend[0];
-    if (b < ga) {
-      const int lb = p.xcdmajor ? lg_xcd_remap(b, ga) : b;
-      up4_run<3, STATS, FUSE, PAIR>(p, smem, lb, ga);
-      __syncthreads();
-      up4_run<0, STATS, FUSE, PAIR>(p, smem, lb, ga);
-    } else {
-      const int lb = p.xcdmajor ? lg_xcd_remap(b - ga, gb) : b - ga;
-      up4_run<1, STATS, FUSE, PAIR>(p, smem, lb, gb);
-      __syncthreads();
-      up4_run<2, STATS, FUSE, PAIR>(p, smem, lb, gb);
-    }
-    return;
+  // one item of each of their classes.  Measured: see DESIGN 10.  (XCD-major block ranks inside a type, and with them row-tile-fastest
+  // items: measured in round 5, not adopted — DESIGN 11.)
+  if (b < p.ga) {
+    up4_run<3, STATS, FUSE, PAIR>(p, smem, b, p.ga);
+    __syncthreads();
+    up4_run<0, STATS, FUSE, PAIR>(p, smem, b, p.ga);
+  } else {
+    up4_run<1, STATS, FUSE, PAIR>(p, smem, b - p.ga, p.gb);
+    __syncthreads();
+    up4_run<2, STATS, FUSE, PAIR>(p, smem, b - p.ga, p.gb);
   }
-  if (b < p.gend[0]) up4_run<3, STATS, FUSE, PAIR>(p, smem, b, p.gend[0]);
-  else if (b < p.gend[1]) up4_run<1, STATS, FUSE, PAIR>(p, smem, b - p.gend[0], p.gend[1] - p.gend[0]);
-  else if (b < p.gend[2]) up4_run<2, STATS, FUSE, PAIR>(p, smem, b - p.gend[1], p.gend[2] - p.gend[1]);
-  else up4_run<0, STATS, FUSE, PAIR>(p, smem, b - p.gend[2], p.gend[3] - p.gend[2]);
 }
 
 }  // namespace
 
-extern "C" int lg_conv_up4_supported(int B, int Hm, int Wm, int Cs, int N) {
-  const bool pair = Hm == 8 && Wm == 8 && B % 2 == 0 && !lg_env_flag("LG_NO_UP4_PAIR");   // 8 x 8 maps: a tile = two samples
-  return (!lg_env_flag("LG_NO_UP4") && B > 0 && ((Hm % TH == 0 && Wm % TW == 0) || pair) && Cs % KC == 0 && N % 128 == 0 &&
-          (long long)Hm * Wm * Cs * 2 * 2 < (1ll << 31)) ? 1 : 0;   // (two samples below the out-of-range offset of the halo loads)
+// The one shape predicate of this file: the tiling the kernel takes for a shape, U4_NONE = not covered (conv_halo.hip takes it).
+// Kill switch and descriptor bound included; lg_conv_up4_supported and the launcher both ask here.
+enum U4Tiling { U4_NONE = 0, U4_PLAIN, U4_PAIR };
+static U4Tiling up4_tiling(int B, int Hm, int Wm, int Cs, int N) {
+  static int off = -1;
+  if (off < 0) off = lg_env_flag("LG_NO_UP4") ? 1 : 0;   // kill switch (cached: per-launch path, the table lookup takes a mutex)
+  if (off || B <= 0 || Cs % KC || N % 128) return U4_NONE;
+  if ((long long)Hm * Wm * Cs * 2 * 2 >= (1ll << 31)) return U4_NONE;   // two samples below the out-of-range offset of the halo loads
+  if (Hm == 8 && Wm == 8 && B % 2 == 0) return U4_PAIR;                 // 8 x 8 maps: a tile = two samples
+  return (Hm % TH == 0 && Wm % TW == 0) ? U4_PLAIN : U4_NONE;
 }
+extern "C" int lg_conv_up4_supported(int B, int Hm, int Wm, int Cs, int N) { return up4_tiling(B, Hm, Wm, Cs, N) != U4_NONE ? 1 : 0; }
 
 // LG_OK: launched.  LG_ERR_UNSUPPORTED: the caller falls back to conv_halo.hip.  Hm, Wm: the SOURCE (small) map.
 // nf (optional; data-gradient use): also the norm-backward sums of the produced gradient ([B][*nparts_out][2] doubles)
@@ -411,15 +402,12 @@ extern "C" int lg_conv_up4_nf_try(const void* src16, const void* wpack_up, const
                                   int Cs, int N, void* spart, size_t spart_bytes, int* nparts_out, const LgNormFuse* nf,
                                   size_t nf_bytes, void* stream) {
   if (nparts_out) *nparts_out = 0;
-  static int off = -1;
-  if (off < 0) off = lg_env_flag("LG_NO_UP4") ? 1 : 0;
-  if (off || !src16 || !wpack_up || !out16 || !lg_conv_up4_supported(B, Hm, Wm, Cs, N)) return LG_ERR_UNSUPPORTED;
+  const U4Tiling tiling = up4_tiling(B, Hm, Wm, Cs, N);
+  if (tiling == U4_NONE || !src16 || !wpack_up || !out16) return LG_ERR_UNSUPPORTED;
+  const bool pair = tiling == U4_PAIR;
   U4Params p{};
   p.src = (const __bf16*)src16; p.wp = (const char*)wpack_up; p.bias = bias; p.out = (__bf16*)out16;
   p.B = B; p.Hs = Hm; p.Ws = Wm; p.Cs = Cs; p.N = N; p.N32 = N / 32; p.KB = Cs / 16;
-  static int nopair = -1;
-  if (nopair < 0) nopair = lg_env_flag("LG_NO_UP4_PAIR") ? 1 : 0;
-  const bool pair = Hm == 8 && Wm == 8 && B % 2 == 0 && !nopair;
   p.tpi_x = pair ? 1 : Wm / TW; p.tpi = pair ? 1 : p.tpi_x * (Hm / TH); p.ntn = N / 128;
   const long long nper = (long long)(pair ? B / 2 : B) * p.tpi * p.ntn;
   if (nper <= 0 || 4 * nper >= (1ll << 30)) return LG_ERR_UNSUPPORTED;
@@ -442,47 +430,19 @@ extern "C" int lg_conv_up4_nf_try(const void* src16, const void* wpack_up, const
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>((conv_up4_kernel<false, false, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>((conv_up4_kernel<false, true, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
   }
-  // the grid is split between the classes in proportion to their tap counts (9 : 6 : 6 : 4), at most one block per item
-  int grid = 0;
-  static int classpair = -1;
-  if (classpair < 0) classpair = lg_env_flag("LG_U4_NO_CLASSPAIR") ? 0 : 1;
-  p.pairmode = classpair;
-  if (classpair) {
-    // blocks of type A run classes (3, 0): 13 tap units per item pair; type B classes (1, 2): 12.  GA + GB <= nblk, each <= nper:
-    // the split with the smallest makespan max(ceil(nper / GA) * 13, ceil(nper / GB) * 12); ties go to the split with fewer idle slots.
-    long long best = -1;
-    int ga_best = 1, gb_best = 1;
-    for (int ga = 1; ga < nblk && ga <= p.nper; ++ga) {
-      int gb = nblk - ga;
-      if (gb > p.nper) gb = p.nper;
-      if (gb < 1) break;
-      const long long ca = (long long)((p.nper + ga - 1) / ga) * 13, cb = (long long)((p.nper + gb - 1) / gb) * 12;
-      const long long cost = (ca > cb ? ca : cb) * 4096 - (ga + gb);   // makespan first, then as many blocks as fit
-      if (best < 0 || cost < best) { best = cost; ga_best = ga; gb_best = gb; }
-    }
-    p.gend[0] = ga_best; p.gend[1] = ga_best + gb_best; p.gend[2] = p.gend[3] = p.gend[1];
-    { static int xm = -1; if (xm < 0) xm = lg_env_flag("LG_U4_XCD") ? 1 : 0; p.xcdmajor = (xm && ga_best % 8 == 0) ? 1 : 0; }
-    {
-      static int mf = -1;
-      if (mf < 0) mf = lg_env_flag("LG_U4_MFAST") ? 1 : 0;
-      p.ntm = p.nper / p.ntn;
-      p.mfast = (mf && p.ntn > 1 && ga_best % 8 == 0 && gb_best % 8 == 0) ? 1 : 0;
-      if (p.mfast) p.xcdmajor = 1;
-    }
-    grid = ga_best + gb_best;
-  } else
-  {
-    const int taps[4] = {9, 6, 6, 4};
-    int left = nblk;
-    for (int rk = 0; rk < 4; ++rk) {
-      int g = rk == 3 ? left : (nblk * taps[rk] + 12) / 25;
-      if (g > left - (3 - rk)) g = left - (3 - rk);
-      if (g < 1) g = 1;
-      if (g > p.nper) g = p.nper;
-      left -= g; grid += g;
-      p.gend[rk] = grid;
-    }
+  // blocks of type A run classes (3, 0): 13 tap units per item pair; type B classes (1, 2): 12.  GA + GB <= nblk, each <= nper:
+  // the split with the smallest makespan max(ceil(nper / GA) * 13, ceil(nper / GB) * 12); ties go to the split with fewer idle slots.
+  long long best = -1;
+  p.ga = p.gb = 1;
+  for (int ga = 1; ga < nblk && ga <= p.nper; ++ga) {
+    int gb = nblk - ga;
+    if (gb > p.nper) gb = p.nper;
+    if (gb < 1) break;
+    const long long ca = (long long)((p.nper + ga - 1) / ga) * 13, cb = (long long)((p.nper + gb - 1) / gb) * 12;
+    const long long cost = (ca > cb ? ca : cb) * 4096 - (ga + gb);   // makespan first, then as many blocks as fit
+    if (best < 0 || cost < best) { best = cost; p.ga = ga; p.gb = gb; }
   }
+  const int grid = p.ga + p.gb;
   hipStream_t st = (hipStream_t)stream;
   if (pair) {
     if (fuse) hipLaunchKernelGGL((conv_up4_kernel<false, true, true>), dim3(grid), dim3(256), LDS_BYTES, st, p);

@@ -26,9 +26,13 @@ extern "C" void lg_set_error(const char* fmt, ...);
 extern "C" void lg_note_kernel(const char* name);
 extern "C" unsigned long long* lg_clock_census(void);   // runtime.hip: buffer of the in-kernel clock census, or null
 
-// 1 if the environment variable is set to a non-empty value; read ONCE per process at its first use (runtime.hip), so a
-// *_supported query and the launch it promises always agree.  `name` must be a string literal.
+// 1 if the environment variable is set to a non-empty value; read ONCE per process at its first use (runtime.hip).  Every name
+// has ONE call site — a kernel file's shape predicate, which its *_supported query and its launcher share.  `name` must be a string literal.
 extern "C" int lg_env_flag(const char* name);
+// Kill switches that more than one file asks about, each read in ONE place: LG_NO_HALO (conv_igemm.hip: the per-tap gather kernel takes
+// every shape of conv_halo.hip), LG_NO_N3 (capi.hip: the generic kernels take the 3-channel layers).  1 = the kernels are in use.
+extern "C" int lg_halo_enabled(void);
+extern "C" int lg_n3_enabled(void);
 // CUs the persistent kernels may fill: device CUs minus those reserved for communication kernels (lg_set_reserved_cus)
 extern "C" int lg_grid_cus(void);
 
@@ -138,12 +142,7 @@ __device__ __forceinline__ u32x4 lg_norm8(const u32x4 z8, float mu, float mul, f
     t0 = lg_leaky(t0, alpha); t1 = lg_leaky(t1, alpha);
     // ONE v_cvt_pk_bf16_f32 per pair (RNE, as the scalar cast): converting the halves separately and or-ing them together costs 4
     typedef __bf16 lg_bf16x2 __attribute__((ext_vector_type(2)));
-#ifdef LG_NORM8_OLD   // A/B builds only
-    const __bf16 h0 = (__bf16)t0, h1 = (__bf16)t1;
-    o[k] = (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
-#else
     o[k] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{t0, t1}, lg_bf16x2));
-#endif
   }
   return o;
 }

@@ -5,7 +5,6 @@
 //   n3_s1t_fwd : y[B,H,W,3] = tanh(convT_s1(x[B,H,W,C]) + b)            /root/reference/model.py:86-87,104
 //   n3_up      : dimg[B,2H,2W,3] = conv2d_backprop_input(dz[B,H,W,C])   (gradient of Encoder.conv1, model.py:15)
 //   n3_wgrad   : dW[5][5][3][C] (+)= sum big3[s*o + k - pad][c3] * small[o][c]   (conv1: s=2,pad=1; final: s=1,pad=2)
-#include <stdlib.h>
 #include "lg_common.h"
 
 namespace {
@@ -126,11 +125,10 @@ __global__ __launch_bounds__(256) void n3_up_kernel(const float* __restrict__ sr
 // 3-channel tensor (per-lane row offset + per-k pixel base), B[k][j] is the small tensor's pixel row.
 // Block = 4 waves, pixel tile 8x16: wave w reduces pixels [32w, 32w+32); the waves merge into one fp32 slab per block.
 // --------------------------------------------------------------------------------------------------------------
-// S16: `small` is read from its bf16 mirror (bf16 path; the values are widened exactly, the MFMA stays f32).
-template <int NT, bool S16>
+// (exact-f32 path; the bf16 path takes n3_wgrad16_kernel below)
+template <int NT>
 __global__ __launch_bounds__(256) void n3_wgrad_kernel(const float* __restrict__ big3, const float* __restrict__ small,
-                                                       const __bf16* __restrict__ small16, float* __restrict__ slab,
-                                                       int B, int H, int W, int s, int pad) {
+                                                       float* __restrict__ slab, int B, int H, int W, int s, int pad) {
   constexpr int Cs = NT * 32, TH = 8, TW = 16;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int HH = s * TH + 4, HW = s * TW + 4;  // halo of the 3-channel tensor (taps span 5 pixels)
@@ -164,14 +162,7 @@ __global__ __launch_bounds__(256) void n3_wgrad_kernel(const float* __restrict__
       const int pix = i / (Cs / 4), c4 = i % (Cs / 4);
       const int yy = y0 + pix / TW, xx = x0 + pix % TW;
       const long long go = ((long long)(n * H + yy) * W + xx) * Cs + c4 * 4;
-      f32x4 v;
-      if constexpr (S16) {
-        const bf16x4 t = *reinterpret_cast<const bf16x4*>(small16 + go);
-        v = f32x4{(float)t[0], (float)t[1], (float)t[2], (float)t[3]};
-      } else {
-        v = *reinterpret_cast<const f32x4*>(small + go);
-      }
-      *reinterpret_cast<f32x4*>(sB + pix * Cs + c4 * 4) = v;
+      *reinterpret_cast<f32x4*>(sB + pix * Cs + c4 * 4) = *reinterpret_cast<const f32x4*>(small + go);
     }
     for (int i = threadIdx.x; i < HH * HW * 3; i += 256) {
       const int hp = i / 3, c3 = i - hp * 3;
@@ -241,11 +232,9 @@ __global__ __launch_bounds__(256) void n3_wgrad_kernel(const float* __restrict__
 // + 3 — so a wave carries 64 accumulator registers instead of 128 and the kernel fits three blocks per CU (round 4: at 256 registers
 // and two blocks every ablation that happened to free registers ran the conv1 weight gradient in ~100 instead of 164 us whatever it
 // removed; held to 168 registers by launch bounds alone it spilled 73).
-#ifndef LG_N3W_LB
-#define LG_N3W_LB 3   // blocks per CU the 64-channel forms are compiled for (A/B builds)
-#endif
+constexpr int N3W_LB = 3;   // blocks per CU the 64-channel forms are compiled for
 template <int NT, int TH = 8, int S = 1>
-__global__ __launch_bounds__(256, NT == 2 ? LG_N3W_LB : 1) void n3_wgrad16_kernel(const float* __restrict__ big3, const __bf16* __restrict__ small16,
+__global__ __launch_bounds__(256, NT == 2 ? N3W_LB : 1) void n3_wgrad16_kernel(const float* __restrict__ big3, const __bf16* __restrict__ small16,
                                                          float* __restrict__ slab, int B, int H, int W, int s_unused, int pad) {
   static_assert(TH == 8 || (TH == 16 && NT == 1 && S == 1), "tile heights");
   static_assert(S == 1 || S == 2, "strides");
@@ -423,9 +412,7 @@ __global__ __launch_bounds__(256) void n3_slab_reduce_kernel(const float* __rest
 // persistent blocks: Cs 64: 3 per CU since the channel-split waves of round 4 (168 registers; 512 / 768 / 1024 blocks: 173 / 138 / 180 us
 // at 2B; before, at 256 registers, 2 per CU was best); Cs 32: 3 per CU (512 / 768 / 1024 / 1536: 121 / 112 / 127 / 120 us with its bias sums)
 inline int wgrad_blocks(int ntiles, int Cs, bool f32_path = false) {
-  static int f32 = -1, f64 = -1;
-  if (f32 < 0) { const char* e = getenv("LG_N3W_CAP32"); f32 = e ? atoi(e) : 0; const char* g = getenv("LG_N3W_CAP64"); f64 = g ? atoi(g) : 0; }
-  const int cap = Cs > 32 ? (f64 > 0 ? f64 : (f32_path ? 512 : 768)) : (f32 > 0 ? f32 : 768);   // (the fp32-source kernel at 64 channels: 41 KB of LDS, 2 per CU measured best)  // measured with the prefetch (256..2048): Cs 64: 128 / 82 / 109 / 99 / 113 / 130 us, Cs 32: 320 / 212 / 182 / 214 / 189 / 200 us
+  const int cap = (Cs > 32 && f32_path) ? 512 : 768;   // (the fp32-source kernel at 64 channels: 41 KB of LDS, 2 per CU measured best)  // measured with the prefetch (256..2048): Cs 64: 128 / 82 / 109 / 99 / 113 / 130 us, Cs 32: 320 / 212 / 182 / 214 / 189 / 200 us
   return ntiles < cap ? ntiles : cap;
 }
 
@@ -474,23 +461,18 @@ extern "C" int lg_n3_wgrad_try(const float* big3, const float* small, const void
   if (ws_bytes < lg_n3_wgrad_workspace_bytes(B, H, W, Cs)) return LG_ERR_UNSUPPORTED;
   if (!big3 || (!small && !small16)) return LG_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  static int th8 = -1;
-  if (th8 < 0) th8 = lg_env_flag("LG_N3W_TH8") ? 1 : 0;   // A/B switch
-  static int n3w_f32 = -1;
-  if (n3w_f32 < 0) n3w_f32 = lg_env_flag("LG_N3W_F32") ? 1 : 0;   // (cached per call site: the table lookup takes a mutex)
-  const bool th16 = Cs == 32 && s == 1 && H % 16 == 0 && small16 && !n3w_f32 && !th8;   // 16-row tiles (bf16 path, final layer)
-  const bool p16 = small16 && !n3w_f32;
+  const bool p16 = small16 != nullptr;   // bf16 path: bf16 MFMA straight from the mirror
+  const bool th16 = Cs == 32 && s == 1 && H % 16 == 0 && p16;   // 16-row tiles (bf16 path, final layer)
   const int ntiles = B * (H / (th16 ? 16 : 8)) * (W / 16), nblk = wgrad_blocks(ntiles, Cs, !p16);   // (the workspace is sized for the larger grid)
   const size_t lds = (size_t)(128 * Cs + (s * 8 + 4) * (s * 16 + 4) * 3 + 4) * 4;
   const __bf16* s16 = (const __bf16*)small16;
   static bool a = false;
   if (!a) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(n3_wgrad_kernel<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(n3_wgrad_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(n3_wgrad_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
     a = true;
   }
   float* slab = (float*)workspace;
-  if (s16 && !n3w_f32) {  // bf16 path: bf16 MFMA straight from the mirror
+  if (p16) {
     // LDS: the wide operand's tile (also the merge buffer) + the bf16 RGBx halo of the 3-channel operand and its zero region
     auto ldsz = [&](int cs, int th = 8) {
       const size_t sb = (size_t)th * 16 * (cs * 2 + 16), mg = (size_t)75 * cs * 4;
@@ -502,14 +484,12 @@ extern "C" int lg_n3_wgrad_try(const float* big3, const float* small, const void
     else if (s == 1) hipLaunchKernelGGL((n3_wgrad16_kernel<2, 8, 1>), dim3(nblk), dim3(256), ldsz(64), st, big3, s16, slab, B, H, W, s, pad);
     else hipLaunchKernelGGL((n3_wgrad16_kernel<2, 8, 2>), dim3(nblk), dim3(256), ldsz(64), st, big3, s16, slab, B, H, W, s, pad);
   } else if (Cs == 32) {
-    if (s16) hipLaunchKernelGGL((n3_wgrad_kernel<1, true>), dim3(nblk), dim3(256), lds, st, big3, small, s16, slab, B, H, W, s, pad);
-    else hipLaunchKernelGGL((n3_wgrad_kernel<1, false>), dim3(nblk), dim3(256), lds, st, big3, small, s16, slab, B, H, W, s, pad);
+    hipLaunchKernelGGL(n3_wgrad_kernel<1>, dim3(nblk), dim3(256), lds, st, big3, small, slab, B, H, W, s, pad);
   } else {
-    if (s16) hipLaunchKernelGGL((n3_wgrad_kernel<2, true>), dim3(nblk), dim3(256), lds, st, big3, small, s16, slab, B, H, W, s, pad);
-    else hipLaunchKernelGGL((n3_wgrad_kernel<2, false>), dim3(nblk), dim3(256), lds, st, big3, small, s16, slab, B, H, W, s, pad);
+    hipLaunchKernelGGL(n3_wgrad_kernel<2>, dim3(nblk), dim3(256), lds, st, big3, small, slab, B, H, W, s, pad);
   }
   LG_CHECK_LAUNCH("lg_n3_wgrad");
-  lg_note_kernel((s16 && !n3w_f32) ? (th16 ? "n3_wgrad16_kernel<1,16>" : Cs == 32 ? "n3_wgrad16_kernel<1>" : "n3_wgrad16_kernel<2>") : "n3_wgrad_kernel<f32>");
+  lg_note_kernel(p16 ? (th16 ? "n3_wgrad16_kernel<1,16>" : Cs == 32 ? "n3_wgrad16_kernel<1>" : "n3_wgrad16_kernel<2>") : "n3_wgrad_kernel<f32>");
   const int n = 75 * Cs;
   hipLaunchKernelGGL(n3_slab_reduce_kernel, dim3((n + 15) / 16), dim3(256), 0, st, (const float*)workspace, dw, nblk, n,
                      accumulate);

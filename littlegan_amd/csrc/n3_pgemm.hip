@@ -12,7 +12,6 @@
 //   up_p16      : dimg[B,2H,2W,3] = conv2d_backprop_input(dz16[B,H,W,C])  (gradient of Encoder.conv1, model.py:15)
 // Weights come from the verbatim fp32 copy in the pack (pack.hip, cb == 3) and are rounded to bf16 (RNE) here, the
 // same rounding the packed MFMA operands get; accumulation is fp32 throughout.
-#include <stdlib.h>
 #include <type_traits>
 #include "lg_common.h"
 
@@ -100,12 +99,10 @@ __global__ __launch_bounds__(256) void s1t_fwd_p16_kernel(const __bf16* __restri
 }
 
 // one thread per SOURCE pixel q of a 16x16 tile; it owns the 2x2 output quad (4 parity classes x 3 channels)
+// (One A-fragment set — no tile-ahead prefetch — compiled for three blocks per CU (168 VGPRs), round 4, same box, a grid of 768:
+//  58.0 against 64.4 us at B = 256, 119.9 against 117.1 at 2B — not adopted.)
 template <int C>
-#ifndef LG_UP16_SINGLE
-#define LG_UP16_SINGLE 0   // A/B builds: 1 = one A-fragment set (no tile-ahead prefetch), compiled for three blocks per CU (168 VGPRs).
-                           // Round 4, same box, LG_PATCH_GRID=768: 58.0 against 64.4 us at B = 256, 119.9 against 117.1 at 2B — not adopted
-#endif
-__global__ __launch_bounds__(256, LG_UP16_SINGLE ? 3 : 1) void up_p16_kernel(const __bf16* __restrict__ src16, const float* __restrict__ w,
+__global__ __launch_bounds__(256, 1) void up_p16_kernel(const __bf16* __restrict__ src16, const float* __restrict__ w,
                                                      float* __restrict__ out, int B, int H, int W) {
   constexpr int HS = TS + 2, NQ = HS * HS, NMT = (NQ + 15) / 16, MTW = (NMT + 3) / 4, KH = C / 32;
   __shared__ float sP[NMT * 16 * PR];
@@ -173,11 +170,6 @@ __global__ __launch_bounds__(256, LG_UP16_SINGLE ? 3 : 1) void up_p16_kernel(con
         for (int co = 0; co < 3; ++co) o[px * 3 + co] = acc[py * 2 + px][co];
     }
   };
-#if LG_UP16_SINGLE
-  bf16x8 afS[MTW][KH];
-  for (int t = blockIdx.x; t < ntiles; t += G) { load_af(t, afS); compute(t, afS); }
-  return;
-#endif
   bf16x8 afA[MTW][KH], afB[MTW][KH];
   int t = blockIdx.x;
   if (t < ntiles) load_af(t, afA);
@@ -414,16 +406,14 @@ __global__ __launch_bounds__(256, 4) void patch_p16_kernel(const float* __restri
 // persistent grid of the patch kernels: a block sets up 12-24 weight fragments (8 converted weights each per lane) and then
 // walks its tiles with the next halo in flight, so it should own several tiles; 3 blocks fit a CU (160 VGPRs)
 static int patch_grid(int ntiles, int per_cu) {  // per_cu: resident blocks per CU of the instantiation (VGPR-limited)
-  static int cus = 0, forced = -1;
+  static int cus = 0;
   if (!cus) {
-    const char* e = getenv("LG_PATCH_GRID");
-    forced = e ? atoi(e) : 0;
     int dev = 0;
     hipDeviceProp_t pr;
     cus = 256;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) cus = pr.multiProcessorCount;
   }
-  const int nb = forced > 0 ? forced : per_cu * (cus < lg_grid_cus() ? cus : lg_grid_cus());
+  const int nb = per_cu * (cus < lg_grid_cus() ? cus : lg_grid_cus());
   return ntiles < nb ? ntiles : nb;
 }
 

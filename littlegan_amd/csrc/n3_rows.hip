@@ -15,7 +15,6 @@
 // NORM: the input is the raw bf16 conv output z of the last decoder level and h = bf16(leaky(a*((z-mu)-mu_lo)+beta)) is
 // formed while staging (same arithmetic, same rounding as apply16_kernel in norm.hip) — the stand-alone apply pass and the
 // h16 tensor of the 128x128x32 map disappear.
-#include <stdlib.h>
 #include <type_traits>
 #include "lg_common.h"
 
@@ -220,22 +219,22 @@ __global__ __launch_bounds__(256, XJ == 2 ? 2 : 1) void s1t_fwd_rows_kernel(cons
 
 }  // namespace
 
-extern "C" int lg_n3_rows_supported(int H, int W, int C) { return (W % 16 == 0 && H >= 1 && C == 32) ? 1 : 0; }
+extern "C" int lg_n3_rows_supported(int H, int W, int C) {   // the one predicate of this kernel: kill switch and shape
+  static int off = -1;
+  if (off < 0) off = lg_env_flag("LG_NO_ROWS") ? 1 : 0;   // (cached: per-launch path, the table lookup takes a mutex)
+  return (!off && W % 16 == 0 && H >= 1 && C == 32) ? 1 : 0;
+}
 
 // x16: the bf16 input h [B,H,W,C]; or, with stats != null, the raw bf16 conv output z of the level below, normalised +
 // LeakyReLU(alpha)'d on the fly from its statistics records [B][8] (norm.hip)
 extern "C" int lg_n3_s1t_fwd_rows_try(const void* x16, const float* stats, float alpha, const float* w, const float* bias, float* y,
                                       int B, int H, int W, int C, void* stream) {
-  static int off = -1;
-  if (off < 0) off = lg_env_flag("LG_NO_ROWS") ? 1 : 0;
-  if (off || !lg_n3_rows_supported(H, W, C) || !x16 || !w || !bias || !y) return LG_ERR_UNSUPPORTED;
+  if (!lg_n3_rows_supported(H, W, C) || !x16 || !w || !bias || !y) return LG_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   const int RB = H <= 64 ? H : 64;
   const RowsNormIn ni{stats, alpha};
   const __bf16* x = (const __bf16*)x16;
-  static int no2 = -1;
-  if (no2 < 0) no2 = lg_env_flag("LG_ROWS_XJ1") ? 1 : 0;   // A/B switch: the one-pixel-per-row form everywhere
-  const bool xj2 = W % 32 == 0 && !no2;
+  const bool xj2 = W % 32 == 0;   // two pixels per row wherever the width allows (the one-pixel form everywhere: measured slower)
   const int sw = xj2 ? 32 : 16;
   const dim3 grid(B * ((W + 4 * sw - 1) / (4 * sw)) * ((H + RB - 1) / RB));
   if (xj2) {

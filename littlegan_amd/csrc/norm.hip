@@ -102,24 +102,20 @@ __global__ __launch_bounds__(64) void stats_final_kernel(const double* __restric
   }
 }
 
-// Non-temporal accesses of the element-wise passes, bf16 and fp32 path alike (bits: 1 backward-apply loads, 2 backward-apply stores, 4 apply loads, 8 apply stores).
+// Non-temporal LOADS in the element-wise passes (apply and backward apply), bf16 and fp32 path alike; their stores are plain.
 // z, g and the skip map are dead behind these passes (z is read again only a whole tape later): loaded non-temporally they stop evicting
 // what the neighbouring conv kernels live on (their sources and weights in L2 / the Infinity Cache).  Round 4, whole step on one box,
 // variant builds, two rounds: 11.15 / 11.17 ms (0) -> 11.06 / 11.07 (1) -> 10.98 / 10.97 (5) = -1.6 %; the stores (3, 7: 11.07 / 10.98) add
 // nothing there — although the passes in isolation (scripts/bench_norm.py) show the opposite: stores -9 .. -13 %, loads nothing.
 // The same treatment of the final layer's input rows, the final weight gradient's activation operand and up_p16's source (their
 // last readers) moved the step by nothing (10.79 - 10.86 against 10.81 - 10.90 ms): removed.
-#ifndef LG_NORM_NT
-#define LG_NORM_NT 5
-#endif
-// The bf16 apply / backward-apply passes walk their maps from the END (bits: 1 apply16p, 2 bwd_apply16; 4 / 8 their fp32 twins).  Their producers (the conv
+// (variants there: 0 none, 1 backward-apply loads, 5 + apply loads, 3 / 7 + the stores)
+constexpr bool NT_LOAD = true;
+// The bf16 apply / backward-apply passes (apply16p, bwd_apply16; not their fp32 twins) walk their maps from the END.  Their producers (the conv
 // kernels) write a map front to back and their consumers read it front to back: a pass in between that starts at the END meets what the
 // producer wrote last — still in the Infinity Cache when the map is larger than it — and leaves the START of its own output for the
 // consumer's first reads.  Round 4, whole step, one box, three rounds: 10.79 / 10.76 / 10.72 ms (0) against 10.75 / 10.66 / 10.64 (3),
 // captured 10.70 against 10.66; results unchanged except the bias column sums of a multi-trip backward pass (trip order).
-#ifndef LG_NORM_REV
-#define LG_NORM_REV 3
-#endif
 template <bool NT, typename V>
 __device__ __forceinline__ V lg_ld(const V* q) { if constexpr (NT) return __builtin_nontemporal_load(q); else return *q; }
 
@@ -130,10 +126,10 @@ __global__ __launch_bounds__(256) void apply_kernel(const float* __restrict__ x,
   // EW_UNR independent 16-B loads per thread per trip: a single load in flight per thread leaves the pass latency-bound
   // (measured 2.5-3.9 TB/s against 5.5+ for a streaming copy)
   const unsigned stride = gridDim.x * blockDim.x * EW_UNR, tot = (unsigned)total4, l4 = (unsigned)L4;
-  const unsigned rb = (LG_NORM_REV & 4) ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
+  const unsigned rb = blockIdx.x;
   const int ntrip = (int)(((unsigned long long)tot + stride - 1) / stride);
-  for (int tr = 0; tr < ntrip; ++tr) {  // block-contiguous 16-KB trips (LG_NORM_REV & 4: from the end of the map)
-    const unsigned long long i0l = (unsigned long long)((LG_NORM_REV & 4) ? ntrip - 1 - tr : tr) * stride + rb * blockDim.x * EW_UNR + threadIdx.x;
+  for (int tr = 0; tr < ntrip; ++tr) {  // block-contiguous 16-KB trips
+    const unsigned long long i0l = (unsigned long long)tr * stride + rb * blockDim.x * EW_UNR + threadIdx.x;
     if (i0l >= tot) continue;
     const unsigned i0 = (unsigned)i0l;
     f32x4 v[EW_UNR], sk[EW_UNR];
@@ -141,8 +137,8 @@ __global__ __launch_bounds__(256) void apply_kernel(const float* __restrict__ x,
     for (int u = 0; u < EW_UNR; ++u) {
       const unsigned i = i0 + u * 256;
       if (i < tot) {
-        v[u] = lg_ld<(LG_NORM_NT & 4) != 0>(reinterpret_cast<const f32x4*>(x + (long long)i * 4));
-        if (skip) sk[u] = lg_ld<(LG_NORM_NT & 4) != 0>(reinterpret_cast<const f32x4*>(skip + (long long)i * 4));
+        v[u] = lg_ld<NT_LOAD>(reinterpret_cast<const f32x4*>(x + (long long)i * 4));
+        if (skip) sk[u] = lg_ld<NT_LOAD>(reinterpret_cast<const f32x4*>(skip + (long long)i * 4));
       }
     }
 #pragma unroll
@@ -296,10 +292,10 @@ __global__ __launch_bounds__(256) void bwd_apply_kernel(const float* __restrict_
   constexpr int UNR = DB ? 1 : EW_UNR;  // DB: a thread must stay on one channel quad -> plain grid stride
   const unsigned stride = gridDim.x * blockDim.x * UNR, tot = (unsigned)total4, l4 = (unsigned)L4;
   f32x4 csum = {0.f, 0.f, 0.f, 0.f};
-  const unsigned rb = (LG_NORM_REV & 8) ? gridDim.x - 1 - blockIdx.x : blockIdx.x;   // (data and column-sum row alike)
+  const unsigned rb = blockIdx.x;
   const int ntrip = (int)(((unsigned long long)tot + stride - 1) / stride);
   for (int tr = 0; tr < ntrip; ++tr) {
-   const unsigned long long i0l = (unsigned long long)((LG_NORM_REV & 8) ? ntrip - 1 - tr : tr) * stride + rb * blockDim.x * UNR + threadIdx.x;
+   const unsigned long long i0l = (unsigned long long)tr * stride + rb * blockDim.x * UNR + threadIdx.x;
    if (i0l >= tot) continue;
    const unsigned i0 = (unsigned)i0l;
    f32x4 xs[UNR], gs[UNR];
@@ -307,8 +303,8 @@ __global__ __launch_bounds__(256) void bwd_apply_kernel(const float* __restrict_
    for (int u = 0; u < UNR; ++u) {
      const unsigned i = i0 + u * 256;
      if (i < tot) {
-       xs[u] = lg_ld<(LG_NORM_NT & 1) != 0>(reinterpret_cast<const f32x4*>(x + (long long)i * 4));   // last reader of z and g
-       gs[u] = load_g4<(LG_NORM_NT & 1) != 0>(g, (long long)i * 4, g16);
+       xs[u] = lg_ld<NT_LOAD>(reinterpret_cast<const f32x4*>(x + (long long)i * 4));   // last reader of z and g
+       gs[u] = load_g4<NT_LOAD>(g, (long long)i * 4, g16);
      }
    }
 #pragma unroll
@@ -379,26 +375,20 @@ __device__ __forceinline__ f32x8 load8(const void* p, long long i8) {  // elemen
   }
   return r;
 }
-template <bool NT = false>
 __device__ __forceinline__ void store8_bf16(__bf16* p, long long i8, const f32x8& v) {
   bf16x8v w;
   w[0] = (__bf16)v.lo[0]; w[1] = (__bf16)v.lo[1]; w[2] = (__bf16)v.lo[2]; w[3] = (__bf16)v.lo[3];
   w[4] = (__bf16)v.hi[0]; w[5] = (__bf16)v.hi[1]; w[6] = (__bf16)v.hi[2]; w[7] = (__bf16)v.hi[3];
-  if constexpr (NT) __builtin_nontemporal_store(w, reinterpret_cast<bf16x8v*>(p + i8 * 8));
-  else *reinterpret_cast<bf16x8v*>(p + i8 * 8) = w;
+  *reinterpret_cast<bf16x8v*>(p + i8 * 8) = w;
 }
 __device__ __forceinline__ void store8_f32(float* p, long long i8, const f32x8& v) {
   *reinterpret_cast<f32x4*>(p + i8 * 8) = v.lo;
   *reinterpret_cast<f32x4*>(p + i8 * 8 + 4) = v.hi;
 }
 
-#ifndef LG_EW8_UNR
-#define LG_EW8_UNR 2   // r3 sweep (same box, B=256 maps): 2 beats 4 and 8 by 3 - 8 % on apply, apply + skip and the backward apply (more waves resident)
-#endif
-#ifndef LG_DB_UNR
-#define LG_DB_UNR 2
-#endif
-constexpr int EW8_UNR = LG_EW8_UNR;  // 16-B accesses in flight per thread and stream
+// 16-B accesses in flight per thread and stream.  r3 sweep (same box, B=256 maps): 2 beats 4 and 8 by 3 - 8 % on apply, apply + skip and the
+// backward apply (more waves resident)
+constexpr int EW8_UNR = 2, DB_UNR = 2;
 
 // y = leaky(a*((z - mu_hi) - mu_lo) + beta) [+ skip]  from the bf16 z;  SK: 0 none, 1 fp32 skip, 2 bf16 skip
 template <int SK>
@@ -450,9 +440,9 @@ __global__ __launch_bounds__(256) void apply16p_kernel(const __bf16* __restrict_
                                                        float* __restrict__ y, __bf16* __restrict__ y16, unsigned L8,
                                                        int post_leaky, float alpha) {
   __shared__ float sst[8];
-  // (LG_NORM_REV & 1: samples and chunks from the end — the producer wrote the end of the map last, the consumer reads its start first)
-  const int n = (LG_NORM_REV & 1) ? (int)(gridDim.y - 1 - blockIdx.y) : (int)blockIdx.y;
-  const unsigned bx = (LG_NORM_REV & 1) ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
+  // samples and chunks from the END — the producer wrote the end of the map last, the consumer reads its start first
+  const int n = (int)(gridDim.y - 1 - blockIdx.y);
+  const unsigned bx = gridDim.x - 1 - blockIdx.x;
   if (threadIdx.x < 64) {
     const int lane = threadIdx.x;
     const double* p = partial + (long long)n * nchunk * 3;
@@ -484,16 +474,16 @@ __global__ __launch_bounds__(256) void apply16p_kernel(const __bf16* __restrict_
   const unsigned stride = gridDim.x * blockDim.x * EW8_UNR;
   const int ntrip = (int)((L8 + stride - 1) / stride);
   for (int tr = 0; tr < ntrip; ++tr) {
-    const unsigned i0 = (unsigned)((LG_NORM_REV & 1) ? ntrip - 1 - tr : tr) * stride + bx * blockDim.x * EW8_UNR + threadIdx.x;
+    const unsigned i0 = (unsigned)(ntrip - 1 - tr) * stride + bx * blockDim.x * EW8_UNR + threadIdx.x;
     if (i0 >= L8) continue;
     f32x8 v[EW8_UNR], sk[EW8_UNR];
 #pragma unroll
     for (int u = 0; u < EW8_UNR; ++u) {
       const unsigned i = i0 + u * 256;
       if (i < L8) {
-        v[u] = load8<true, (LG_NORM_NT & 4) != 0>(x, base + i);
-        if constexpr (SK == 1) sk[u] = load8<false, (LG_NORM_NT & 4) != 0>(skip, base + i);
-        if constexpr (SK == 2) sk[u] = load8<true, (LG_NORM_NT & 4) != 0>(skip, base + i);
+        v[u] = load8<true, NT_LOAD>(x, base + i);
+        if constexpr (SK == 1) sk[u] = load8<false, NT_LOAD>(skip, base + i);
+        if constexpr (SK == 2) sk[u] = load8<true, NT_LOAD>(skip, base + i);
       }
     }
 #pragma unroll
@@ -509,7 +499,7 @@ __global__ __launch_bounds__(256) void apply16p_kernel(const __bf16* __restrict_
         if (k < 4) v[u].lo[k & 3] = t; else v[u].hi[k & 3] = t;
       }
       if (y) store8_f32(y, base + i, v[u]);
-      if (y16) store8_bf16<(LG_NORM_NT & 8) != 0>(y16, base + i, v[u]);
+      if (y16) store8_bf16(y16, base + i, v[u]);
     }
   }
 }
@@ -571,24 +561,24 @@ __global__ __launch_bounds__(256) void bwd_apply16_kernel(const __bf16* __restri
                                                           float* __restrict__ dx, __bf16* __restrict__ dx16, long long L8,
                                                           long long total8, int pre_leaky, int post_leaky, float alpha,
                                                           float* __restrict__ colpart, int C8) {
-  constexpr int UNR = DB ? LG_DB_UNR : EW8_UNR;  // DB: the extra loads of a trip sit gridDim.x*256 units apart (same channel octet)
+  constexpr int UNR = DB ? DB_UNR : EW8_UNR;  // DB: the extra loads of a trip sit gridDim.x*256 units apart (same channel octet)
   const unsigned tot = (unsigned)total8, l8 = (unsigned)L8;
   const unsigned ustep = DB ? gridDim.x * blockDim.x : 256u;                  // distance between a thread's units of one trip
   const unsigned stride = DB ? gridDim.x * blockDim.x * UNR : gridDim.x * blockDim.x * UNR;
-  const unsigned rb = (LG_NORM_REV & 2) ? gridDim.x - 1 - blockIdx.x : blockIdx.x;   // (the block's data AND its column-sum row: results unchanged)
+  const unsigned rb = gridDim.x - 1 - blockIdx.x;   // from the END of the map (the block's data AND its column-sum row: results unchanged)
   const unsigned first = DB ? rb * blockDim.x + threadIdx.x : rb * blockDim.x * UNR + threadIdx.x;
   f32x8 csum;
   csum.lo = f32x4{0.f, 0.f, 0.f, 0.f}; csum.hi = f32x4{0.f, 0.f, 0.f, 0.f};
   const int ntrip = (int)(((unsigned long long)tot + stride - 1) / stride);
   for (int tr = 0; tr < ntrip; ++tr) {
-    const unsigned long long i0l = (unsigned long long)((LG_NORM_REV & 2) ? ntrip - 1 - tr : tr) * stride + first;
+    const unsigned long long i0l = (unsigned long long)(ntrip - 1 - tr) * stride + first;
     if (i0l >= tot) continue;
     const unsigned i0 = (unsigned)i0l;
     f32x8 xs[UNR], gs[UNR];
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
       const unsigned i = i0 + u * ustep;
-      if (i < tot) { xs[u] = load8<true, (LG_NORM_NT & 1) != 0>(x, i); gs[u] = load8<G16, (LG_NORM_NT & 1) != 0>(g, i); }
+      if (i < tot) { xs[u] = load8<true, NT_LOAD>(x, i); gs[u] = load8<G16, NT_LOAD>(g, i); }
     }
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
@@ -612,7 +602,7 @@ __global__ __launch_bounds__(256) void bwd_apply16_kernel(const __bf16* __restri
         if (k < 4) o.lo[k & 3] = d; else o.hi[k & 3] = d;
       }
       if (dx) store8_f32(dx, i, o);
-      if (dx16) store8_bf16<(LG_NORM_NT & 2) != 0>(dx16, i, o);
+      if (dx16) store8_bf16(dx16, i, o);
       if constexpr (DB) { csum.lo += o.lo; csum.hi += o.hi; }
     }
   }
@@ -658,24 +648,14 @@ __global__ __launch_bounds__(1024) void colsum_final_kernel(const float* __restr
   }
 }
 
-// Grid caps of the element-wise passes (blocks of 256 threads walking the map in trips).  LG_NORM_MAXBLK / LG_NORM_MAXBLK_DB: A/B of the cap
-// (round 5, scripts/probe/norm_maxblk.sh): fewer, longer-lived blocks against many short ones.
-inline long long ew_cap() {
-  static long long v = 0;
-  if (!v) { const char* e = getenv("LG_NORM_MAXBLK"); v = e && atoi(e) >= 64 ? atoi(e) : 8192; if (v > 8192) v = 8192; }
-  return v;
-}
-inline long long db_cap(long long hard) {
-  static long long v = 0;
-  if (!v) { const char* e = getenv("LG_NORM_MAXBLK_DB"); v = e && atoi(e) >= 64 ? atoi(e) : hard; if (v > hard) v = hard; }
-  return v;
-}
+// Grid cap of the element-wise passes (blocks of 256 threads walking the map in trips); the bias-sum forms are capped by DB_MAX_BLOCKS.
+// (Fewer, longer-lived blocks against many short ones: swept in round 5, the whole-rounds rule below is what came of it.)
+constexpr long long EW_MAX_BLOCKS = 8192;
 // WHOLE ROUNDS (round 5).  These grids are larger than what the chip holds at once (blocks of 256 threads, 4 .. 8 per CU by their
 // VGPRs), so they run in rounds — and a last partial round costs a whole trip time for a fraction of the work: the bias-sum form of
 // the backward apply (71 VGPRs: 7 blocks per CU = 1792 resident) was launched as 2046 blocks = one round + 254 blocks, 14 % of a
-// round at the price of one (`scripts/probe/norm_maxblk.sh`: 1533 = six per CU beat both 2046 and 1023; C3 step -0.9 %).  A grid
+// round at the price of one (1533 = six per CU beat both 2046 and 1023; C3 step -0.9 %).  A grid
 // beyond one round is cut to a whole number of rounds of the kernel's own residency (occupancy query, once per kernel).
-// LG_NO_NORM_ROUNDS=1 = the caps alone, as before.
 extern "C" int lg_device_cus(void);
 #define LG_RESIDENT_BLOCKS(kern)                                                                                       \
   ([]() -> long long {                                                                                                 \
@@ -688,17 +668,15 @@ extern "C" int lg_device_cus(void);
     return r;                                                                                                          \
   }())
 inline long long fit_rounds(long long nb, long long resident, long long hard, int unit) {
-  static int off = -1;
-  if (off < 0) off = lg_env_flag("LG_NO_NORM_ROUNDS") ? 1 : 0;
   if (nb > hard) nb = hard;
-  if (!off && nb > resident) nb = nb / resident * resident;
+  if (nb > resident) nb = nb / resident * resident;
   nb = nb / unit * unit;
   return nb < unit ? unit : nb;
 }
 inline int nchunks(long long L) { return (int)((L + CHUNK - 1) / CHUNK); }
 inline int ew_blocks(long long total4) {
   long long b = (total4 + 256 * EW_UNR - 1) / (256 * EW_UNR);
-  return (int)(b < ew_cap() ? (b > 0 ? b : 1) : ew_cap());
+  return (int)(b < EW_MAX_BLOCKS ? (b > 0 ? b : 1) : EW_MAX_BLOCKS);
 }
 inline size_t part_bytes(int B, long long L) { return ((size_t)B * nchunks(L) * 3 * sizeof(double) + 255) / 256 * 256; }
 inline size_t bst_bytes(int B) { return ((size_t)B * 4 * sizeof(float) + 255) / 256 * 256; }
@@ -755,7 +733,7 @@ extern "C" int lg_instnorm_leaky_apply(const float* x, const float* stats, const
   LG_CHECK_ARG(x && stats && (y || y16), "lg_instnorm_leaky_apply: null pointer");
   LG_CHECK_ARG(B > 0 && L > 0 && L % 4 == 0 && (long long)B * L / 4 < (1LL << 31), "lg_instnorm_leaky_apply: bad shape B=%d L=%lld", B, L);
   const long long total4 = (long long)B * L / 4;
-  hipLaunchKernelGGL(apply_kernel, dim3((int)fit_rounds(ew_blocks(total4), LG_RESIDENT_BLOCKS(apply_kernel), ew_cap(), 1)), dim3(256), 0, (hipStream_t)stream, x, stats, skip, y,
+  hipLaunchKernelGGL(apply_kernel, dim3((int)fit_rounds(ew_blocks(total4), LG_RESIDENT_BLOCKS(apply_kernel), EW_MAX_BLOCKS, 1)), dim3(256), 0, (hipStream_t)stream, x, stats, skip, y,
                      (__bf16*)y16, L / 4, total4, pre_leaky, post_leaky, alpha);
   LG_CHECK_LAUNCH("lg_instnorm_leaky_apply");
   return LG_OK;
@@ -814,13 +792,13 @@ extern "C" int lg_instnorm_leaky_bwd_db(const float* x, const float* stats, cons
   }
   const long long total4 = (long long)B * L / 4;
   if (!db) {
-    hipLaunchKernelGGL(bwd_apply_kernel<false>, dim3((int)fit_rounds(ew_blocks(total4), LG_RESIDENT_BLOCKS(bwd_apply_kernel<false>), ew_cap(), 1)), dim3(256), 0, st, x, g, g_is_bf16, stats,
+    hipLaunchKernelGGL(bwd_apply_kernel<false>, dim3((int)fit_rounds(ew_blocks(total4), LG_RESIDENT_BLOCKS(bwd_apply_kernel<false>), EW_MAX_BLOCKS, 1)), dim3(256), 0, st, x, g, g_is_bf16, stats,
                        (const float*)bstats, dx, (__bf16*)dx16, L / 4, total4, pre_leaky, post_leaky, alpha, nullptr, 0);
     LG_CHECK_LAUNCH("lg_instnorm_leaky_bwd(apply)");
     return LG_OK;
   }
   const int C4 = C / 4, unit = 256 % C4 == 0 ? 1 : 3;  // blocks per period of the thread -> channel map
-  long long nb = fit_rounds((total4 + 255) / 256, LG_RESIDENT_BLOCKS(bwd_apply_kernel<true>), db_cap(DB_MAX_BLOCKS), unit);
+  long long nb = fit_rounds((total4 + 255) / 256, LG_RESIDENT_BLOCKS(bwd_apply_kernel<true>), DB_MAX_BLOCKS, unit);
   float* colpart = (float*)(ws + lg_instnorm_workspace_bytes(B, L));
   hipLaunchKernelGGL(bwd_apply_kernel<true>, dim3((int)nb), dim3(256), 0, st, x, g, g_is_bf16, stats, (const float*)bstats, dx,
                      (__bf16*)dx16, L / 4, total4, pre_leaky, post_leaky, alpha, colpart, C4);
@@ -841,7 +819,7 @@ extern "C" int lg_instnorm_leaky_apply_z16(const void* z16, const float* stats, 
                "lg_instnorm_leaky_apply_z16: bad shape B=%d L=%lld", B, L);
   const long long total8 = (long long)B * L / 8;
   long long nb = (total8 + 256 * EW8_UNR - 1) / (256 * EW8_UNR);
-  nb = fit_rounds(nb, !skip ? LG_RESIDENT_BLOCKS(apply16_kernel<0>) : !skip_is_bf16 ? LG_RESIDENT_BLOCKS(apply16_kernel<1>) : LG_RESIDENT_BLOCKS(apply16_kernel<2>), ew_cap(), 1);
+  nb = fit_rounds(nb, !skip ? LG_RESIDENT_BLOCKS(apply16_kernel<0>) : !skip_is_bf16 ? LG_RESIDENT_BLOCKS(apply16_kernel<1>) : LG_RESIDENT_BLOCKS(apply16_kernel<2>), EW_MAX_BLOCKS, 1);
   hipStream_t st = (hipStream_t)stream;
   const __bf16* x = (const __bf16*)z16;
   if (!skip)
@@ -867,7 +845,7 @@ extern "C" int lg_instnorm_leaky_apply_z16_p(const void* z16, const void* partia
                "lg_instnorm_leaky_apply_z16_p: bad shape B=%d L=%lld nparts=%d", B, L, nparts);
   const long long L8 = L / 8;
   long long bps = (L8 + 256 * EW8_UNR * 4 - 1) / (256 * EW8_UNR * 4);   // ~4 trips per block: the merge is paid once per 32 KB of z
-  if (bps * B > ew_cap()) bps = ew_cap() / B;
+  if (bps * B > EW_MAX_BLOCKS) bps = EW_MAX_BLOCKS / B;
   if (bps < 1) bps = 1;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)bps, (unsigned)B);
@@ -945,7 +923,7 @@ extern "C" int lg_instnorm_leaky_bwd_z16_p(const void* z16, const float* stats, 
   const long long total8 = (long long)B * L / 8;
   if (!db) {
     long long nb = (total8 + 256 * EW8_UNR - 1) / (256 * EW8_UNR);
-    nb = fit_rounds(nb, g_is_bf16 ? LG_RESIDENT_BLOCKS((bwd_apply16_kernel<false, true>)) : LG_RESIDENT_BLOCKS((bwd_apply16_kernel<false, false>)), ew_cap(), 1);
+    nb = fit_rounds(nb, g_is_bf16 ? LG_RESIDENT_BLOCKS((bwd_apply16_kernel<false, true>)) : LG_RESIDENT_BLOCKS((bwd_apply16_kernel<false, false>)), EW_MAX_BLOCKS, 1);
     if (g_is_bf16)
       hipLaunchKernelGGL((bwd_apply16_kernel<false, true>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
                          (__bf16*)dx16, L / 8, total8, pre_leaky, post_leaky, alpha, (float*)nullptr, 0);
@@ -957,7 +935,7 @@ extern "C" int lg_instnorm_leaky_bwd_z16_p(const void* z16, const float* stats, 
   }
   const int C8 = C / 8, unit = 256 % C8 == 0 ? 1 : 3;
   long long nb = (total8 + 511) / 512;   // two units per thread per trip
-  nb = fit_rounds(nb, g_is_bf16 ? LG_RESIDENT_BLOCKS((bwd_apply16_kernel<true, true>)) : LG_RESIDENT_BLOCKS((bwd_apply16_kernel<true, false>)), db_cap(DB_MAX_BLOCKS), unit);
+  nb = fit_rounds(nb, g_is_bf16 ? LG_RESIDENT_BLOCKS((bwd_apply16_kernel<true, true>)) : LG_RESIDENT_BLOCKS((bwd_apply16_kernel<true, false>)), DB_MAX_BLOCKS, unit);
   float* colpart = (float*)(ws + lg_instnorm_workspace_bytes(B, L));   // [nb][C] floats, nb <= DB_MAX_BLOCKS (+2)
   if (g_is_bf16)
     hipLaunchKernelGGL((bwd_apply16_kernel<true, true>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,

@@ -37,11 +37,11 @@ extern "C" int lg_set_reserved_cus(int n) {
 
 extern "C" int lg_grid_cus(void) { return device_cus() - g_reserved_cus; }
 
-// One switch table for the whole library: every A/B environment switch is read ONCE, at its first use, through this
-// function, so a *_supported query and the launch it promises can never see two different values.
+// One switch table for the whole library: every kill switch (the keep list) is read ONCE, at its first use, through this
+// function — the only getenv of the library — and each name has exactly one call site.
 extern "C" int lg_env_flag(const char* name) {
   struct Slot { const char* name; int val; };
-  static Slot slots[64];
+  static Slot slots[16];
   static int n = 0;
   static std::mutex mu;
   std::lock_guard<std::mutex> lock(mu);
@@ -49,8 +49,8 @@ extern "C" int lg_env_flag(const char* name) {
     if (slots[i].name == name || strcmp(slots[i].name, name) == 0) return slots[i].val;
   const char* e = getenv(name);
   const int v = (e && *e) ? 1 : 0;   // set AND non-empty (round 4; `LG_NO_X=` no longer switches anything)
-  if (n >= 64) {   // a full table would silently re-read the environment on every call: the "read once" promise would be gone
-    fprintf(stderr, "littlegan_hip: lg_env_flag table full (64 switches) at %s — enlarge it\n", name);
+  if (n >= 16) {   // a full table would silently re-read the environment on every call: the "read once" promise would be gone
+    fprintf(stderr, "littlegan_hip: lg_env_flag table full (16 switches) at %s — enlarge it\n", name);
     abort();
   }
   slots[n].name = name; slots[n].val = v; ++n;

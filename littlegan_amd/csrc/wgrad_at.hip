@@ -13,12 +13,8 @@
 //     A fragment read once, used twice); tap 24 rotates — wave w runs it on k step w of every item and the 8 partial
 //     tiles are summed through LDS at the end — so every wave issues exactly 50 MFMAs per item.
 //   * output: slab[split][tap][cb][cs] (fp32), reduced in fixed order by slab_reduce4_kernel (deterministic, no atomics).
-#include <stdlib.h>
 #include "lg_common.h"
 
-#ifndef LG_WGAT_SCHED
-#define LG_WGAT_SCHED 0   // 0: k step in pinned groups (sched_barrier); 1: interleaved by sched_group_barrier (MFMA, two LDS reads, ...)
-#endif
 #ifndef LG_WGAT_DBG
 #define LG_WGAT_DBG 0   // timing ablations (results wrong): 1 no MFMA, 2 no fragment reads in the k loop, 4 no staging after the first item
 #endif
@@ -32,7 +28,6 @@ struct WgAtParams {
   int B, Hm, Wm, Cb, Cs;
   int nuj, nunits;      // units = (Cb/32) x (Cs/64)
   int items_total, items_per;
-  int nsplit, interleave;   // interleave (round 5, LG_WGAT_INTERLEAVE): split s walks items s, s + nsplit, ... — the chip sweeps the maps front to back together
 };
 
 // SW == 8 is the 8x8-map configuration: an item is a PAIR of samples (2 x 64 small pixels = 8 k steps), each with its own
@@ -77,9 +72,9 @@ __global__ __launch_bounds__(512) void wgrad_at_kernel(const WgAtParams p) {
   const int bx = lg_xcd_remap(blockIdx.x, gridDim.x);
   const int unit = bx % p.nunits, split = bx / p.nunits;   // units of one split run together: they share the pixels
   const int i0 = (unit / p.nuj) * 32, j0 = (unit % p.nuj) * 64;
-  const int it0 = p.interleave ? 0 : split * p.items_per;
-  const int it1 = p.interleave ? (p.items_total - split + p.nsplit - 1) / p.nsplit : min(it0 + p.items_per, p.items_total);   // local item indices it0 .. it1 - 1
-  auto item_of = [&](int j) { return p.interleave ? split + j * p.nsplit : j; };
+  // a split owns a contiguous run of items (interleaved splits — s, s + nsplit, ...: the chip sweeping the maps front to back together — measured
+  // in round 5, not adopted)
+  const int it0 = split * p.items_per, it1 = min(it0 + p.items_per, p.items_total);   // items it0 .. it1 - 1
   const int nxs = p.Wm / SW, nyb = p.Hm / R;
   const int Hb = 2 * p.Hm, Wb = 2 * p.Wm;
 
@@ -160,13 +155,13 @@ __global__ __launch_bounds__(512) void wgrad_at_kernel(const WgAtParams p) {
   }
 
   if (it0 < it1) {
-    load_item(item_of(it0));
+    load_item(it0);
     store_item(smem);
   }
   __syncthreads();
   for (int it = it0; it < it1; ++it) {
     const int cur = (it - it0) & 1;
-    if (it + 1 < it1 && !(LG_WGAT_DBG & 4)) load_item(item_of(it + 1));
+    if (it + 1 < it1 && !(LG_WGAT_DBG & 4)) load_item(it + 1);
     const char* sb = smem + cur * C::BUF;
     // k-step offsets of the two operands (compile-time once the loop is unrolled).  PAIR: k step ks = rows 2(ks&3),
     // 2(ks&3)+1 of sample ks >> 2; otherwise the 16 pixels of chunk xc of row yy.
@@ -180,40 +175,31 @@ __global__ __launch_bounds__(512) void wgrad_at_kernel(const WgAtParams p) {
     };
     // Order PINNED (sched_barrier; left alone hipcc puts every fragment read right in front of its MFMA and waits for it):
     // a step starts with a0, b0, b1 already in registers (requested during the previous step), requests a1, a2, runs the
-    // two MFMAs of a0 under that latency, requests the next step's a0, b0, b1, then runs the other four.
+    // two MFMAs of a0 under that latency, requests the next step's a0, b0, b1, then runs the other four.  (The reads dealt two by two into
+    // the MFMAs' shadows by sched_group_barrier, as in conv_down3.hip: measured, not adopted.)
     bf16x8 b[2], a0;
 #pragma unroll
     for (int h = 0; h < 2; ++h) b[h] = rd_tr(sb + bb + koffB(0, h));
     a0 = rd_tr(sb + ab[0] + koffA(0));
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
-      if constexpr (LG_WGAT_SCHED == 0) __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_sched_barrier(0);
       const bf16x8 a1 = (LG_WGAT_DBG & 2) ? a0 : rd_tr(sb + ab[1] + koffA(ks)), a2 = (LG_WGAT_DBG & 2) ? a0 : rd_tr(sb + ab[2] + koffA(ks));
-      if constexpr (LG_WGAT_SCHED == 0) __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_sched_barrier(0);
       acc[0][0] = at_mfma(a0, b[0], acc[0][0]);
       acc[0][1] = at_mfma(a0, b[1], acc[0][1]);
-      if constexpr (LG_WGAT_SCHED == 0) __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_sched_barrier(0);
       bf16x8 bn[2] = {b[0], b[1]}, a0n = a0;
       if (ks + 1 < 8 && !(LG_WGAT_DBG & 2)) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) bn[h] = rd_tr(sb + bb + koffB(ks + 1, h));
         a0n = rd_tr(sb + ab[0] + koffA(ks + 1));
       }
-      if constexpr (LG_WGAT_SCHED == 0) __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_sched_barrier(0);
       acc[1][0] = at_mfma(a1, b[0], acc[1][0]);
       acc[1][1] = at_mfma(a1, b[1], acc[1][1]);
       acc[2][0] = at_mfma(a2, b[0], acc[2][0]);
       acc[2][1] = at_mfma(a2, b[1], acc[2][1]);
-      if constexpr (LG_WGAT_SCHED != 0 && (LG_WGAT_DBG & 3) == 0) {
-        // the ten transposed reads of the step (a1, a2; then b0', b1', a0' of the next one) go two by two into the shadows of
-        // the MFMAs: an MFMA holds the vector issue port for 8 of its 32 cycles
-#pragma unroll
-        for (int m = 0; m < 5; ++m) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
-          __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);   // 2 DS reads
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      }
       if (wid == ks) {
         const bf16x8 a3 = rd_tr(sb + a24 + koffA(ks));
 #pragma unroll
@@ -306,8 +292,6 @@ extern "C" int lg_wgrad_at_try(const void* big16, const void* small16, void* wor
   p.nuj = cs / 64; p.nunits = (cb / 32) * (cs / 64);
   int ns;
   at_plan(B, Hm, Wm, cb, cs, sw, &ns, &p.items_total, &p.items_per);
-  p.nsplit = ns;
-  { static int il = -1; if (il < 0) il = lg_env_flag("LG_WGAT_INTERLEAVE") ? 1 : 0; p.interleave = il; }
   LG_CHECK_ARG(ws_bytes >= (size_t)ns * 25 * cb * cs * sizeof(float), "lg_wgrad_at: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   static bool attr = false;

@@ -23,12 +23,6 @@ from . import ops
 from ._lib import DT_BF16, DT_F32
 
 
-import os as _os
-_ZN = not _os.environ.get("LG_NO_ZN")   # A/B switch: apply passes left to the consuming conv where no one else reads the map
-_BN = not _os.environ.get("LG_NO_BWDNORM")   # A/B switch: norm-backward apply left to the consuming data-gradient conv (no-weight-gradient levels)
-_DEFER = not _os.environ.get("LG_NO_DEFER")   # A/B switch: moments finished by the apply launch (default) or by their own kernel
-
-
 def _dtype_of(args) -> int:
     name = getattr(args, "mfma_dtype", "f32")
     if name not in ("f32", "bf16"):
@@ -150,13 +144,13 @@ class Encoder(_ConvStack):
             gm, bt = self._w[f"norm{i}.gamma"], self._w[f"norm{i}.beta"]
             # does the NEXT conv normalise this level's output itself?
             Bn, Hn, Wn = (x if x is not None else x16 if x16 is not None else raw[0]).shape[:3]
-            skip_apply = (top_only and _ZN and i < 4 and
+            skip_apply = (top_only and i < 4 and
                           ops.conv2d_s2_fwd_stats_zn_supported(Bn, Hn // 2, Wn // 2, cs, self.chans[i][1], self.dtype))
             if raw is not None:
                 z, st = ops.conv2d_s2_fwd_stats_zn(raw[0], raw[1], a, packs[i - 1], self._w[f"conv{i}.bias"], cs, self.dtype, gm, bt)
             else:
                 z, st = ops.conv2d_s2_fwd_stats(x, packs[i - 1], self._w[f"conv{i}.bias"], cs, self.dtype, gm, bt, x16=x16,
-                                                z16=m16, alpha=a, defer_stats=m16 and _DEFER and not skip_apply)
+                                                z16=m16, alpha=a, defer_stats=m16 and not skip_apply)
             if st is None:  # kernel without the fused-moments epilogue (small maps, 3-channel input)
                 st = ops.instnorm_stats(z, gm, bt, 0, a)
             if skip_apply:
@@ -339,7 +333,7 @@ class Decoder(_ConvStack):
         for i, (cb, cs) in enumerate(self.chans, 1):
             gm, bt = self._w[f"norm{i}.gamma"], self._w[f"norm{i}.beta"]
             z, st = ops.convT_s2_fwd_stats(x, packs[i - 1], self._w[f"conv{i}.bias"], cb, self.dtype, gm, bt, x16=x16,
-                                           z16=m16, alpha=a, defer_stats=m16 and _DEFER)
+                                           z16=m16, alpha=a, defer_stats=m16)
             if st is None:
                 st = ops.instnorm_stats(z, gm, bt, 0, a)
             skip = add[i] if i < 4 else None
@@ -395,7 +389,7 @@ class Decoder(_ConvStack):
             # reader of its dz: the data-gradient conv below.  Where that kernel can take the norm backward through its operand
             # staging (ops.convT_s2_dgrad_bn: dz = a (g' - m1 - c m2') formed from (z, g) per halo piece), the apply pass and the
             # dz tensor are left out; only the per-sample coefficients are finished from the producer-fused sums.
-            if (_BN and not need_wgrad and want_dx and i > 1 and i - 1 >= lowest and nfp is not None and self.dtype == DT_BF16
+            if (not need_wgrad and want_dx and i > 1 and i - 1 >= lowest and nfp is not None and self.dtype == DT_BF16
                     and z.dtype == torch.bfloat16 and g_h.dtype == torch.bfloat16
                     and ops.convT_s2_dgrad_bn_supported(z.shape[0], z.shape[1] // 2, z.shape[2] // 2, cb, cs, self.dtype)):
                 coef = ops.instnorm_bwd_coef(z, st, nfp)

@@ -1,5 +1,5 @@
 """Micro-benchmark (GPU) of single conv layers at the C3 shapes (B=256, 128x128), HIP-event timed.
-   LG_DBG=<bits> enables the ablation switches of conv_halo.hip (results are then wrong, timing only)."""
+   A kill switch of DESIGN 4 (LG_NO_DOWN3=1, LG_NO_UP4=1, ...) times the kernel a specialised one replaced; the kernel's name is printed."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -82,4 +82,4 @@ for name, kind, Hs, cb, cs in LAYERS:
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / n
     fl = 50.0 * B * Hs * Hs * cb * cs
-    print(f"{name:26s} {ms*1e3:9.1f} us  {fl/ms/1e9:8.1f} TFLOP/s", flush=True)
+    print(f"{name:26s} {ms*1e3:9.1f} us  {fl/ms/1e9:8.1f} TFLOP/s  ({ops.last_kernel()})", flush=True)

@@ -56,7 +56,9 @@ def short(name):
         return f"conv_down3_kernel<NW={t(3, '128')}{norm}>"
     if base == "conv_up3_kernel":        # <CS, N, STATS, FUSE, NTT = tiles per step>; (64, 32) with one tile per step = the 4-wave form
         return f"conv_up3_kernel<{t(0)},{t(1)}" + (",4w>" if (t(1) == "32" and t(4, "2") == "1") else ">")
-    if base == "conv_halo_kernel":       # <T, MODE, KCH, DBUF, SRC16, RES, ...>
+    if base == "conv_halo_kernel":       # <T, MODE, KCH, SRC16, RES, WAVES_M, WAVES_N, MT, NT, W3> (traces of older builds: DBUF behind KCH)
+        if len(a) == 11:
+            a = a[:3] + a[4:]
         ty = "bf16" if t(0) == "__bf16" else "f32"
         mode = t(1)
         if mode == "?":                  # K-sliced UP tiles are the KCH = 4 builds, DOWN tiles KCH = 2 (conv_halo.hip: halo_w3_ok)
@@ -64,7 +66,7 @@ def short(name):
         if mode == "0":
             return f"conv_halo_kernel<{ty},DOWN>"
         if mode == "1":
-            if t(5) == "true":
+            if t(4) == "true":
                 return "conv_halo_kernel<UP,resident>" if ty == "bf16" else "conv_halo_kernel<f32,UP,resident>"
             return f"conv_halo_kernel<{ty},UP,K-sliced>"
         return "conv_halo_kernel<S1T>"

@@ -1,5 +1,5 @@
-"""A/B (GPU): weight gradient of the final 3-channel layer (n3_wgrad16, 32 channels, stride 1) and of Encoder.conv1 (64 channels, stride 2)
-at the launch shapes; LG_N3W_TH8=1 = 8-row tiles everywhere."""
+"""Timer (GPU): weight gradient of the final 3-channel layer (n3_wgrad16, 32 channels, stride 1) and of Encoder.conv1 (64 channels, stride 2)
+at the launch shapes; scripts/probe/n3w_ablate.sh runs it against its LG_N3W_DBG variant builds."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch

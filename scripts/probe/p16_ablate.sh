@@ -10,4 +10,3 @@ for bits in ${LG_P16_BITS:-1 2 4 8 15}; do
   echo "== LG_P16_DBG=$bits"
   LG_LIB_VARIANT=p16d$bits python scripts/bench_patch.py | grep -E "conv1 fwd|final dgrad"
 done
-for gsz in 512 768 1024 1536; do echo "== LG_PATCH_GRID=$gsz"; LG_PATCH_GRID=$gsz python scripts/bench_patch.py | grep -E "conv1 fwd|final dgrad"; done

@@ -1,6 +1,6 @@
 """How far do the 1-element gradient tensors (gamma / beta: sums with heavy cancellation) of one bf16 step sit from the bf16-emulating
-oracle, and how much does that distance move between EQUIVALENT kernel choices?  Run once per environment (the switches are read once per
-process), e.g.  LG_ROWS_XJ1=1 / LG_NO_ZN=1 / LG_NO_UP4_PAIR=1:  the kernels behind those switches compute the same sums in another
+oracle, and how much does that distance move between EQUIVALENT kernel choices?  Run once per environment (the kill switches of
+DESIGN 4 are read once per process), e.g.  LG_NO_ROWS=1 / LG_NO_D3_NORM=1 / LG_NO_UP4=1:  the kernels the shapes then fall to compute the same sums in another
 order, so a difference between the runs is the noise floor of the whole-step comparison, not an error of either kernel.
 Measured in round 3 (init_dim 8): between the build whose final layer added its taps in kx order 0..4 and the one adding them 4..0
 (same products, fp32 sums in another order: images differ in the last bit) the ORACLE's Adjuster norm-beta gradient moved from 0.011329
