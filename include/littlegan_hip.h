@@ -219,6 +219,45 @@ int lg_convT_s2_dgrad_bn(const void* z16, const void* g16, const float* coef, fl
  * {sum g', sum g' c} ([B][nparts][2] doubles): the norm backward without its apply pass (L = elements per sample) */
 int lg_instnorm_bwd_coef(const float* stats, const void* partials, int nparts, float* coef, int B, long long L, void* stream);
 
+/* ---- encoder dropout (dropout_train / dropout_rate, sample.config.json: `dropout_rate`) ---------------------------------- *
+ * The reference calls tf.compat.v1.layers.dropout without training=True (model.py:25): the identity.  THIS PROJECT's live form
+ * (DESIGN.md 15): every encoder level of the training step is h = LeakyReLU(InstanceNorm(z)) * keep * scale, the mask regenerated
+ * from a counter inside the norm passes and never stored.  Element e (flat NHWC index) of sample row r (absolute row of the
+ * encoder call's batch; L elements per sample, L % 8 == 0):
+ *   T = round(rate * 65536),  scale = 65536 / (65536 - T) (fp32),
+ *   offset = key_offset + (call << 34) + ((level-1) << 32) + r*(L/8) + e/8,
+ *   P = philox4x32_10(ctr = (lo32(offset), hi32(offset), 0, 0), key = (lo32(seed), hi32(seed))),
+ *   w = (P[(e%8) >> 1] >> (16*(e&1))) & 0xFFFF,  keep = (w >= T).
+ * key = {seed, key_offset} as two 64-bit words in DEVICE memory (a step input: a captured graph replays with new masks);
+ * call 0..3 (the step uses 0: D on [new_image ; fake], 1: the Adjuster's encoder pass, 2: D on the Adjuster's output), level 1..4,
+ * r0 = the row the first sample of the launch has in the call's batch, rate in [0, 1).  All arguments are checked on the host
+ * before any launch.  The *_drop entry points are the twins of the plain ones in the encoder's form (no skip operand, LeakyReLU
+ * behind the norm); the backward multiplies the arriving gradient g by the same keep * scale in both of its passes. */
+/* key[2] = {seed, key_offset}, written on the device from launch scalars (no host-to-device copy, no synchronisation) */
+int lg_dropout_key(long long* key, unsigned long long seed, unsigned long long key_offset, void* stream);
+/* keep[B][L] bytes (1 = kept) of rows r0 .. r0+B-1: the definition above, testable; keep 8-byte aligned.  Everywhere below the rows
+ * r0 .. r0+B-1 must lie inside the level's window: (r0 + B) * (L/8) <= 2^32 */
+int lg_dropout_mask(const long long* key, int call, int level, int r0, int B, long long L, float rate, unsigned char* keep,
+                    void* stream);
+int lg_instnorm_leaky_apply_drop(const float* x, const float* stats, float* y, void* y16, int B, long long L, float alpha,
+                                 const long long* key, int call, int level, int r0, float rate, void* stream);
+int lg_instnorm_leaky_apply_z16_drop(const void* z16, const float* stats, float* y, void* y16, int B, long long L, float alpha,
+                                     const long long* key, int call, int level, int r0, float rate, void* stream);
+int lg_instnorm_leaky_apply_z16_p_drop(const void* z16, const void* partials, int nparts, const float* gamma, const float* beta,
+                                       float* stats, float* y, void* y16, int B, long long L, float alpha, const long long* key,
+                                       int call, int level, int r0, float rate, void* stream);
+/* workspace: lg_instnorm_bwd_db_workspace_bytes, as the plain twins */
+int lg_instnorm_leaky_bwd_drop(const float* x, const float* stats, const void* g, int g_is_bf16, float* dx, void* dx16,
+                               float* dgamma, float* dbeta, float* db, int C, void* workspace, size_t ws_bytes, int B,
+                               long long L, float alpha, int accumulate, const long long* key, int call, int level, int r0,
+                               float rate, void* stream);
+/* partials / nparts_in (may be null / 0) as lg_instnorm_leaky_bwd_z16_p: accepted only where the mask keeps everything (T == 0) -
+ * producer-fused sums are those of the unmasked gradient */
+int lg_instnorm_leaky_bwd_z16_drop(const void* z16, const float* stats, const void* g, int g_is_bf16, float* dx, void* dx16,
+                                   float* dgamma, float* dbeta, float* db, int C, const void* partials, int nparts_in,
+                                   void* workspace, size_t ws_bytes, int B, long long L, float alpha, int accumulate,
+                                   const long long* key, int call, int level, int r0, float rate, void* stream);
+
 int lg_convT_s1_tanh_bwd_nf(const float* x, const void* x16, const float* dpre, const void* pack, void* dx16, float* dw,
                             float* db, void* workspace, size_t ws_bytes, int B, int H, int W, int cb, int cs, int accumulate,
                             int dtype, const void* z16, const float* stats, float alpha, void* part, size_t part_bytes,

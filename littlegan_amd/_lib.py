@@ -70,6 +70,14 @@ SIGNATURES = {
     "lg_convT_s2_dgrad_bn_supported": (I, [I, I, I, I, I]),
     "lg_convT_s2_dgrad_bn": (I, [P, P, P, F, P, P, I, I, I, I, I, P, P, F, P, Z, P, P]),
     "lg_instnorm_bwd_coef": (I, [P, P, I, P, I, L, P]),
+    # encoder dropout (dropout_train): the mask made testable + the dropped twins of the encoder's norm passes (norm.hip)
+    "lg_dropout_key": (I, [P, L, L, P]),   # seed / key_offset: unsigned long long in C, passed as their 64-bit pattern
+    "lg_dropout_mask": (I, [P, I, I, I, I, L, F, P, P]),
+    "lg_instnorm_leaky_apply_drop": (I, [P, P, P, P, I, L, F, P, I, I, I, F, P]),
+    "lg_instnorm_leaky_apply_z16_drop": (I, [P, P, P, P, I, L, F, P, I, I, I, F, P]),
+    "lg_instnorm_leaky_apply_z16_p_drop": (I, [P, P, I, P, P, P, P, P, I, L, F, P, I, I, I, F, P]),
+    "lg_instnorm_leaky_bwd_drop": (I, [P, P, P, I, P, P, P, P, P, I, P, Z, I, L, F, I, P, I, I, I, F, P]),
+    "lg_instnorm_leaky_bwd_z16_drop": (I, [P, P, P, I, P, P, P, P, P, I, P, I, P, Z, I, L, F, I, P, I, I, I, F, P]),
     "lg_convT_s1_tanh_bwd_nf": (I, [P, P, P, P, P, P, P, P, Z, I, I, I, I, I, I, I, P, P, F, P, Z, P, P]),
     "lg_dense_fwd": (I, [P, P, P, P, I, I, I, P]),
     "lg_dense_wgrad": (I, [P, P, P, P, I, I, I, I, P]),

@@ -1,7 +1,8 @@
 """Mirror of /root/reference/config.py:6-42: sample.config.json < <env>.config.json < CLI, every key an
 attribute, derived cond_dim / result_dir / gpu / prefetch.  Extra keys of this build: mfma_dtype ("f32" |
 "bf16"), synthetic (bool: use the synthetic CelebA-shaped dataset), seed, packed_path / data_resident / fuse_input
-(the packed uint8 data set, dataset.py), fid_chunk_rows / fid_device_sqrt (streamed FID statistics, device square root, fid.py)."""
+(the packed uint8 data set, dataset.py), fid_chunk_rows / fid_device_sqrt (streamed FID statistics, device square root, fid.py), dropout_train (bool: make the encoder's
+dropout(dropout_rate) live in the training step — the reference's, and the default here, is the identity)."""
 import json
 import os
 from argparse import ArgumentParser
@@ -55,6 +56,9 @@ DEFAULTS = {
     # FID pass: rows per streamed block of activations (null: the whole matrix at once, the present path); whether
     # tr sqrt(S1 S2) is taken on the device by the fp64 Newton-Schulz iteration instead of scipy's sqrtm
     'fid_chunk_rows': None, 'fid_device_sqrt': False,
+    # live encoder dropout: the reference declares dropout_rate and never applies it (model.py:25); with this key the
+    # training step's encoder passes apply it (0 < dropout_rate < 1), masks regenerated inside the norm kernels.  Excludes use_gp.
+    'dropout_train': False,
 }
 
 MODES = ["train", "pack", "plot", "visual", "random-sample", "evaluate", "condition-sample", "evaluate-sample", "export-model"]

@@ -38,11 +38,13 @@ def build(force=False, verbose=True, variant=None):
         raise SystemExit("LG_EXTRA_FLAGS needs --variant NAME: ablation builds never replace the product library")
     os.makedirs(objdir, exist_ok=True)
     common_h, public_h = os.path.join(HERE, "lg_common.h"), os.path.join(os.path.dirname(PKG), "include", "littlegan_hip.h")
-    augment_h = os.path.join(HERE, "augment_core.h")
+    augment_h, philox_h = os.path.join(HERE, "augment_core.h"), os.path.join(HERE, "philox.h")
 
     def hdrs_of(path):   # the public header is a dependency of the sources that include it (capi.hip, runtime.hip), not of every kernel file
-        text = open(path).read()   # augment_core.h: the device code augment.hip and input_u8.hip share
-        return [common_h] + ([public_h] if "littlegan_hip.h" in text else []) + ([augment_h] if "augment_core.h" in text else [])
+        text = open(path).read()   # augment_core.h: the device code augment.hip and input_u8.hip share; philox.h: those and norm.hip
+        aug = "augment_core.h" in text
+        return ([common_h] + ([public_h] if "littlegan_hip.h" in text else []) + ([augment_h] if aug else [])
+                + ([philox_h] if aug or "philox.h" in text else []))
 
     # LG_EXTRA_FLAGS carries the ablation macros of scripts/probe/*.sh ("results wrong, timing only"): the flag set an object
     # was built with is recorded beside it, and an object (hence the library) built with OTHER flags is stale — a probe build

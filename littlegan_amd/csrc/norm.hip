@@ -13,7 +13,10 @@
 // rounding error is coherent; the later reductions of the step (bias / weight gradients = sums over up to
 // 10^6 pixels of quantities whose mean was removed here) amplify a coherent 1e-7 error to 1e-3.
 // All kernels are HBM-bound: 16-B vector loads, one pass over x for the moments (values kept in registers).
+// The encoder's live dropout (dropout_train) rides on the same passes: dropped twins of apply / bwd regenerate the mask from a
+// Philox counter in registers (DropK below); the mask-free kernels are the DROP = false instances of the shared bodies.
 #include "lg_common.h"
+#include "philox.h"
 
 #define LG_IN_EPS 1e-3f
 #define LG_NSTAT 8
@@ -119,17 +122,63 @@ constexpr bool NT_LOAD = true;
 template <bool NT, typename V>
 __device__ __forceinline__ V lg_ld(const V* q) { if constexpr (NT) return __builtin_nontemporal_load(q); else return *q; }
 
-__global__ __launch_bounds__(256) void apply_kernel(const float* __restrict__ x, const float* __restrict__ stats,
+// ---- encoder dropout (dropout_train): h = LeakyReLU(InstanceNorm(z)) * keep * scale, the mask REGENERATED in registers
+// by every pass that needs it (forward apply, both passes of the backward) from a counter — nothing is stored.  Element e of sample row r
+// (absolute row of the encoder call's batch, L elements per sample, NHWC) takes 16 bits of Philox block
+//   offset = key_offset + (call << 34) + ((level-1) << 32) + r*(L/8) + e/8,  ctr = (lo32(offset), hi32(offset), 0, 0), key = seed:
+//   w = (P[(e%8) >> 1] >> (16*(e&1))) & 0xFFFF,  keep = (w >= T),  T = round(rate * 65536),  scale = 65536 / (65536 - T)
+// One block = 8 consecutive elements = one 16-byte bf16 access.  A launch covers whole rows of one tensor, so r*(L/8) + e/8 is the
+// launch's first-row term (in `base`) plus the 8-element unit index within the launch's tensor: the mask cannot depend on the grid, the
+// unroll, the operand path or the batch slice.  {seed, key_offset} are read from DEVICE memory (a step input: a captured graph replays
+// with the masks of the step it is given).  The DROP = false instance of every body below is the mask-free kernel, unchanged.
+struct DropK {
+  const unsigned long long* key;  // device: {seed, key_offset}
+  unsigned long long base;        // (call << 34) + ((level-1) << 32) + r0*(L/8)
+  unsigned T;
+  float scale;
+};
+// launch geometry, read in the KERNEL and handed to its body: there the compiler folds blockDim with the launch bounds
+struct Geo { unsigned bdx, gdx, gdy; };
+struct DropCtx { unsigned k0, k1; unsigned long long c0; unsigned T; float scale; };
+template <bool DROP>
+__device__ __forceinline__ DropCtx drop_begin(const DropK& dk) {
+  DropCtx c{0u, 0u, 0ull, 0u, 1.f};
+  if constexpr (DROP) {
+    const unsigned long long seed = dk.key[0];
+    c.k0 = (unsigned)seed; c.k1 = (unsigned)(seed >> 32);
+    c.c0 = dk.key[1] + dk.base; c.T = dk.T; c.scale = dk.scale;
+  }
+  return c;
+}
+__device__ __forceinline__ float drop_mul(const DropCtx& c, unsigned w16) { return w16 >= c.T ? c.scale : 0.f; }
+// keep*scale of the 8 elements of unit u8 (8-element unit index within the launch's tensor)
+__device__ __forceinline__ void drop_mult8(const DropCtx& c, unsigned long long u8, float (&m)[8]) {
+  const unsigned long long o = c.c0 + u8;
+  const u4 p = philox4x32_10(u4{(unsigned)o, (unsigned)(o >> 32), 0u, 0u}, c.k0, c.k1);
+  m[0] = drop_mul(c, p.x & 0xFFFFu); m[1] = drop_mul(c, p.x >> 16); m[2] = drop_mul(c, p.y & 0xFFFFu); m[3] = drop_mul(c, p.y >> 16);
+  m[4] = drop_mul(c, p.z & 0xFFFFu); m[5] = drop_mul(c, p.z >> 16); m[6] = drop_mul(c, p.w & 0xFFFFu); m[7] = drop_mul(c, p.w >> 16);
+}
+// the same for the 4 elements of unit u4i of the fp32 passes (half a block)
+__device__ __forceinline__ void drop_mult4(const DropCtx& c, unsigned long long u4i, float (&m)[4]) {
+  const unsigned long long o = c.c0 + (u4i >> 1);
+  const u4 p = philox4x32_10(u4{(unsigned)o, (unsigned)(o >> 32), 0u, 0u}, c.k0, c.k1);
+  const unsigned w0 = (u4i & 1) ? p.z : p.x, w1 = (u4i & 1) ? p.w : p.y;
+  m[0] = drop_mul(c, w0 & 0xFFFFu); m[1] = drop_mul(c, w0 >> 16); m[2] = drop_mul(c, w1 & 0xFFFFu); m[3] = drop_mul(c, w1 >> 16);
+}
+
+template <bool DROP>
+__device__ __forceinline__ void apply_body(const float* __restrict__ x, const float* __restrict__ stats,
                                                     const float* __restrict__ skip, float* __restrict__ y,
                                                     __bf16* __restrict__ y16, long long L4, long long total4,
-                                                    int pre_leaky, int post_leaky, float alpha) {
+                                                    int pre_leaky, int post_leaky, float alpha, const DropK& dk, const Geo ge) {
+  const DropCtx dc = drop_begin<DROP>(dk);
   // EW_UNR independent 16-B loads per thread per trip: a single load in flight per thread leaves the pass latency-bound
   // (measured 2.5-3.9 TB/s against 5.5+ for a streaming copy)
-  const unsigned stride = gridDim.x * blockDim.x * EW_UNR, tot = (unsigned)total4, l4 = (unsigned)L4;
+  const unsigned stride = ge.gdx * ge.bdx * EW_UNR, tot = (unsigned)total4, l4 = (unsigned)L4;
   const unsigned rb = blockIdx.x;
   const int ntrip = (int)(((unsigned long long)tot + stride - 1) / stride);
   for (int tr = 0; tr < ntrip; ++tr) {  // block-contiguous 16-KB trips
-    const unsigned long long i0l = (unsigned long long)tr * stride + rb * blockDim.x * EW_UNR + threadIdx.x;
+    const unsigned long long i0l = (unsigned long long)tr * stride + rb * ge.bdx * EW_UNR + threadIdx.x;
     if (i0l >= tot) continue;
     const unsigned i0 = (unsigned)i0l;
     f32x4 v[EW_UNR], sk[EW_UNR];
@@ -147,12 +196,15 @@ __global__ __launch_bounds__(256) void apply_kernel(const float* __restrict__ x,
       if (i >= tot) break;
       const float* sp = stats + (long long)(i / l4) * LG_NSTAT;
       const float mu = sp[0], a = sp[2], b = sp[3], mul = sp[4];
+      float dm[4];
+      if constexpr (DROP) drop_mult4(dc, i, dm);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         float t = v[u][k];
         if (pre_leaky) t = lg_leaky(t, alpha);
         t = a * ((t - mu) - mul) + b;  // (x-mu)/(sigma+eps)*gamma + beta, as instance.py:116-127 (no cancellation)
         if (post_leaky) t = lg_leaky(t, alpha);
+        if constexpr (DROP) t = t * dm[k];
         v[u][k] = t;
       }
       if (skip) v[u] += sk[u];
@@ -166,6 +218,19 @@ __global__ __launch_bounds__(256) void apply_kernel(const float* __restrict__ x,
   }
 }
 
+__global__ __launch_bounds__(256) void apply_kernel(const float* __restrict__ x, const float* __restrict__ stats,
+                                                    const float* __restrict__ skip, float* __restrict__ y,
+                                                    __bf16* __restrict__ y16, long long L4, long long total4,
+                                                    int pre_leaky, int post_leaky, float alpha) {
+  apply_body<false>(x, stats, skip, y, y16, L4, total4, pre_leaky, post_leaky, alpha, DropK{}, Geo{blockDim.x, gridDim.x, gridDim.y});
+}
+// the encoder's form (no skip operand, LeakyReLU behind the norm) with the dropout mask
+__global__ __launch_bounds__(256) void apply_drop_kernel(const float* __restrict__ x, const float* __restrict__ stats,
+                                                         float* __restrict__ y, __bf16* __restrict__ y16, long long L4,
+                                                         long long total4, float alpha, DropK dk) {
+  apply_body<true>(x, stats, nullptr, y, y16, L4, total4, 0, 1, alpha, dk, Geo{blockDim.x, gridDim.x, gridDim.y});
+}
+
 template <bool NT = false>
 __device__ __forceinline__ f32x4 load_g4(const void* g, long long i4, int g16) {  // 4 gradient values, fp32 or bf16 storage
   if (g16) {
@@ -176,18 +241,20 @@ __device__ __forceinline__ f32x4 load_g4(const void* g, long long i4, int g16) {
 }
 
 // partial[n][chunk] = {sum dz, sum dz*c} (doubles)
-__global__ __launch_bounds__(256) void bwd_partial_kernel(const float* __restrict__ x, const void* __restrict__ g, int g16,
-                                                          const float* __restrict__ stats, double* __restrict__ partial,
-                                                          long long L, int nchunk, int pre_leaky, int post_leaky,
-                                                          float alpha) {
-  // gridDim.x blocks per sample, each sweeping chunks blockIdx.x, blockIdx.x + gridDim.x, ... (few long-lived blocks
-  // stream better than one short block per chunk), ONE block reduction at the end; nchunk = gridDim.x partial records
+template <bool DROP>
+__device__ __forceinline__ void bwd_partial_body(const float* __restrict__ x, const void* __restrict__ g, int g16,
+                                                 const float* __restrict__ stats, double* __restrict__ partial,
+                                                 long long L, int nchunk, int pre_leaky, int post_leaky,
+                                                 float alpha, const DropK& dk, const Geo ge) {
+  const DropCtx dc = drop_begin<DROP>(dk);
+  // ge.gdx blocks per sample, each sweeping chunks blockIdx.x, blockIdx.x + ge.gdx, ... (few long-lived blocks
+  // stream better than one short block per chunk), ONE block reduction at the end; nchunk = ge.gdx partial records
   const int n = blockIdx.y;
   const float* sp = stats + (long long)n * LG_NSTAT;
   const float mu = sp[0], a = sp[2], b = sp[3], mul = sp[4];
   __shared__ double sred[32];
   double s1 = 0.0, s2 = 0.0;
-  for (long long c0 = (long long)blockIdx.x * CHUNK; c0 < L; c0 += (long long)gridDim.x * CHUNK) {
+  for (long long c0 = (long long)blockIdx.x * CHUNK; c0 < L; c0 += (long long)ge.gdx * CHUNK) {
    const long long base = (long long)n * L + c0;
    const long long lim = L - c0;
 #pragma unroll
@@ -199,12 +266,15 @@ __global__ __launch_bounds__(256) void bwd_partial_kernel(const float* __restric
       // the 4 values of a quad are summed in fp32 (c = (x - mu_hi) - mu_lo is the float-float centred value the
       // forward pass uses, so no coherent error enters), the quads in fp64: the fp64 VALU rate, not HBM, bounded this pass
       float q1 = 0.f, q2 = 0.f;
+      float dm[4];
+      if constexpr (DROP) drop_mult4(dc, (unsigned long long)(base + e) >> 2, dm);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         float xx = xv[k];
         if (pre_leaky) xx = lg_leaky(xx, alpha);
         const float c = (xx - mu) - mul;
         float dz = gv[k];
+        if constexpr (DROP) dz = dz * dm[k];   // the gradient behind the mask: both passes of the backward see it
         if (post_leaky) dz = (a * c + b > 0.f) ? dz : alpha * dz;
         q1 += dz;
         q2 += dz * c;
@@ -220,6 +290,18 @@ __global__ __launch_bounds__(256) void bwd_partial_kernel(const float* __restric
     double* o = partial + ((long long)n * nchunk + blockIdx.x) * 2;
     o[0] = red[0]; o[1] = red[1];
   }
+}
+
+__global__ __launch_bounds__(256) void bwd_partial_kernel(const float* __restrict__ x, const void* __restrict__ g, int g16,
+                                                          const float* __restrict__ stats, double* __restrict__ partial,
+                                                          long long L, int nchunk, int pre_leaky, int post_leaky,
+                                                          float alpha) {
+  bwd_partial_body<false>(x, g, g16, stats, partial, L, nchunk, pre_leaky, post_leaky, alpha, DropK{}, Geo{blockDim.x, gridDim.x, gridDim.y});
+}
+__global__ __launch_bounds__(256) void bwd_partial_drop_kernel(const float* __restrict__ x, const void* __restrict__ g, int g16,
+                                                               const float* __restrict__ stats, double* __restrict__ partial,
+                                                               long long L, int nchunk, float alpha, DropK dk) {
+  bwd_partial_body<true>(x, g, g16, stats, partial, L, nchunk, 0, 1, alpha, dk, Geo{blockDim.x, gridDim.x, gridDim.y});
 }
 
 // bstats[n][4] = {m1_hi, m2'_hi, m1_lo, m2'_lo} ; gsum[n] = per-sample dgamma / dbeta contributions
@@ -283,19 +365,20 @@ __global__ __launch_bounds__(256) void bwd_affine_grad_kernel(const double* __re
 // channels innermost).  The launch makes gridDim.x*256 a multiple of C/4, so a thread meets the same 4 channels in
 // every trip; threads of a block are merged in thread order into colpart[block][C] (deterministic), blocks by
 // colsum_final (below).
-template <bool DB>
-__global__ __launch_bounds__(256) void bwd_apply_kernel(const float* __restrict__ x, const void* __restrict__ g, int g16,
-                                                        const float* __restrict__ stats, const float* __restrict__ bstats,
-                                                        float* __restrict__ dx, __bf16* __restrict__ dx16, long long L4,
-                                                        long long total4, int pre_leaky, int post_leaky, float alpha,
-                                                        float* __restrict__ colpart, int C4) {
+template <bool DB, bool DROP>
+__device__ __forceinline__ void bwd_apply_body(const float* __restrict__ x, const void* __restrict__ g, int g16,
+                                               const float* __restrict__ stats, const float* __restrict__ bstats,
+                                               float* __restrict__ dx, __bf16* __restrict__ dx16, long long L4,
+                                               long long total4, int pre_leaky, int post_leaky, float alpha,
+                                               float* __restrict__ colpart, int C4, const DropK& dk, const Geo ge) {
+  const DropCtx dc = drop_begin<DROP>(dk);
   constexpr int UNR = DB ? 1 : EW_UNR;  // DB: a thread must stay on one channel quad -> plain grid stride
-  const unsigned stride = gridDim.x * blockDim.x * UNR, tot = (unsigned)total4, l4 = (unsigned)L4;
+  const unsigned stride = ge.gdx * ge.bdx * UNR, tot = (unsigned)total4, l4 = (unsigned)L4;
   f32x4 csum = {0.f, 0.f, 0.f, 0.f};
   const unsigned rb = blockIdx.x;
   const int ntrip = (int)(((unsigned long long)tot + stride - 1) / stride);
   for (int tr = 0; tr < ntrip; ++tr) {
-   const unsigned long long i0l = (unsigned long long)tr * stride + rb * blockDim.x * UNR + threadIdx.x;
+   const unsigned long long i0l = (unsigned long long)tr * stride + rb * ge.bdx * UNR + threadIdx.x;
    if (i0l >= tot) continue;
    const unsigned i0 = (unsigned)i0l;
    f32x4 xs[UNR], gs[UNR];
@@ -317,12 +400,15 @@ __global__ __launch_bounds__(256) void bwd_apply_kernel(const float* __restrict_
     const float m1 = bstats[n * 4], m2 = bstats[n * 4 + 1], m1l = bstats[n * 4 + 2], m2l = bstats[n * 4 + 3];
     const f32x4 xv = xs[u], gv = gs[u];
     f32x4 o;
+    float dm[4];
+    if constexpr (DROP) drop_mult4(dc, i, dm);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       float xx = xv[k];
       if (pre_leaky) xx = lg_leaky(xx, alpha);
       const float c = (xx - mu) - mul;
       float dz = gv[k];
+      if constexpr (DROP) dz = dz * dm[k];
       if (post_leaky) dz = (a * c + b > 0.f) ? dz : alpha * dz;
       float d = a * ((((dz - m1) - m1l) - c * m2) - c * m2l);
       if (pre_leaky) d = (xv[k] > 0.f) ? d : alpha * d;
@@ -349,6 +435,22 @@ __global__ __launch_bounds__(256) void bwd_apply_kernel(const float* __restrict_
       *reinterpret_cast<f32x4*>(colpart + ((long long)rb * C4 + q) * 4) = t;
     }
   }
+}
+template <bool DB>
+__global__ __launch_bounds__(256) void bwd_apply_kernel(const float* __restrict__ x, const void* __restrict__ g, int g16,
+                                                        const float* __restrict__ stats, const float* __restrict__ bstats,
+                                                        float* __restrict__ dx, __bf16* __restrict__ dx16, long long L4,
+                                                        long long total4, int pre_leaky, int post_leaky, float alpha,
+                                                        float* __restrict__ colpart, int C4) {
+  bwd_apply_body<DB, false>(x, g, g16, stats, bstats, dx, dx16, L4, total4, pre_leaky, post_leaky, alpha, colpart, C4, DropK{}, Geo{blockDim.x, gridDim.x, gridDim.y});
+}
+template <bool DB>
+__global__ __launch_bounds__(256) void bwd_apply_drop_kernel(const float* __restrict__ x, const void* __restrict__ g, int g16,
+                                                             const float* __restrict__ stats, const float* __restrict__ bstats,
+                                                             float* __restrict__ dx, __bf16* __restrict__ dx16, long long L4,
+                                                             long long total4, float alpha, float* __restrict__ colpart, int C4,
+                                                             DropK dk) {
+  bwd_apply_body<DB, true>(x, g, g16, stats, bstats, dx, dx16, L4, total4, 0, 1, alpha, colpart, C4, dk, Geo{blockDim.x, gridDim.x, gridDim.y});
 }
 
 
@@ -391,13 +493,14 @@ __device__ __forceinline__ void store8_f32(float* p, long long i8, const f32x8& 
 constexpr int EW8_UNR = 2, DB_UNR = 2;
 
 // y = leaky(a*((z - mu_hi) - mu_lo) + beta) [+ skip]  from the bf16 z;  SK: 0 none, 1 fp32 skip, 2 bf16 skip
-template <int SK>
-__global__ __launch_bounds__(256) void apply16_kernel(const __bf16* __restrict__ x, const float* __restrict__ stats,
-                                                      const void* __restrict__ skip, float* __restrict__ y,
-                                                      __bf16* __restrict__ y16, long long L8, long long total8,
-                                                      int pre_leaky, int post_leaky, float alpha) {
-  const unsigned stride = gridDim.x * blockDim.x * EW8_UNR, tot = (unsigned)total8, l8 = (unsigned)L8;
-  for (unsigned i0 = blockIdx.x * blockDim.x * EW8_UNR + threadIdx.x; i0 < tot; i0 += stride) {
+template <int SK, bool DROP>
+__device__ __forceinline__ void apply16_body(const __bf16* __restrict__ x, const float* __restrict__ stats,
+                                             const void* __restrict__ skip, float* __restrict__ y,
+                                             __bf16* __restrict__ y16, long long L8, long long total8,
+                                             int pre_leaky, int post_leaky, float alpha, const DropK& dk, const Geo ge) {
+  const DropCtx dc = drop_begin<DROP>(dk);
+  const unsigned stride = ge.gdx * ge.bdx * EW8_UNR, tot = (unsigned)total8, l8 = (unsigned)L8;
+  for (unsigned i0 = blockIdx.x * ge.bdx * EW8_UNR + threadIdx.x; i0 < tot; i0 += stride) {
     f32x8 v[EW8_UNR], sk[EW8_UNR];
 #pragma unroll
     for (int u = 0; u < EW8_UNR; ++u) {
@@ -414,12 +517,15 @@ __global__ __launch_bounds__(256) void apply16_kernel(const __bf16* __restrict__
       if (i >= tot) break;
       const float* sp = stats + (long long)(i / l8) * LG_NSTAT;
       const float mu = sp[0], a = sp[2], b = sp[3], mul = sp[4];
+      float dm[8];
+      if constexpr (DROP) drop_mult8(dc, i, dm);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         float t = k < 4 ? v[u].lo[k & 3] : v[u].hi[k & 3];
         if (pre_leaky) t = lg_leaky(t, alpha);
         t = a * ((t - mu) - mul) + b;
         if (post_leaky) t = lg_leaky(t, alpha);
+        if constexpr (DROP) t = t * dm[k];
         if constexpr (SK != 0) t += k < 4 ? sk[u].lo[k & 3] : sk[u].hi[k & 3];
         if (k < 4) v[u].lo[k & 3] = t; else v[u].hi[k & 3] = t;
       }
@@ -429,20 +535,34 @@ __global__ __launch_bounds__(256) void apply16_kernel(const __bf16* __restrict__
   }
 }
 
+template <int SK>
+__global__ __launch_bounds__(256) void apply16_kernel(const __bf16* __restrict__ x, const float* __restrict__ stats,
+                                                      const void* __restrict__ skip, float* __restrict__ y,
+                                                      __bf16* __restrict__ y16, long long L8, long long total8,
+                                                      int pre_leaky, int post_leaky, float alpha) {
+  apply16_body<SK, false>(x, stats, skip, y, y16, L8, total8, pre_leaky, post_leaky, alpha, DropK{}, Geo{blockDim.x, gridDim.x, gridDim.y});
+}
+__global__ __launch_bounds__(256) void apply16_drop_kernel(const __bf16* __restrict__ x, const float* __restrict__ stats,
+                                                           float* __restrict__ y, __bf16* __restrict__ y16, long long L8,
+                                                           long long total8, float alpha, DropK dk) {
+  apply16_body<0, true>(x, stats, nullptr, y, y16, L8, total8, 0, 1, alpha, dk, Geo{blockDim.x, gridDim.x, gridDim.y});
+}
+
 // apply16 with the statistics FINALISED IN THE SAME LAUNCH: grid (blocks per sample, B); the first wave of every block merges the
 // sample's moment partials {count, mean, M2} exactly as stats_final_kernel does (same order, same fp64 arithmetic: the record is
 // bit-identical), block 0 of a sample writes the record for the later consumers (backward, fused conv epilogues).  One launch and
 // one kernel boundary less per normalised map (22 per C3 step); post-LeakyReLU form only (pre_leaky = 0).
-template <int SK>
-__global__ __launch_bounds__(256) void apply16p_kernel(const __bf16* __restrict__ x, const double* __restrict__ partial, int nchunk,
-                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                       float* __restrict__ stats, const void* __restrict__ skip,
-                                                       float* __restrict__ y, __bf16* __restrict__ y16, unsigned L8,
-                                                       int post_leaky, float alpha) {
+template <int SK, bool DROP>
+__device__ __forceinline__ void apply16p_body(const __bf16* __restrict__ x, const double* __restrict__ partial, int nchunk,
+                                              const float* __restrict__ gamma, const float* __restrict__ beta,
+                                              float* __restrict__ stats, const void* __restrict__ skip,
+                                              float* __restrict__ y, __bf16* __restrict__ y16, unsigned L8,
+                                              int post_leaky, float alpha, const DropK& dk, const Geo ge) {
+  const DropCtx dc = drop_begin<DROP>(dk);
   __shared__ float sst[8];
   // samples and chunks from the END — the producer wrote the end of the map last, the consumer reads its start first
-  const int n = (int)(gridDim.y - 1 - blockIdx.y);
-  const unsigned bx = gridDim.x - 1 - blockIdx.x;
+  const int n = (int)(ge.gdy - 1 - blockIdx.y);
+  const unsigned bx = ge.gdx - 1 - blockIdx.x;
   if (threadIdx.x < 64) {
     const int lane = threadIdx.x;
     const double* p = partial + (long long)n * nchunk * 3;
@@ -471,10 +591,10 @@ __global__ __launch_bounds__(256) void apply16p_kernel(const __bf16* __restrict_
   __syncthreads();
   const float mu = sst[0], a = sst[2], b = sst[3], mul = sst[4];
   const long long base = (long long)n * L8;
-  const unsigned stride = gridDim.x * blockDim.x * EW8_UNR;
+  const unsigned stride = ge.gdx * ge.bdx * EW8_UNR;
   const int ntrip = (int)((L8 + stride - 1) / stride);
   for (int tr = 0; tr < ntrip; ++tr) {
-    const unsigned i0 = (unsigned)(ntrip - 1 - tr) * stride + bx * blockDim.x * EW8_UNR + threadIdx.x;
+    const unsigned i0 = (unsigned)(ntrip - 1 - tr) * stride + bx * ge.bdx * EW8_UNR + threadIdx.x;
     if (i0 >= L8) continue;
     f32x8 v[EW8_UNR], sk[EW8_UNR];
 #pragma unroll
@@ -490,11 +610,14 @@ __global__ __launch_bounds__(256) void apply16p_kernel(const __bf16* __restrict_
     for (int u = 0; u < EW8_UNR; ++u) {
       const unsigned i = i0 + u * 256;
       if (i >= L8) break;
+      float dm[8];
+      if constexpr (DROP) drop_mult8(dc, (unsigned long long)(base + i), dm);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         float t = k < 4 ? v[u].lo[k & 3] : v[u].hi[k & 3];
         t = a * ((t - mu) - mul) + b;
         if (post_leaky) t = lg_leaky(t, alpha);
+        if constexpr (DROP) t = t * dm[k];
         if constexpr (SK != 0) t += k < 4 ? sk[u].lo[k & 3] : sk[u].hi[k & 3];
         if (k < 4) v[u].lo[k & 3] = t; else v[u].hi[k & 3] = t;
       }
@@ -504,19 +627,35 @@ __global__ __launch_bounds__(256) void apply16p_kernel(const __bf16* __restrict_
   }
 }
 
+template <int SK>
+__global__ __launch_bounds__(256) void apply16p_kernel(const __bf16* __restrict__ x, const double* __restrict__ partial, int nchunk,
+                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                       float* __restrict__ stats, const void* __restrict__ skip,
+                                                       float* __restrict__ y, __bf16* __restrict__ y16, unsigned L8,
+                                                       int post_leaky, float alpha) {
+  apply16p_body<SK, false>(x, partial, nchunk, gamma, beta, stats, skip, y, y16, L8, post_leaky, alpha, DropK{}, Geo{blockDim.x, gridDim.x, gridDim.y});
+}
+__global__ __launch_bounds__(256) void apply16p_drop_kernel(const __bf16* __restrict__ x, const double* __restrict__ partial, int nchunk,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            float* __restrict__ stats, float* __restrict__ y,
+                                                            __bf16* __restrict__ y16, unsigned L8, float alpha, DropK dk) {
+  apply16p_body<0, true>(x, partial, nchunk, gamma, beta, stats, nullptr, y, y16, L8, 1, alpha, dk, Geo{blockDim.x, gridDim.x, gridDim.y});
+}
+
 // partial[n][blk] = {sum dz, sum dz*c} from the bf16 z; G16: gradient stored as bf16
-template <bool G16>
-__global__ __launch_bounds__(256) void bwd_partial16_kernel(const __bf16* __restrict__ x, const void* __restrict__ g,
-                                                            const float* __restrict__ stats, double* __restrict__ partial,
-                                                            long long L, int nchunk, int pre_leaky, int post_leaky,
-                                                            float alpha) {
+template <bool G16, bool DROP>
+__device__ __forceinline__ void bwd_partial16_body(const __bf16* __restrict__ x, const void* __restrict__ g,
+                                                   const float* __restrict__ stats, double* __restrict__ partial,
+                                                   long long L, int nchunk, int pre_leaky, int post_leaky,
+                                                   float alpha, const DropK& dk, const Geo ge) {
+  const DropCtx dc = drop_begin<DROP>(dk);
   const int n = blockIdx.y;
   const float* sp = stats + (long long)n * LG_NSTAT;
   const float mu = sp[0], a = sp[2], b = sp[3], mul = sp[4];
   __shared__ double sred[32];
   double s1 = 0.0, s2 = 0.0;
   constexpr int CH8 = 2 * CHUNK;  // elements per block trip (256 threads x 4 x 8)
-  for (long long c0 = (long long)blockIdx.x * CH8; c0 < L; c0 += (long long)gridDim.x * CH8) {
+  for (long long c0 = (long long)blockIdx.x * CH8; c0 < L; c0 += (long long)ge.gdx * CH8) {
     const long long base8 = ((long long)n * L + c0) / 8;
     const long long lim = L - c0;
     f32x8 xv[4], gv[4];
@@ -530,12 +669,15 @@ __global__ __launch_bounds__(256) void bwd_partial16_kernel(const __bf16* __rest
       const int e = (q * 256 + threadIdx.x) * 8;
       if (e < lim) {
         float q1 = 0.f, q2 = 0.f;
+        float dm[8];
+        if constexpr (DROP) drop_mult8(dc, (unsigned long long)(base8 + e / 8), dm);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
           float xx = k < 4 ? xv[q].lo[k & 3] : xv[q].hi[k & 3];
           if (pre_leaky) xx = lg_leaky(xx, alpha);
           const float c = (xx - mu) - mul;
           float dz = k < 4 ? gv[q].lo[k & 3] : gv[q].hi[k & 3];
+          if constexpr (DROP) dz = dz * dm[k];
           if (post_leaky) dz = (a * c + b > 0.f) ? dz : alpha * dz;
           q1 += dz;
           q2 += dz * c;
@@ -553,20 +695,35 @@ __global__ __launch_bounds__(256) void bwd_partial16_kernel(const __bf16* __rest
   }
 }
 
+template <bool G16>
+__global__ __launch_bounds__(256) void bwd_partial16_kernel(const __bf16* __restrict__ x, const void* __restrict__ g,
+                                                            const float* __restrict__ stats, double* __restrict__ partial,
+                                                            long long L, int nchunk, int pre_leaky, int post_leaky,
+                                                            float alpha) {
+  bwd_partial16_body<G16, false>(x, g, stats, partial, L, nchunk, pre_leaky, post_leaky, alpha, DropK{}, Geo{blockDim.x, gridDim.x, gridDim.y});
+}
+template <bool G16>
+__global__ __launch_bounds__(256) void bwd_partial16_drop_kernel(const __bf16* __restrict__ x, const void* __restrict__ g,
+                                                                 const float* __restrict__ stats, double* __restrict__ partial,
+                                                                 long long L, int nchunk, float alpha, DropK dk) {
+  bwd_partial16_body<G16, true>(x, g, stats, partial, L, nchunk, 0, 1, alpha, dk, Geo{blockDim.x, gridDim.x, gridDim.y});
+}
+
 // dz = a*(dy' - m1 - c*m2') from the bf16 z; DB: + column sums (bias gradient); the launch makes gridDim.x*256 a multiple
 // of C/8, so a thread meets the same 8 channels in every trip
-template <bool DB, bool G16>
-__global__ __launch_bounds__(256) void bwd_apply16_kernel(const __bf16* __restrict__ x, const void* __restrict__ g,
-                                                          const float* __restrict__ stats, const float* __restrict__ bstats,
-                                                          float* __restrict__ dx, __bf16* __restrict__ dx16, long long L8,
-                                                          long long total8, int pre_leaky, int post_leaky, float alpha,
-                                                          float* __restrict__ colpart, int C8) {
-  constexpr int UNR = DB ? DB_UNR : EW8_UNR;  // DB: the extra loads of a trip sit gridDim.x*256 units apart (same channel octet)
+template <bool DB, bool G16, bool DROP>
+__device__ __forceinline__ void bwd_apply16_body(const __bf16* __restrict__ x, const void* __restrict__ g,
+                                                 const float* __restrict__ stats, const float* __restrict__ bstats,
+                                                 float* __restrict__ dx, __bf16* __restrict__ dx16, long long L8,
+                                                 long long total8, int pre_leaky, int post_leaky, float alpha,
+                                                 float* __restrict__ colpart, int C8, const DropK& dk, const Geo ge) {
+  const DropCtx dc = drop_begin<DROP>(dk);
+  constexpr int UNR = DB ? DB_UNR : EW8_UNR;  // DB: the extra loads of a trip sit ge.gdx*256 units apart (same channel octet)
   const unsigned tot = (unsigned)total8, l8 = (unsigned)L8;
-  const unsigned ustep = DB ? gridDim.x * blockDim.x : 256u;                  // distance between a thread's units of one trip
-  const unsigned stride = DB ? gridDim.x * blockDim.x * UNR : gridDim.x * blockDim.x * UNR;
-  const unsigned rb = gridDim.x - 1 - blockIdx.x;   // from the END of the map (the block's data AND its column-sum row: results unchanged)
-  const unsigned first = DB ? rb * blockDim.x + threadIdx.x : rb * blockDim.x * UNR + threadIdx.x;
+  const unsigned ustep = DB ? ge.gdx * ge.bdx : 256u;                  // distance between a thread's units of one trip
+  const unsigned stride = DB ? ge.gdx * ge.bdx * UNR : ge.gdx * ge.bdx * UNR;
+  const unsigned rb = ge.gdx - 1 - blockIdx.x;   // from the END of the map (the block's data AND its column-sum row: results unchanged)
+  const unsigned first = DB ? rb * ge.bdx + threadIdx.x : rb * ge.bdx * UNR + threadIdx.x;
   f32x8 csum;
   csum.lo = f32x4{0.f, 0.f, 0.f, 0.f}; csum.hi = f32x4{0.f, 0.f, 0.f, 0.f};
   const int ntrip = (int)(((unsigned long long)tot + stride - 1) / stride);
@@ -589,6 +746,8 @@ __global__ __launch_bounds__(256) void bwd_apply16_kernel(const __bf16* __restri
       const float mu = sp[0], a = sp[2], b = sp[3], mul = sp[4];
       const float m1 = bstats[n * 4], m2 = bstats[n * 4 + 1], m1l = bstats[n * 4 + 2], m2l = bstats[n * 4 + 3];
       f32x8 o;
+      float dm[8];
+      if constexpr (DROP) drop_mult8(dc, i, dm);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const float x0 = k < 4 ? xs[u].lo[k & 3] : xs[u].hi[k & 3];
@@ -596,6 +755,7 @@ __global__ __launch_bounds__(256) void bwd_apply16_kernel(const __bf16* __restri
         if (pre_leaky) xx = lg_leaky(xx, alpha);
         const float c = (xx - mu) - mul;
         float dz = k < 4 ? gs[u].lo[k & 3] : gs[u].hi[k & 3];
+        if constexpr (DROP) dz = dz * dm[k];
         if (post_leaky) dz = (a * c + b > 0.f) ? dz : alpha * dz;
         float d = a * ((((dz - m1) - m1l) - c * m2) - c * m2l);
         if (pre_leaky) d = (x0 > 0.f) ? d : alpha * d;
@@ -618,6 +778,36 @@ __global__ __launch_bounds__(256) void bwd_apply16_kernel(const __bf16* __restri
       *reinterpret_cast<f32x4*>(colpart + ((long long)rb * C8 + q) * 8) = tl;
       *reinterpret_cast<f32x4*>(colpart + ((long long)rb * C8 + q) * 8 + 4) = th;
     }
+  }
+}
+
+template <bool DB, bool G16>
+__global__ __launch_bounds__(256) void bwd_apply16_kernel(const __bf16* __restrict__ x, const void* __restrict__ g,
+                                                          const float* __restrict__ stats, const float* __restrict__ bstats,
+                                                          float* __restrict__ dx, __bf16* __restrict__ dx16, long long L8,
+                                                          long long total8, int pre_leaky, int post_leaky, float alpha,
+                                                          float* __restrict__ colpart, int C8) {
+  bwd_apply16_body<DB, G16, false>(x, g, stats, bstats, dx, dx16, L8, total8, pre_leaky, post_leaky, alpha, colpart, C8, DropK{}, Geo{blockDim.x, gridDim.x, gridDim.y});
+}
+template <bool DB, bool G16>
+__global__ __launch_bounds__(256) void bwd_apply16_drop_kernel(const __bf16* __restrict__ x, const void* __restrict__ g,
+                                                               const float* __restrict__ stats, const float* __restrict__ bstats,
+                                                               float* __restrict__ dx, __bf16* __restrict__ dx16, long long L8,
+                                                               long long total8, float alpha, float* __restrict__ colpart, int C8,
+                                                               DropK dk) {
+  bwd_apply16_body<DB, G16, true>(x, g, stats, bstats, dx, dx16, L8, total8, 0, 1, alpha, colpart, C8, dk, Geo{blockDim.x, gridDim.x, gridDim.y});
+}
+
+// keep[r][e] (bytes, 1 = kept) of the rows r0 .. r0+B-1 of one (call, level) slot: the definition above made testable
+__global__ __launch_bounds__(256) void dropout_mask_kernel(unsigned char* __restrict__ keep, long long total8, DropK dk) {
+  const DropCtx dc = drop_begin<true>(dk);
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total8; i += (long long)gridDim.x * 256) {
+    float dm[8];
+    drop_mult8(dc, (unsigned long long)i, dm);
+    unsigned lo = 0, hi = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { lo |= (dm[k] != 0.f ? 1u : 0u) << (8 * k); hi |= (dm[4 + k] != 0.f ? 1u : 0u) << (8 * k); }
+    *reinterpret_cast<unsigned long long*>(keep + i * 8) = (unsigned long long)lo | ((unsigned long long)hi << 32);
   }
 }
 
@@ -681,6 +871,25 @@ inline int ew_blocks(long long total4) {
 inline size_t part_bytes(int B, long long L) { return ((size_t)B * nchunks(L) * 3 * sizeof(double) + 255) / 256 * 256; }
 inline size_t bst_bytes(int B) { return ((size_t)B * 4 * sizeof(float) + 255) / 256 * 256; }
 
+// host-side checks of a dropout launch + its kernel argument (see DropK)
+int drop_args(const char* who, const long long* key, int call, int level, int r0, int B, long long L, float rate, DropK* dk) {
+  LG_CHECK_ARG(key, "%s: null pointer (dropout key)", who);
+  LG_CHECK_ARG(L > 0 && L % 8 == 0, "%s: dropout needs L %% 8 == 0 (one Philox block per 8 elements), got L=%lld", who, L);
+  LG_CHECK_ARG(rate >= 0.f && rate < 1.f, "%s: dropout rate %g outside [0, 1)", who, (double)rate);
+  LG_CHECK_ARG(call >= 0 && call <= 3, "%s: dropout call slot %d outside 0..3", who, call);
+  LG_CHECK_ARG(level >= 1 && level <= 4, "%s: dropout level %d outside 1..4", who, level);
+  // rows r0 .. r0+B-1 must stay inside the level's window of 2^32 blocks: the next level's (and call's) masks start there
+  LG_CHECK_ARG(r0 >= 0 && B > 0 && ((unsigned long long)r0 + (unsigned long long)B) * (unsigned long long)(L / 8) <= (1ull << 32),
+               "%s: first row %d + %d rows of %lld elements leave the level's counter window", who, r0, B, L);
+  const long long T = llrint((double)rate * 65536.0);
+  LG_CHECK_ARG(T < 65536, "%s: dropout rate %g rounds to 1", who, (double)rate);
+  dk->key = reinterpret_cast<const unsigned long long*>(key);
+  dk->base = ((unsigned long long)call << 34) + ((unsigned long long)(level - 1) << 32) + (unsigned long long)r0 * (unsigned long long)(L / 8);
+  dk->T = (unsigned)T;
+  dk->scale = 65536.f / (float)(65536 - T);
+  return LG_OK;
+}
+
 }  // namespace
 
 extern "C" int lg_instnorm_stats_stride(void) { return LG_NSTAT; }
@@ -728,15 +937,32 @@ extern "C" int lg_instnorm_stats_finalize(const void* partials, int nparts, floa
 }
 
 // y = [post_leaky] (a_n * ([pre_leaky](x) - mu_n) + beta) [+ skip]
-extern "C" int lg_instnorm_leaky_apply(const float* x, const float* stats, const float* skip, float* y, void* y16, int B,
-                                       long long L, int pre_leaky, int post_leaky, float alpha, void* stream) {
+static int apply_impl(const float* x, const float* stats, const float* skip, float* y, void* y16, int B, long long L, int pre_leaky,
+                      int post_leaky, float alpha, const DropK* dk, void* stream) {
   LG_CHECK_ARG(x && stats && (y || y16), "lg_instnorm_leaky_apply: null pointer");
   LG_CHECK_ARG(B > 0 && L > 0 && L % 4 == 0 && (long long)B * L / 4 < (1LL << 31), "lg_instnorm_leaky_apply: bad shape B=%d L=%lld", B, L);
   const long long total4 = (long long)B * L / 4;
+  if (dk) {
+    hipLaunchKernelGGL(apply_drop_kernel, dim3((int)fit_rounds(ew_blocks(total4), LG_RESIDENT_BLOCKS(apply_drop_kernel), EW_MAX_BLOCKS, 1)), dim3(256), 0,
+                       (hipStream_t)stream, x, stats, y, (__bf16*)y16, L / 4, total4, alpha, *dk);
+    LG_CHECK_LAUNCH("lg_instnorm_leaky_apply_drop");
+    return LG_OK;
+  }
   hipLaunchKernelGGL(apply_kernel, dim3((int)fit_rounds(ew_blocks(total4), LG_RESIDENT_BLOCKS(apply_kernel), EW_MAX_BLOCKS, 1)), dim3(256), 0, (hipStream_t)stream, x, stats, skip, y,
                      (__bf16*)y16, L / 4, total4, pre_leaky, post_leaky, alpha);
   LG_CHECK_LAUNCH("lg_instnorm_leaky_apply");
   return LG_OK;
+}
+extern "C" int lg_instnorm_leaky_apply(const float* x, const float* stats, const float* skip, float* y, void* y16, int B,
+                                       long long L, int pre_leaky, int post_leaky, float alpha, void* stream) {
+  return apply_impl(x, stats, skip, y, y16, B, L, pre_leaky, post_leaky, alpha, nullptr, stream);
+}
+// y = LeakyReLU(a_n (x - mu_n) + beta) * keep * scale: the encoder's form with the dropout mask of (call, level), first row r0
+extern "C" int lg_instnorm_leaky_apply_drop(const float* x, const float* stats, float* y, void* y16, int B, long long L, float alpha,
+                                            const long long* key, int call, int level, int r0, float rate, void* stream) {
+  DropK dk;
+  if (int rc = drop_args("lg_instnorm_leaky_apply_drop", key, call, level, r0, B, L, rate, &dk)) return rc;
+  return apply_impl(x, stats, nullptr, y, y16, B, L, 0, 1, alpha, &dk, stream);
 }
 
 // g = dL/d(apply output before skip); writes dx = dL/dx, (accumulates) dgamma, dbeta
@@ -760,9 +986,9 @@ extern "C" int lg_instnorm_leaky_bwd(const float* x, const float* stats, const v
 
 // as lg_instnorm_leaky_bwd; db (may be null): db[C] (+)= column sums of dx viewed as [B*L/C][C] — the bias gradient of the
 // conv layer whose output x is (C = its channel count, innermost), taken in the same pass that writes dx
-extern "C" int lg_instnorm_leaky_bwd_db(const float* x, const float* stats, const void* g, int g_is_bf16, float* dx, void* dx16,
-                                        float* dgamma, float* dbeta, float* db, int C, void* workspace, size_t ws_bytes, int B,
-                                        long long L, int pre_leaky, int post_leaky, float alpha, int accumulate, void* stream) {
+static int bwd_impl(const float* x, const float* stats, const void* g, int g_is_bf16, float* dx, void* dx16,
+                    float* dgamma, float* dbeta, float* db, int C, void* workspace, size_t ws_bytes, int B,
+                    long long L, int pre_leaky, int post_leaky, float alpha, int accumulate, const DropK* dk, void* stream) {
   LG_CHECK_ARG(x && stats && g && (dx || dx16) && workspace, "lg_instnorm_leaky_bwd: null pointer");
   LG_CHECK_ARG(B > 0 && B <= 65535 && L > 0 && L % 4 == 0 && (long long)B * L / 4 < (1LL << 31),
                "lg_instnorm_leaky_bwd: bad shape B=%d L=%lld", B, L);
@@ -780,8 +1006,11 @@ extern "C" int lg_instnorm_leaky_bwd_db(const float* x, const float* stats, cons
   double* partial = (double*)ws;
   float* bstats = (float*)(ws + part_bytes(B, L));
   double* gsum = (double*)(ws + part_bytes(B, L) + bst_bytes(B));
-  hipLaunchKernelGGL(bwd_partial_kernel, dim3(nc, B), dim3(256), 0, st, x, g, g_is_bf16, stats, partial, L, nc, pre_leaky,
-                     post_leaky, alpha);
+  if (dk)
+    hipLaunchKernelGGL(bwd_partial_drop_kernel, dim3(nc, B), dim3(256), 0, st, x, g, g_is_bf16, stats, partial, L, nc, alpha, *dk);
+  else
+    hipLaunchKernelGGL(bwd_partial_kernel, dim3(nc, B), dim3(256), 0, st, x, g, g_is_bf16, stats, partial, L, nc, pre_leaky,
+                       post_leaky, alpha);
   LG_CHECK_LAUNCH("lg_instnorm_leaky_bwd(partial)");
   hipLaunchKernelGGL(bwd_final_kernel, dim3(B), dim3(64), 0, st, (const double*)partial, stats, bstats, gsum, L, nc);
   LG_CHECK_LAUNCH("lg_instnorm_leaky_bwd(final)");
@@ -792,28 +1021,51 @@ extern "C" int lg_instnorm_leaky_bwd_db(const float* x, const float* stats, cons
   }
   const long long total4 = (long long)B * L / 4;
   if (!db) {
-    hipLaunchKernelGGL(bwd_apply_kernel<false>, dim3((int)fit_rounds(ew_blocks(total4), LG_RESIDENT_BLOCKS(bwd_apply_kernel<false>), EW_MAX_BLOCKS, 1)), dim3(256), 0, st, x, g, g_is_bf16, stats,
-                       (const float*)bstats, dx, (__bf16*)dx16, L / 4, total4, pre_leaky, post_leaky, alpha, nullptr, 0);
+    if (dk)
+      hipLaunchKernelGGL(bwd_apply_drop_kernel<false>, dim3((int)fit_rounds(ew_blocks(total4), LG_RESIDENT_BLOCKS(bwd_apply_drop_kernel<false>), EW_MAX_BLOCKS, 1)), dim3(256), 0, st, x, g,
+                         g_is_bf16, stats, (const float*)bstats, dx, (__bf16*)dx16, L / 4, total4, alpha, (float*)nullptr, 0, *dk);
+    else
+      hipLaunchKernelGGL(bwd_apply_kernel<false>, dim3((int)fit_rounds(ew_blocks(total4), LG_RESIDENT_BLOCKS(bwd_apply_kernel<false>), EW_MAX_BLOCKS, 1)), dim3(256), 0, st, x, g, g_is_bf16, stats,
+                         (const float*)bstats, dx, (__bf16*)dx16, L / 4, total4, pre_leaky, post_leaky, alpha, nullptr, 0);
     LG_CHECK_LAUNCH("lg_instnorm_leaky_bwd(apply)");
     return LG_OK;
   }
   const int C4 = C / 4, unit = 256 % C4 == 0 ? 1 : 3;  // blocks per period of the thread -> channel map
+  // (the dropped twin takes its plain twin's grid: the column sums then merge in the same order)
   long long nb = fit_rounds((total4 + 255) / 256, LG_RESIDENT_BLOCKS(bwd_apply_kernel<true>), DB_MAX_BLOCKS, unit);
   float* colpart = (float*)(ws + lg_instnorm_workspace_bytes(B, L));
-  hipLaunchKernelGGL(bwd_apply_kernel<true>, dim3((int)nb), dim3(256), 0, st, x, g, g_is_bf16, stats, (const float*)bstats, dx,
-                     (__bf16*)dx16, L / 4, total4, pre_leaky, post_leaky, alpha, colpart, C4);
+  if (dk)
+    hipLaunchKernelGGL(bwd_apply_drop_kernel<true>, dim3((int)nb), dim3(256), 0, st, x, g, g_is_bf16, stats, (const float*)bstats, dx,
+                       (__bf16*)dx16, L / 4, total4, alpha, colpart, C4, *dk);
+  else
+    hipLaunchKernelGGL(bwd_apply_kernel<true>, dim3((int)nb), dim3(256), 0, st, x, g, g_is_bf16, stats, (const float*)bstats, dx,
+                       (__bf16*)dx16, L / 4, total4, pre_leaky, post_leaky, alpha, colpart, C4);
   LG_CHECK_LAUNCH("lg_instnorm_leaky_bwd_db(apply)");
   hipLaunchKernelGGL(colsum_final_kernel, dim3((C + 15) / 16), dim3(1024), 0, st, (const float*)colpart, db, (int)nb, C,
                      accumulate);
   LG_CHECK_LAUNCH("lg_instnorm_leaky_bwd_db(bias)");
   return LG_OK;
 }
+extern "C" int lg_instnorm_leaky_bwd_db(const float* x, const float* stats, const void* g, int g_is_bf16, float* dx, void* dx16,
+                                        float* dgamma, float* dbeta, float* db, int C, void* workspace, size_t ws_bytes, int B,
+                                        long long L, int pre_leaky, int post_leaky, float alpha, int accumulate, void* stream) {
+  return bwd_impl(x, stats, g, g_is_bf16, dx, dx16, dgamma, dbeta, db, C, workspace, ws_bytes, B, L, pre_leaky, post_leaky, alpha,
+                  accumulate, nullptr, stream);
+}
+// lg_instnorm_leaky_bwd_db of the encoder's form with g multiplied by the mask of (call, level), first row r0, in both passes
+extern "C" int lg_instnorm_leaky_bwd_drop(const float* x, const float* stats, const void* g, int g_is_bf16, float* dx, void* dx16,
+                                          float* dgamma, float* dbeta, float* db, int C, void* workspace, size_t ws_bytes, int B,
+                                          long long L, float alpha, int accumulate, const long long* key, int call, int level, int r0,
+                                          float rate, void* stream) {
+  DropK dk;
+  if (int rc = drop_args("lg_instnorm_leaky_bwd_drop", key, call, level, r0, B, L, rate, &dk)) return rc;
+  return bwd_impl(x, stats, g, g_is_bf16, dx, dx16, dgamma, dbeta, db, C, workspace, ws_bytes, B, L, 0, 1, alpha, accumulate, &dk, stream);
+}
 
 // ---- bf16 activation path: the same ops reading the conv output z as bf16 (see the kernels above) -------------------
 // skip (may be null): fp32, or bf16 when skip_is_bf16
-extern "C" int lg_instnorm_leaky_apply_z16(const void* z16, const float* stats, const void* skip, int skip_is_bf16, float* y,
-                                           void* y16, int B, long long L, int pre_leaky, int post_leaky, float alpha,
-                                           void* stream) {
+static int apply16_impl(const void* z16, const float* stats, const void* skip, int skip_is_bf16, float* y, void* y16, int B, long long L,
+                        int pre_leaky, int post_leaky, float alpha, const DropK* dk, void* stream) {
   LG_CHECK_ARG(z16 && stats && (y || y16), "lg_instnorm_leaky_apply_z16: null pointer");
   LG_CHECK_ARG(B > 0 && L > 0 && L % 8 == 0 && (long long)B * L / 8 < (1LL << 31),
                "lg_instnorm_leaky_apply_z16: bad shape B=%d L=%lld", B, L);
@@ -822,6 +1074,12 @@ extern "C" int lg_instnorm_leaky_apply_z16(const void* z16, const float* stats, 
   nb = fit_rounds(nb, !skip ? LG_RESIDENT_BLOCKS(apply16_kernel<0>) : !skip_is_bf16 ? LG_RESIDENT_BLOCKS(apply16_kernel<1>) : LG_RESIDENT_BLOCKS(apply16_kernel<2>), EW_MAX_BLOCKS, 1);
   hipStream_t st = (hipStream_t)stream;
   const __bf16* x = (const __bf16*)z16;
+  if (dk) {
+    nb = fit_rounds((total8 + 256 * EW8_UNR - 1) / (256 * EW8_UNR), LG_RESIDENT_BLOCKS(apply16_drop_kernel), EW_MAX_BLOCKS, 1);
+    hipLaunchKernelGGL(apply16_drop_kernel, dim3((int)nb), dim3(256), 0, st, x, stats, y, (__bf16*)y16, L / 8, total8, alpha, *dk);
+    LG_CHECK_LAUNCH("lg_instnorm_leaky_apply_z16_drop");
+    return LG_OK;
+  }
   if (!skip)
     hipLaunchKernelGGL(apply16_kernel<0>, dim3((int)nb), dim3(256), 0, st, x, stats, skip, y, (__bf16*)y16, L / 8, total8,
                        pre_leaky, post_leaky, alpha);
@@ -834,12 +1092,24 @@ extern "C" int lg_instnorm_leaky_apply_z16(const void* z16, const float* stats, 
   LG_CHECK_LAUNCH("lg_instnorm_leaky_apply_z16");
   return LG_OK;
 }
+extern "C" int lg_instnorm_leaky_apply_z16(const void* z16, const float* stats, const void* skip, int skip_is_bf16, float* y,
+                                           void* y16, int B, long long L, int pre_leaky, int post_leaky, float alpha,
+                                           void* stream) {
+  return apply16_impl(z16, stats, skip, skip_is_bf16, y, y16, B, L, pre_leaky, post_leaky, alpha, nullptr, stream);
+}
+// lg_instnorm_leaky_apply_drop reading the conv output as bf16
+extern "C" int lg_instnorm_leaky_apply_z16_drop(const void* z16, const float* stats, float* y, void* y16, int B, long long L, float alpha,
+                                                const long long* key, int call, int level, int r0, float rate, void* stream) {
+  DropK dk;
+  if (int rc = drop_args("lg_instnorm_leaky_apply_z16_drop", key, call, level, r0, B, L, rate, &dk)) return rc;
+  return apply16_impl(z16, stats, nullptr, 0, y, y16, B, L, 0, 1, alpha, &dk, stream);
+}
 
 // lg_instnorm_stats_finalize + lg_instnorm_leaky_apply_z16 in ONE launch (see apply16p_kernel): `partials` = the [B][nparts][3]
 // moment records a *_fwd_stats conv left behind; `stats` [B][8] receives the finished records (bit-identical to the two-call form)
-extern "C" int lg_instnorm_leaky_apply_z16_p(const void* z16, const void* partials, int nparts, const float* gamma, const float* beta,
-                                             float* stats, const void* skip, int skip_is_bf16, float* y, void* y16, int B,
-                                             long long L, int post_leaky, float alpha, void* stream) {
+static int apply16p_impl(const void* z16, const void* partials, int nparts, const float* gamma, const float* beta, float* stats,
+                         const void* skip, int skip_is_bf16, float* y, void* y16, int B, long long L, int post_leaky, float alpha,
+                         const DropK* dk, void* stream) {
   LG_CHECK_ARG(z16 && partials && gamma && beta && stats && (y || y16), "lg_instnorm_leaky_apply_z16_p: null pointer");
   LG_CHECK_ARG(nparts > 0 && B > 0 && B <= 65535 && L > 0 && L % 8 == 0 && L / 8 < (1LL << 31),
                "lg_instnorm_leaky_apply_z16_p: bad shape B=%d L=%lld nparts=%d", B, L, nparts);
@@ -851,7 +1121,9 @@ extern "C" int lg_instnorm_leaky_apply_z16_p(const void* z16, const void* partia
   const dim3 grid((unsigned)bps, (unsigned)B);
   const __bf16* x = (const __bf16*)z16;
   const double* pr = (const double*)partials;
-  if (!skip)
+  if (dk)
+    hipLaunchKernelGGL(apply16p_drop_kernel, grid, dim3(256), 0, st, x, pr, nparts, gamma, beta, stats, y, (__bf16*)y16, (unsigned)L8, alpha, *dk);
+  else if (!skip)
     hipLaunchKernelGGL(apply16p_kernel<0>, grid, dim3(256), 0, st, x, pr, nparts, gamma, beta, stats, skip, y, (__bf16*)y16, (unsigned)L8, post_leaky, alpha);
   else if (!skip_is_bf16)
     hipLaunchKernelGGL(apply16p_kernel<1>, grid, dim3(256), 0, st, x, pr, nparts, gamma, beta, stats, skip, y, (__bf16*)y16, (unsigned)L8, post_leaky, alpha);
@@ -859,6 +1131,19 @@ extern "C" int lg_instnorm_leaky_apply_z16_p(const void* z16, const void* partia
     hipLaunchKernelGGL(apply16p_kernel<2>, grid, dim3(256), 0, st, x, pr, nparts, gamma, beta, stats, skip, y, (__bf16*)y16, (unsigned)L8, post_leaky, alpha);
   LG_CHECK_LAUNCH("lg_instnorm_leaky_apply_z16_p");
   return LG_OK;
+}
+extern "C" int lg_instnorm_leaky_apply_z16_p(const void* z16, const void* partials, int nparts, const float* gamma, const float* beta,
+                                             float* stats, const void* skip, int skip_is_bf16, float* y, void* y16, int B,
+                                             long long L, int post_leaky, float alpha, void* stream) {
+  return apply16p_impl(z16, partials, nparts, gamma, beta, stats, skip, skip_is_bf16, y, y16, B, L, post_leaky, alpha, nullptr, stream);
+}
+// lg_instnorm_leaky_apply_z16_p (statistics finalised in the same launch) with the dropout mask
+extern "C" int lg_instnorm_leaky_apply_z16_p_drop(const void* z16, const void* partials, int nparts, const float* gamma, const float* beta,
+                                                  float* stats, float* y, void* y16, int B, long long L, float alpha,
+                                                  const long long* key, int call, int level, int r0, float rate, void* stream) {
+  DropK dk;
+  if (int rc = drop_args("lg_instnorm_leaky_apply_z16_p_drop", key, call, level, r0, B, L, rate, &dk)) return rc;
+  return apply16p_impl(z16, partials, nparts, gamma, beta, stats, nullptr, 0, y, y16, B, L, 1, alpha, &dk, stream);
 }
 
 extern "C" int lg_instnorm_leaky_bwd_z16_p(const void* z16, const float* stats, const void* g, int g_is_bf16, float* dx,
@@ -875,11 +1160,12 @@ extern "C" int lg_instnorm_leaky_bwd_z16(const void* z16, const float* stats, co
 }
 // partials / nparts_in (optional): the per-sample sums {sum g', sum g' c} as [B][nparts_in][2] doubles, already produced by
 // the epilogue of the conv that wrote g (lg_conv2d_s2_dgrad_nf, ...): the first (partial-sums) pass over z and g is skipped
-extern "C" int lg_instnorm_leaky_bwd_z16_p(const void* z16, const float* stats, const void* g, int g_is_bf16, float* dx,
-                                           void* dx16, float* dgamma, float* dbeta, float* db, int C, const void* partials,
-                                           int nparts_in, void* workspace, size_t ws_bytes, int B, long long L, int pre_leaky,
-                                           int post_leaky, float alpha, int accumulate, void* stream) {
+static int bwd16_impl(const void* z16, const float* stats, const void* g, int g_is_bf16, float* dx, void* dx16, float* dgamma, float* dbeta,
+                      float* db, int C, const void* partials, int nparts_in, void* workspace, size_t ws_bytes, int B, long long L,
+                      int pre_leaky, int post_leaky, float alpha, int accumulate, const DropK* dk, void* stream) {
   LG_CHECK_ARG(z16 && stats && g && (dx || dx16) && workspace, "lg_instnorm_leaky_bwd_z16: null pointer");
+  // producer-fused sums are those of the UNMASKED gradient: with a mask they are right only when it keeps everything (T = 0)
+  LG_CHECK_ARG(!(dk && partials && nparts_in > 0 && dk->T != 0), "lg_instnorm_leaky_bwd_z16_drop: fused partial sums know no dropout mask");
   LG_CHECK_ARG(B > 0 && B <= 65535 && L > 0 && L % 8 == 0 && (long long)B * L / 8 < (1LL << 31),
                "lg_instnorm_leaky_bwd_z16: bad shape B=%d L=%lld", B, L);
   LG_CHECK_ARG(ws_bytes >= lg_instnorm_workspace_bytes(B, L), "lg_instnorm_leaky_bwd_z16: workspace too small");
@@ -906,7 +1192,11 @@ extern "C" int lg_instnorm_leaky_bwd_z16_p(const void* z16, const float* stats, 
     partial = (double*)partials;
     nc = nparts_in;
   } else {
-    if (g_is_bf16)
+    if (dk && g_is_bf16)
+      hipLaunchKernelGGL(bwd_partial16_drop_kernel<true>, dim3(nc, B), dim3(256), 0, st, x, g, stats, partial, L, nc, alpha, *dk);
+    else if (dk)
+      hipLaunchKernelGGL(bwd_partial16_drop_kernel<false>, dim3(nc, B), dim3(256), 0, st, x, g, stats, partial, L, nc, alpha, *dk);
+    else if (g_is_bf16)
       hipLaunchKernelGGL(bwd_partial16_kernel<true>, dim3(nc, B), dim3(256), 0, st, x, g, stats, partial, L, nc, pre_leaky,
                          post_leaky, alpha);
     else
@@ -923,8 +1213,17 @@ extern "C" int lg_instnorm_leaky_bwd_z16_p(const void* z16, const float* stats, 
   const long long total8 = (long long)B * L / 8;
   if (!db) {
     long long nb = (total8 + 256 * EW8_UNR - 1) / (256 * EW8_UNR);
-    nb = fit_rounds(nb, g_is_bf16 ? LG_RESIDENT_BLOCKS((bwd_apply16_kernel<false, true>)) : LG_RESIDENT_BLOCKS((bwd_apply16_kernel<false, false>)), EW_MAX_BLOCKS, 1);
-    if (g_is_bf16)
+    if (dk)
+      nb = fit_rounds(nb, g_is_bf16 ? LG_RESIDENT_BLOCKS((bwd_apply16_drop_kernel<false, true>)) : LG_RESIDENT_BLOCKS((bwd_apply16_drop_kernel<false, false>)), EW_MAX_BLOCKS, 1);
+    else
+      nb = fit_rounds(nb, g_is_bf16 ? LG_RESIDENT_BLOCKS((bwd_apply16_kernel<false, true>)) : LG_RESIDENT_BLOCKS((bwd_apply16_kernel<false, false>)), EW_MAX_BLOCKS, 1);
+    if (dk && g_is_bf16)
+      hipLaunchKernelGGL((bwd_apply16_drop_kernel<false, true>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
+                         (__bf16*)dx16, L / 8, total8, alpha, (float*)nullptr, 0, *dk);
+    else if (dk)
+      hipLaunchKernelGGL((bwd_apply16_drop_kernel<false, false>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
+                         (__bf16*)dx16, L / 8, total8, alpha, (float*)nullptr, 0, *dk);
+    else if (g_is_bf16)
       hipLaunchKernelGGL((bwd_apply16_kernel<false, true>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
                          (__bf16*)dx16, L / 8, total8, pre_leaky, post_leaky, alpha, (float*)nullptr, 0);
     else
@@ -937,7 +1236,14 @@ extern "C" int lg_instnorm_leaky_bwd_z16_p(const void* z16, const float* stats, 
   long long nb = (total8 + 511) / 512;   // two units per thread per trip
   nb = fit_rounds(nb, g_is_bf16 ? LG_RESIDENT_BLOCKS((bwd_apply16_kernel<true, true>)) : LG_RESIDENT_BLOCKS((bwd_apply16_kernel<true, false>)), DB_MAX_BLOCKS, unit);
   float* colpart = (float*)(ws + lg_instnorm_workspace_bytes(B, L));   // [nb][C] floats, nb <= DB_MAX_BLOCKS (+2)
-  if (g_is_bf16)
+  // (the dropped twins take their plain twins' grid: the column sums then merge in the same order)
+  if (dk && g_is_bf16)
+    hipLaunchKernelGGL((bwd_apply16_drop_kernel<true, true>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
+                       (__bf16*)dx16, L / 8, total8, alpha, colpart, C8, *dk);
+  else if (dk)
+    hipLaunchKernelGGL((bwd_apply16_drop_kernel<true, false>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
+                       (__bf16*)dx16, L / 8, total8, alpha, colpart, C8, *dk);
+  else if (g_is_bf16)
     hipLaunchKernelGGL((bwd_apply16_kernel<true, true>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
                        (__bf16*)dx16, L / 8, total8, pre_leaky, post_leaky, alpha, colpart, C8);
   else
@@ -947,6 +1253,51 @@ extern "C" int lg_instnorm_leaky_bwd_z16_p(const void* z16, const float* stats, 
   hipLaunchKernelGGL(colsum_final_kernel, dim3((C + 15) / 16), dim3(1024), 0, st, (const float*)colpart, db, (int)nb, C,
                      accumulate);
   LG_CHECK_LAUNCH("lg_instnorm_leaky_bwd_z16(bias)");
+  return LG_OK;
+}
+extern "C" int lg_instnorm_leaky_bwd_z16_p(const void* z16, const float* stats, const void* g, int g_is_bf16, float* dx,
+                                           void* dx16, float* dgamma, float* dbeta, float* db, int C, const void* partials,
+                                           int nparts_in, void* workspace, size_t ws_bytes, int B, long long L, int pre_leaky,
+                                           int post_leaky, float alpha, int accumulate, void* stream) {
+  return bwd16_impl(z16, stats, g, g_is_bf16, dx, dx16, dgamma, dbeta, db, C, partials, nparts_in, workspace, ws_bytes, B, L, pre_leaky,
+                    post_leaky, alpha, accumulate, nullptr, stream);
+}
+// lg_instnorm_leaky_bwd_drop reading the conv output as bf16.  partials / nparts_in as lg_instnorm_leaky_bwd_z16_p: accepted only
+// where the mask keeps everything (rate rounds to T = 0) — producer-fused sums are those of the unmasked gradient
+extern "C" int lg_instnorm_leaky_bwd_z16_drop(const void* z16, const float* stats, const void* g, int g_is_bf16, float* dx, void* dx16,
+                                              float* dgamma, float* dbeta, float* db, int C, const void* partials, int nparts_in,
+                                              void* workspace, size_t ws_bytes, int B, long long L, float alpha, int accumulate,
+                                              const long long* key, int call, int level, int r0, float rate, void* stream) {
+  DropK dk;
+  if (int rc = drop_args("lg_instnorm_leaky_bwd_z16_drop", key, call, level, r0, B, L, rate, &dk)) return rc;
+  return bwd16_impl(z16, stats, g, g_is_bf16, dx, dx16, dgamma, dbeta, db, C, partials, nparts_in, workspace, ws_bytes, B, L, 0, 1, alpha,
+                    accumulate, &dk, stream);
+}
+
+__global__ void dropout_key_kernel(unsigned long long* __restrict__ key, unsigned long long seed, unsigned long long key_offset) {
+  if (threadIdx.x == 0) { key[0] = seed; key[1] = key_offset; }
+}
+// key[2] = {seed, key_offset} written on the device from launch scalars: the step's key without a host-to-device copy (no sync)
+extern "C" int lg_dropout_key(long long* key, unsigned long long seed, unsigned long long key_offset, void* stream) {
+  LG_CHECK_ARG(key && ((uintptr_t)key & 7) == 0, "lg_dropout_key: null or misaligned pointer");
+  hipLaunchKernelGGL(dropout_key_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<unsigned long long*>(key), seed, key_offset);
+  LG_CHECK_LAUNCH("lg_dropout_key");
+  return LG_OK;
+}
+
+// keep[B][L] bytes (1 = kept) of the rows r0 .. r0+B-1 of the (call, level) slot under `key` = device {seed, key_offset}
+extern "C" int lg_dropout_mask(const long long* key, int call, int level, int r0, int B, long long L, float rate, unsigned char* keep,
+                               void* stream) {
+  LG_CHECK_ARG(keep, "lg_dropout_mask: null pointer");
+  LG_CHECK_ARG(((uintptr_t)keep & 7) == 0, "lg_dropout_mask: keep must be 8-byte aligned (8 decisions per store)");
+  LG_CHECK_ARG(B > 0 && L > 0 && (long long)B * L / 8 < (1LL << 31), "lg_dropout_mask: bad shape B=%d L=%lld", B, L);
+  DropK dk;
+  if (int rc = drop_args("lg_dropout_mask", key, call, level, r0, B, L, rate, &dk)) return rc;
+  const long long total8 = (long long)B * L / 8;
+  long long nb = (total8 + 255) / 256;
+  if (nb > EW_MAX_BLOCKS) nb = EW_MAX_BLOCKS;
+  hipLaunchKernelGGL(dropout_mask_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, keep, total8, dk);
+  LG_CHECK_LAUNCH("lg_dropout_mask");
   return LG_OK;
 }
 

@@ -57,6 +57,16 @@ class EagerTrainer:
         self.device = generator.device
         # gradient penalty on the disc tape (the reference raises here, eager_trainer.py:141-143; definition: DESIGN.md §12)
         self.use_gp = bool(getattr(args, "use_gp", False))
+        # live encoder dropout (the reference's dropout is the identity, model.py:25): on when dropout_train is set
+        # and 0 < dropout_rate < 1.  dropout_rate == 0 under dropout_train keeps the whole plumbing (key, call slots, the dropped
+        # kernels) with masks that keep everything: bit-identical to the feature off (tests/test_dropout_gpu.py)
+        self.dropout_rate = float(getattr(args, "dropout_rate", 0.0))
+        self.dropout = bool(getattr(args, "dropout_train", False))
+        if self.dropout and not 0.0 <= self.dropout_rate < 1.0:
+            raise ValueError(f"dropout_train needs 0 <= dropout_rate < 1, got {self.dropout_rate}")
+        if self.dropout and self.use_gp:
+            raise ValueError("use_gp and dropout_train exclude each other: the penalty's double backward through a masked norm "
+                             "is not built (DESIGN.md §15)")
         self.store = ParamStore(generator, discriminator, adjuster)
         # tf.compat.v1.train.AdamOptimizer x3 (eager_trainer.py:28-30): {beta1_power, beta2_power} per optimizer
         self.opt_cfg = {"G": (args.lr, args.beta_1, args.beta_2), "D": (args.lr, args.beta_1, args.beta_2),
@@ -87,7 +97,8 @@ class EagerTrainer:
     # ------------------------------------------------------------------ hot path
     def train_step_from_inputs(self, batch_no: int, inp: Dict[str, torch.Tensor]):
         """inp: real_image_1, real_cond_1, real_image_2, real_cond_2, noise, new_image (device fp32, NHWC); with use_gp also
-        gp_eps [B] (the penalty's interpolation weights, U[0,1)).
+        gp_eps [B] (the penalty's interpolation weights, U[0,1)); with dropout_train also dropout_key (int64 [2] = {seed, key_offset} of
+        the step's mask stream, draw_dropout_key).
         Returns (fake_image, adj_image|None, gen_loss, disc_loss, adj_loss|None) — losses are 1-element device tensors
         (no host sync on the hot path)."""
         a = self.args
@@ -99,6 +110,14 @@ class EagerTrainer:
         gp_eps = inp.get("gp_eps") if self.use_gp else None
         if self.use_gp and gp_eps is None:
             raise ValueError("train_step_from_inputs: use_gp is on and inp has no 'gp_eps' ([B] fp32 device tensor, U[0,1))")
+        # dropout call slots of the step's encoder passes: 0 = D on [new_image ; fake], 1 = the Adjuster's own pass on img1,
+        # 2 = D on the Adjuster's output.  The key is a device tensor: a captured graph replays with the masks of its step.
+        drop = [None, None, None]
+        if self.dropout:
+            if inp.get("dropout_key") is None:
+                raise ValueError("train_step_from_inputs: dropout_train is on and inp has no 'dropout_key' (int64 [2] device tensor "
+                                 "{seed, key_offset}: draw_dropout_key)")
+            drop = [ops.Drop(inp["dropout_key"], call, rate=self.dropout_rate) for call in range(3)]
 
         # ---- forward: fake = G(noise, c2); D on the [new_image ; fake] batch (eager_trainer.py:134-137)
         ctx_g: dict = {}
@@ -118,7 +137,7 @@ class EagerTrainer:
         ctx_d: dict = {}
         run_adj = bool(a.train_adj and batch_no > 10)
         # the Adjuster reuses D's encoder maps of `fake` as its skip inputs: keep the fp32 maps only then
-        p = D.forward_packed(d_in, ctx_d, keep_maps=run_adj)  # [2B, 1+c]: rows [0,B) real, [B,2B) fake
+        p = D.forward_packed(d_in, ctx_d, keep_maps=run_adj, drop=drop[0])  # [2B, 1+c]: rows [0,B) real, [B,2B) fake
 
         # ---- disc tape (eager_trainer.py:139,145): 2*BCE(c1,real_c) + BCE(.98,real_pr) + BCE(.02,fake_pr)
         dz = torch.empty(2 * B, 1 + c, dtype=torch.float32, device=self.device)
@@ -152,10 +171,11 @@ class EagerTrainer:
             ctx_a: dict = {}
             # encoder(fake) was computed by D above with the same weights: hand its 4 maps to the Adjuster
             tails = [m[B:] for m in ctx_d["enc_maps"]]  # fp32 maps (f32 path) / bf16 mirrors + the fp32 top map (bf16 path)
-            # Adjuster input = [img1 ; fake]: with the encoder maps of `fake` handed over, only img1 is encoded here
-            adj_image = A([img1, adj_in_cond], ctx_a, enc_tails=tails)
+            # Adjuster input = [img1 ; fake]: with the encoder maps of `fake` handed over, only img1 is encoded here (dropout: the
+            # handed-over maps keep the masks call 0 drew for them — no tape differentiates through the skips)
+            adj_image = A([img1, adj_in_cond], ctx_a, enc_tails=tails, drop=drop[1])
             ctx_d2: dict = {}
-            p_a = D.forward_packed(adj_image, ctx_d2, keep_maps=False, top_only=True)
+            p_a = D.forward_packed(adj_image, ctx_d2, keep_maps=False, top_only=True, drop=drop[2])
             dz_a = torch.empty(2 * B, 1 + c, dtype=torch.float32, device=self.device)
             ops.bce_heads_loss(p_a, adj_t_cond, soft(1.0), 1.0, 1.0, self.losses["adj"], dz_a, False)
             g_adj = D.backward(ctx_d2, dz_a, need_wgrad=False, need_input_grad=True)
@@ -258,6 +278,8 @@ class EagerTrainer:
                    real_cond_2=real_cond_2, noise=noise, new_image=new_image, disc_input=d_in)
         if self.use_gp:
             inp["gp_eps"] = self.draw_gp_eps(real_image_1.shape[0])
+        if self.dropout:
+            inp["dropout_key"] = self.draw_dropout_key()
         fake, adj, lg, ld, la = self.train_step_from_inputs(batch_no, inp)
         return True, fake, adj, lg, ld, la
 
@@ -283,6 +305,8 @@ class EagerTrainer:
                    real_cond_2=real_cond_2, noise=noise, new_image=new_image, disc_input=d_in)
         if self.use_gp:
             inp["gp_eps"] = self.draw_gp_eps(B)
+        if self.dropout:
+            inp["dropout_key"] = self.draw_dropout_key()
         fake, adj, lg, ld, la = self.train_step_from_inputs(batch_no, inp)
         return True, fake, adj, lg, ld, la
 
@@ -320,6 +344,18 @@ class EagerTrainer:
         block window at 2^37 of that step's counter window (no other draw of a step uses it), on the device."""
         seed = (int(getattr(self.args, "seed", 0)) << 20) ^ self.rank
         return ops.gp_draw_eps(B, seed, (self._input_step << 40) + (1 << 37), device=self.device)
+
+    def dropout_key_words(self):
+        """(seed, key_offset) of the dropout masks of the step draw_step_inputs last drew for: the block window at 2^36 of that step's
+        counter window (0, 2^39, 2^38 and 2^37 are the other draws').  input_step is part of the checkpoint, so a resumed run
+        continues the mask stream."""
+        seed = (int(getattr(self.args, "seed", 0)) << 20) ^ self.rank
+        return seed, (self._input_step << 40) + (1 << 36)
+
+    def draw_dropout_key(self):
+        """dropout_key_words as the int64 [2] device tensor the norm kernels read, written on the device from launch scalars
+        (lg_dropout_key): like the other draws of the step, no host-to-device copy and no host synchronisation."""
+        return ops.dropout_key(*self.dropout_key_words(), device=self.device)
 
     # ------------------------------------------------------------------ eager_trainer.py:180-229
     def _interrupted(self, signum, f_name):

@@ -103,7 +103,10 @@ class _ConvStack(_Module):
 
 
 class Encoder(_ConvStack):
-    """model.py:6-27.  conv_i: Conv2D(conv_filter[4-i], 5, 2, 'same') -> InstanceNorm -> leaky -> dropout(identity)."""
+    """model.py:6-27.  conv_i: Conv2D(conv_filter[4-i], 5, 2, 'same') -> InstanceNorm -> leaky -> dropout.
+    The reference's dropout is the identity (model.py:25 calls it without training=True) and so is this one unless the caller hands
+    a drop context over (the training step under dropout_train): then every level is
+    h_i = LeakyReLU(InstanceNorm(conv_i(x))) * keep * scale, the mask regenerated inside the norm passes."""
 
     def __init__(self, args):
         cf = args.conv_filter
@@ -117,7 +120,8 @@ class Encoder(_ConvStack):
     def _bias_dim(cb, cs):
         return cs
 
-    def __call__(self, inputs, ctx: Optional[dict] = None, tails=None, keep_maps: bool = True, top_only: bool = False):
+    def __call__(self, inputs, ctx: Optional[dict] = None, tails=None, keep_maps: bool = True, top_only: bool = False,
+                 drop: Optional[ops.Drop] = None):
         """Returns the 4 maps (model.py:27).  f32 path: fp32 tensors.  bf16 path: maps 1-3 are the bf16 mirrors the next
         conv reads anyway (they are also what the Adjuster's decoder adds as skips), map 4 (8x8, heads input) is fp32;
         the raw conv outputs z are kept in HBM as bf16 only (moments from the fp32 accumulators of the conv epilogue).
@@ -129,7 +133,10 @@ class Encoder(_ConvStack):
         top_only (bf16 path): the caller reads the LAST map only and no tape will ask this pass for a weight gradient (D on the
         Adjuster's output, eager_trainer.py:158-160) — the normalised maps 1-3 then have one reader, the next conv, and where its
         kernel can normalise while it stages (ops.conv2d_s2_fwd_stats_zn) they are never written: outs[i] is None there and the
-        context holds no x / x16 for the level above.  Bit-identical results."""
+        context holds no x / x16 for the level above.  Bit-identical results.
+        drop (ops.Drop naming the step's key and this pass's call slot; `inputs` are rows 0.. of the call's batch): the 4 maps are
+        post-dropout, and the context records each level's drop context — backward() reads it there and nowhere else, so it cannot
+        disagree with the forward.  The fused route of top_only knows no mask: with an active one every level runs its apply pass."""
         x = inputs
         a = self.args.leaky_alpha
         packs = self.packs()
@@ -137,8 +144,9 @@ class Encoder(_ConvStack):
         saved = []
         m16 = self.dtype == DT_BF16  # bf16 MFMA path: keep a bf16 mirror of every conv input (the operand image)
         x16 = None
-        if top_only and (tails is not None or not m16):
+        if top_only and (tails is not None or not m16 or (drop is not None and drop.active)):
             top_only = False
+        drops = [drop.at(level=i, r0=0) for i in range(1, 5)] if drop is not None else None
         raw = None   # (z, stats) of the level below when its apply pass was left out
         for i, (cb, cs) in enumerate(self.chans, 1):
             gm, bt = self._w[f"norm{i}.gamma"], self._w[f"norm{i}.beta"]
@@ -165,18 +173,20 @@ class Encoder(_ConvStack):
                 # skip add) and inputs of shapes only the per-tap gather kernel covers
                 need32 = i == 4 or not ops.conv_halo_supported(0, self.dtype, z.shape[0], z.shape[1] // 2, z.shape[2] // 2, cs,
                                                                self.chans[i][1])
-                h = ops.instnorm_apply(z, st, None, 0, 1, a, out16=h16, want_f32=need32)   # (finishes deferred moments itself)
+                h = ops.instnorm_apply(z, st, None, 0, 1, a, out16=h16, want_f32=need32,   # (finishes deferred moments itself)
+                                       drop=drops[i - 1] if drops else None)
                 st = ops.stats_tensor(st)
                 m = h if i == 4 else h16
             else:
                 h16 = None
-                h = m = ops.instnorm_apply(z, st, None, 0, 1, a)
+                h = m = ops.instnorm_apply(z, st, None, 0, 1, a, drop=drops[i - 1] if drops else None)
             outs.append(m if tails is None else (m, tails[i - 1]))  # pair (own part, tail): no concatenated copy is made
             saved.append((x, z, st, x16))
             x, x16, raw = h, h16, None
         if ctx is not None:
             ctx["enc"] = saved
             ctx["enc_maps"] = outs
+            ctx["enc_drop"] = drops
         return outs
 
     def backward(self, ctx, g_last, need_wgrad: bool, need_input_grad: bool, rows: Optional[slice] = None,
@@ -185,9 +195,19 @@ class Encoder(_ConvStack):
         rows: restrict to a batch slice of the recorded context (the fake half of a [real;fake] batch).
         wgrad_levels (with need_wgrad): the levels (1..4) whose 4 weights are differentiated — a partition step
         (eager_trainer.py:104-113) trains one weight group only, and like the reference's tape.gradient the chain then
-        stops at the lowest level anything is asked of."""
+        stops at the lowest level anything is asked of.
+        A forward recorded with a drop context is differentiated through its masks: the gradient arriving at a level's output is
+        multiplied by the same keep * scale (rows: the masks of exactly those rows) inside both passes of the norm backward.  The
+        producer-fused first-pass sums are those of the unmasked gradient: with an active mask that pass runs on its own."""
         a = self.args.leaky_alpha
         packs = self.packs()
+        drops = ctx.get("enc_drop")
+        r0 = 0
+        if drops is not None and rows is not None:
+            r0, _, step = rows.indices(ctx["enc"][0][1].shape[0])
+            if step != 1:
+                raise ValueError("Encoder.backward: contiguous row ranges only")
+        masked = drops is not None and drops[0].active
         g_h = g_last
         levels = set(range(1, 5)) if (need_wgrad and wgrad_levels is None) else (set(wgrad_levels or ()) if need_wgrad else set())
         lowest = 1 if need_input_grad else (min(levels) if levels else 5)
@@ -220,7 +240,7 @@ class Encoder(_ConvStack):
                 dz16 = torch.empty(z.shape, dtype=torch.bfloat16, device=z.device) if drop32 else None
             dz = ops.instnorm_bwd(z, st, g_h, dgm, dbt, 0, 1, a, out16=dz16, want_f32=not drop32,
                                   db=self._g[f"conv{i}.bias"] if need_wgrad else None,  # bias gradient = column sums of dz
-                                  partials=nfp)
+                                  partials=nfp, drop=drops[i - 1].at(r0=r0) if drops is not None else None)
             nfp = None
             if need_wgrad:
                 ops.conv2d_s2_wgrad(x, dz, self._g[f"conv{i}.kernel"], False, self.dtype, x16=x16, dy16=dz16)
@@ -228,7 +248,7 @@ class Encoder(_ConvStack):
             # gradient of level 1 is fp32 (consumed by the loss / tanh backward)
             if not want_dx:
                 g_h = None
-            elif m16 and i > 1 and drop32 and i - 1 >= lowest:
+            elif m16 and i > 1 and drop32 and i - 1 >= lowest and not masked:
                 # bf16 path: the conv that writes the gradient of level i-1 also adds up the first-pass sums of that level's
                 # norm backward (its z and statistics are at hand) where the kernel covers the shape
                 zl, stl = ctx["enc"][i - 2][1], ctx["enc"][i - 2][2]
@@ -607,9 +627,11 @@ class Discriminator(_Module):
     def weights(self):
         return self.encoder.weights + [self._w[n] for n in self._names]
 
-    def forward_packed(self, image, ctx: Optional[dict] = None, keep_maps: bool = True, top_only: bool = False):
-        """top_only: no weight gradient will be asked of this pass and only the heads read the encoder (see Encoder.__call__)."""
-        outs = self.encoder(image, ctx, keep_maps=keep_maps, top_only=top_only)
+    def forward_packed(self, image, ctx: Optional[dict] = None, keep_maps: bool = True, top_only: bool = False,
+                       drop: Optional[ops.Drop] = None):
+        """top_only: no weight gradient will be asked of this pass and only the heads read the encoder (see Encoder.__call__).
+        drop: the encoder's drop context of this pass (training step only; backward() finds it in ctx)."""
+        outs = self.encoder(image, ctx, keep_maps=keep_maps, top_only=top_only, drop=drop)
         x = outs[3].view(image.shape[0], -1)
         p = ops.heads_fwd(x, self._w["dense_pr.kernel"], self._w["dense_pr.bias"], self._w["dense_cond.kernel"],
                           self._w["dense_cond.bias"])
@@ -688,14 +710,16 @@ class Adjuster(_Module):
     def weights(self):
         return self.encoder.weights + self._dn.weights + self.decoder.weights + self.conv.weights
 
-    def __call__(self, inputs, ctx: Optional[dict] = None, enc_tails=None):
+    def __call__(self, inputs, ctx: Optional[dict] = None, enc_tails=None, drop: Optional[ops.Drop] = None):
+        """drop: the drop context of the Adjuster's own encoder pass (training step only).  Handed-over enc_tails keep the masks
+        the pass that produced them drew: no tape differentiates through the skips, so only the masks' marginals matter."""
         image, cond = inputs
         if enc_tails is None:
-            enc = self.encoder(image)  # no context: no tape of the step differentiates through it
+            enc = self.encoder(image, drop=drop)  # no context: no tape of the step differentiates through it
         else:  # the trailing samples of `image` were already encoded by D in this step (same weights): reuse
             # `image` holds the leading samples only (or the whole batch: then its trailing rows are the ones already encoded)
             own = cond.shape[0] - enc_tails[0].shape[0]
-            enc = self.encoder(image[:own], None, tails=enc_tails)
+            enc = self.encoder(image[:own], None, tails=enc_tails, drop=drop)
         # the decoder's first skip (the encoder's top map, model.py:131-135) is added by the dense-norm apply launch
         c4 = self._dn(cond, ctx, skip=enc[3], want16=self.dtype == DT_BF16)
         # the Adjuster's tape differentiates dense + norm only (eager_trainer.py:51,62,163): nothing ever reads the decoder's

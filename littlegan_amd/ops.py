@@ -502,9 +502,67 @@ def _chk16(t, like, name):
     return t
 
 
-def instnorm_apply(x, stats, skip, pre_leaky, post_leaky, alpha, out=None, out16=None, want_f32=True):
+class Drop:
+    """Dropout context of one encoder norm pass: `key` = the int64 [2] device tensor {seed, key_offset} of the step
+    (a step input, like gp_eps), the call slot of the encoder pass within the step, the encoder level (1..4), the row the first
+    sample of the tensor at hand has in that call's batch, and the rate.  The forward apply multiplies its output by keep * scale,
+    the backward the arriving gradient; both regenerate the mask from these five values alone."""
+    __slots__ = ("key", "call", "level", "r0", "rate")
+
+    def __init__(self, key, call, level=1, r0=0, rate=0.5):
+        if not (isinstance(key, torch.Tensor) and key.is_cuda and key.dtype == torch.int64 and key.numel() == 2 and key.is_contiguous()):
+            raise ValueError("Drop: key must be a contiguous int64 CUDA tensor {seed, key_offset}")
+        self.key, self.call, self.level, self.r0, self.rate = key, int(call), int(level), int(r0), float(rate)
+
+    def at(self, level=None, r0=None):
+        return Drop(self.key, self.call, self.level if level is None else level, self.r0 if r0 is None else r0, self.rate)
+
+    @property
+    def threshold(self):
+        """T = round(rate * 65536) as the library rounds it (the rate crosses the C ABI as a float)"""
+        import ctypes
+        return int(round(ctypes.c_float(self.rate).value * 65536.0))
+
+    @property
+    def active(self):
+        """False: the mask keeps everything (T == 0) and the pass is bit-identical to its plain twin"""
+        return self.threshold > 0
+
+    def _args(self):
+        return (_p(self.key), self.call, self.level, self.r0, self.rate)
+
+
+def _chk_drop(drop, what, skip, pre_leaky, post_leaky, Ln):
+    if skip is not None or pre_leaky or not post_leaky:
+        raise ValueError(f"{what}: dropout exists for the encoder's form only (no skip operand, pre_leaky=0, post_leaky=1)")
+    if Ln % 8:
+        raise ValueError(f"{what}: dropout needs a multiple of 8 elements per sample (one Philox block per 8 elements), got {Ln}")
+
+
+def dropout_key(seed, key_offset, device="cuda", out=None):
+    """The step's dropout key {seed, key_offset} as the int64 [2] device tensor the norm kernels read, written by a one-block
+    kernel from launch scalars: no host-to-device copy, so the host does not wait for the stream."""
+    if out is None:
+        out = torch.empty(2, dtype=torch.int64, device=device)
+    if not (out.is_cuda and out.dtype == torch.int64 and out.numel() == 2 and out.is_contiguous()):
+        raise ValueError("dropout_key: out must be a contiguous int64 CUDA tensor of 2 elements")
+    check(_lib.load().lg_dropout_key(_p(out), _i64(seed), _i64(key_offset), _stream()), "lg_dropout_key")
+    return out
+
+
+def dropout_mask(key, call, level, r0, B, L, rate):
+    """keep [B, L] uint8 (1 = kept) of rows r0 .. r0+B-1 of the (call, level) slot: the mask definition, for tests and debugging"""
+    d = Drop(key, call, level, r0, rate)
+    keep = torch.empty(B, L, dtype=torch.uint8, device=key.device)
+    check(_lib.load().lg_dropout_mask(_p(key), d.call, d.level, d.r0, B, L, d.rate, _p(keep), _stream()), "lg_dropout_mask")
+    return keep
+
+
+def instnorm_apply(x, stats, skip, pre_leaky, post_leaky, alpha, out=None, out16=None, want_f32=True, drop=None):
     """want_f32=False: only the bf16 mirror out16 is written (returns None).
-    x may be the bf16 conv output of the bf16 activation path (then skip may be bf16 too)."""
+    x may be the bf16 conv output of the bf16 activation path (then skip may be bf16 too).
+    drop (ops.Drop, optional): the output is multiplied by the dropout mask's keep * scale (encoder form only); without it the code
+    path and the launches are exactly the plain ones."""
     B = x.shape[0]
     Ln = x.numel() // B
     x_is16 = x.dtype == torch.bfloat16
@@ -514,6 +572,8 @@ def instnorm_apply(x, stats, skip, pre_leaky, post_leaky, alpha, out=None, out16
             raise ValueError("instnorm_apply: a bf16 input needs a multiple of 8 elements per sample")
     else:
         _chk(x, name="x")
+    if drop is not None:
+        _chk_drop(drop, "instnorm_apply", skip, pre_leaky, post_leaky, Ln)
     pend = None   # unfinished moments (Moments / a row range of them): finished inside the apply launch where the kernel exists
     if isinstance(stats, (Moments, _MomentRows)):
         mrows = stats if isinstance(stats, _MomentRows) else _MomentRows(stats, 0, stats.B)
@@ -545,6 +605,21 @@ def instnorm_apply(x, stats, skip, pre_leaky, post_leaky, alpha, out=None, out16
         _chk(out, x.shape, "out")
     if out16 is not None:
         _chk16(out16, x, "out16")
+    if drop is not None:
+        lib = _lib.load()
+        if pend is not None:
+            m = pend.m
+            part = m.ws.data_ptr() + pend.lo * m.nparts * 3 * 8
+            check(lib.lg_instnorm_leaky_apply_z16_p_drop(_p(x), part, m.nparts, _p(m.gamma), _p(m.beta), _p(stats), _p(out), _p(out16), B, Ln,
+                                                         float(alpha), *drop._args(), _stream()), "lg_instnorm_leaky_apply_z16_p_drop")
+            m.covered += B
+        elif x_is16:
+            check(lib.lg_instnorm_leaky_apply_z16_drop(_p(x), _p(stats), _p(out), _p(out16), B, Ln, float(alpha), *drop._args(), _stream()),
+                  "lg_instnorm_leaky_apply_z16_drop")
+        else:
+            check(lib.lg_instnorm_leaky_apply_drop(_p(x), _p(stats), _p(out), _p(out16), B, Ln, float(alpha), *drop._args(), _stream()),
+                  "lg_instnorm_leaky_apply_drop")
+        return out
     if pend is not None:
         m = pend.m
         part = m.ws.data_ptr() + pend.lo * m.nparts * 3 * 8
@@ -563,11 +638,13 @@ def instnorm_apply(x, stats, skip, pre_leaky, post_leaky, alpha, out=None, out16
 
 
 def instnorm_bwd(x, stats, g, dgamma, dbeta, pre_leaky, post_leaky, alpha, accumulate=False, out=None, out16=None,
-                 want_f32=True, db=None, partials=None):
+                 want_f32=True, db=None, partials=None, drop=None):
     """g may be fp32 or bf16 (as written by a bf16 data-gradient conv); x fp32, or the bf16 conv output of the bf16
     activation path.  Returns the fp32 dx (or None if want_f32 is False, in which case only the bf16 mirror out16 is
     written).  db [C] (optional, C = x.shape[-1]): receives the column sums of dx = the bias gradient of the conv
-    layer that produced x, in the same pass."""
+    layer that produced x, in the same pass.
+    drop (ops.Drop, optional): g is multiplied by the dropout mask's keep * scale — the forward's, regenerated — in both passes of
+    the backward (encoder form only); without it the code path and the launches are exactly the plain ones."""
     B = x.shape[0]
     Ln = x.numel() // B
     x_is16 = x.dtype == torch.bfloat16
@@ -577,6 +654,11 @@ def instnorm_bwd(x, stats, g, dgamma, dbeta, pre_leaky, post_leaky, alpha, accum
             raise ValueError("instnorm_bwd: a bf16 input needs a multiple of 8 elements per sample")
     else:
         _chk(x, name="x")
+    if drop is not None:
+        _chk_drop(drop, "instnorm_bwd", None, pre_leaky, post_leaky, Ln)
+        if partials is not None and drop.active:
+            raise ValueError("instnorm_bwd: producer-fused partial sums are those of the unmasked gradient; with an active dropout "
+                             "mask the first pass must run (partials=None)")
     g16 = g.dtype == torch.bfloat16
     if g16:
         _chk16(g, x, "g")
@@ -608,10 +690,25 @@ def instnorm_bwd(x, stats, g, dgamma, dbeta, pre_leaky, post_leaky, alpha, accum
         if pre_leaky or not post_leaky or float(alpha) != partials.alpha or tuple(x.shape) != partials.shape:
             raise ValueError(f"instnorm_bwd: partial sums were produced for the post-LeakyReLU(alpha={partials.alpha}) form on "
                              f"shape {partials.shape}; asked for pre={pre_leaky} post={post_leaky} alpha={alpha} shape {tuple(x.shape)}")
+        if drop is not None:
+            check(lib.lg_instnorm_leaky_bwd_z16_drop(_p(x), _p(stats), _p(g), int(g16), _p(out), _p(out16), _p(dgamma), _p(dbeta), _p(db), C,
+                                                     _p(partials.buf), int(partials.nparts), _p(ws), ws.numel(), B, Ln, float(alpha),
+                                                     int(accumulate), *drop._args(), _stream()), "lg_instnorm_leaky_bwd_z16_drop")
+            return out
         check(lib.lg_instnorm_leaky_bwd_z16_p(_p(x), _p(stats), _p(g), int(g16), _p(out), _p(out16), _p(dgamma), _p(dbeta), _p(db), C,
                                               _p(partials.buf), int(partials.nparts), _p(ws), ws.numel(), B, Ln, int(pre_leaky),
                                               int(post_leaky), float(alpha), int(accumulate), _stream()),
               "lg_instnorm_leaky_bwd_z16_p")
+        return out
+    if drop is not None:
+        if x_is16:
+            check(lib.lg_instnorm_leaky_bwd_z16_drop(_p(x), _p(stats), _p(g), int(g16), _p(out), _p(out16), _p(dgamma), _p(dbeta), _p(db), C,
+                                                     None, 0, _p(ws), ws.numel(), B, Ln, float(alpha), int(accumulate), *drop._args(),
+                                                     _stream()), "lg_instnorm_leaky_bwd_z16_drop")
+        else:
+            check(lib.lg_instnorm_leaky_bwd_drop(_p(x), _p(stats), _p(g), int(g16), _p(out), _p(out16), _p(dgamma), _p(dbeta), _p(db), C,
+                                                 _p(ws), ws.numel(), B, Ln, float(alpha), int(accumulate), *drop._args(), _stream()),
+                  "lg_instnorm_leaky_bwd_drop")
         return out
     fn = lib.lg_instnorm_leaky_bwd_z16 if x_is16 else lib.lg_instnorm_leaky_bwd_db
     check(fn(_p(x), _p(stats), _p(g), int(g16), _p(out), _p(out16), _p(dgamma), _p(dbeta), _p(db), C, _p(ws), ws.numel(), B, Ln,
