@@ -299,6 +299,23 @@ int lg_clip_adam_update(float* w, const float* g, float* m, float* v, long long 
 int lg_adam_advance(float* state, float b1, float b2, void* stream);
 int lg_axpby(float* y, const float* x, float a, float b, long long n, void* stream);
 
+/* ---- weight average for sampling (no reference counterpart: the reference samples from the raw last-step weights) ----
+ * Semantics of tf.train.ExponentialMovingAverage(decay, num_updates), the library the reference is written on:
+ *   ema -= (1 - d_t) * (ema - w),  d_t = min(decay, (1 + k) / (10 + k)),  k = ema_state[0] = averages taken so far (int, device).
+ * lg_clip_adam_ema_update runs over one model's whole weight range [0, n): inside [lo, hi) exactly lg_clip_adam_update's arithmetic
+ * (w, m, v bit-identical to it), then the average against the new w; outside it the average alone against the unchanged w — g, m, v
+ * are not read and w is not written there (a partition step's gradients outside the trained group are stale).  lo == hi: the
+ * average alone.  d_t is computed in the kernel from the device counter, so a replayed graph walks the ramp.  n, lo, hi multiples
+ * of 4, all five arrays 16-byte aligned (16-byte accesses).  lg_ema_advance: k += 1, saturating; once per step, after the last
+ * launch that read k. */
+int lg_clip_adam_ema_update(float* w, const float* g, float* m, float* v, float* ema, long long n, long long lo, long long hi,
+                            const float* adam_state, const int* ema_state, float lr, float b1, float b2, float eps, float clip,
+                            float gscale, float decay, void* stream);
+int lg_ema_advance(int* ema_state, void* stream);
+/* a <-> b in place, n a multiple of 4, both 16-byte aligned: switches between the raw and the averaged weights without changing
+ * any address a captured graph holds */
+int lg_swap_f32(float* a, float* b, long long n, void* stream);
+
 /* ---- step inputs drawn on the device  eager_trainer.py:125-131 ------------------------ */
 /* counter-based Philox4x32-10: block i = philox(counter = offset + i, key = seed); 4 x 32 bits per block */
 int lg_philox4x32(unsigned* out, int nblocks, unsigned long long seed, unsigned long long offset, void* stream);

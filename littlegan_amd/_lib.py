@@ -94,6 +94,10 @@ SIGNATURES = {
     "lg_clip_adam_update": (I, [P, P, P, P, L, P, F, F, F, F, F, F, P]),
     "lg_adam_advance": (I, [P, F, F, P]),
     "lg_axpby": (I, [P, P, F, F, L, P]),
+    # weight average for sampling (loss_optim.hip): fused into the Adam pass; the counter's advance; raw <-> averaged swap
+    "lg_clip_adam_ema_update": (I, [P, P, P, P, P, L, L, L, P, P, F, F, F, F, F, F, F, P]),
+    "lg_ema_advance": (I, [P, P]),
+    "lg_swap_f32": (I, [P, P, L, P]),
     "lg_philox4x32": (I, [P, I, L, L, P]),   # seed / offset: unsigned long long in C, passed as their 64-bit pattern
     "lg_randn": (I, [P, L, F, F, L, L, P]),
     "lg_augment_workspace_bytes": (Z, [I]),

@@ -2,7 +2,8 @@
 attribute, derived cond_dim / result_dir / gpu / prefetch.  Extra keys of this build: mfma_dtype ("f32" |
 "bf16"), synthetic (bool: use the synthetic CelebA-shaped dataset), seed, packed_path / data_resident / fuse_input
 (the packed uint8 data set, dataset.py), fid_chunk_rows / fid_device_sqrt (streamed FID statistics, device square root, fid.py), dropout_train (bool: make the encoder's
-dropout(dropout_rate) live in the training step — the reference's, and the default here, is the identity)."""
+dropout(dropout_rate) live in the training step — the reference's, and the default here, is the identity),
+ema_decay / sample_ema (exponential moving average of the weights, used for sampling and kept in checkpoints)."""
 import json
 import os
 from argparse import ArgumentParser
@@ -59,6 +60,10 @@ DEFAULTS = {
     # live encoder dropout: the reference declares dropout_rate and never applies it (model.py:25); with this key the
     # training step's encoder passes apply it (0 < dropout_rate < 1), masks regenerated inside the norm kernels.  Excludes use_gp.
     'dropout_train': False,
+    # weight average for sampling: an exponential moving average of every weight, taken inside the Adam pass with the
+    # semantics of tf.train.ExponentialMovingAverage(ema_decay, num_updates); 0 = off.  sample_ema: predict and the sampling modes read
+    # the average instead of the raw last-step weights (only when ema_decay > 0).
+    'ema_decay': 0.0, 'sample_ema': True,
 }
 
 MODES = ["train", "pack", "plot", "visual", "random-sample", "evaluate", "condition-sample", "evaluate-sample", "export-model"]

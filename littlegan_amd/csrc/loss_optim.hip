@@ -81,6 +81,18 @@ __global__ __launch_bounds__(256) void l1_final_kernel(const float* __restrict__
   if (threadIdx.x == 0) loss[0] = (accumulate ? loss[0] : 0.f) + (float)(sd[0] * (double)scale);
 }
 
+// One element of clip + Adam, shared by the plain and the EMA-fused kernel so that both give the same bits (the library is built
+// with -ffp-contract=off: the same expressions are the same IEEE operations).  Returns the new weight.
+__device__ __forceinline__ float clip_adam_element(float w, float g, float& m, float& v, float lr_t, float b1, float b2, float eps,
+                                                   float clip, float gscale) {
+  float gv = g * gscale;
+  if (clip > 0.f) gv = fminf(fmaxf(gv, -clip), clip);
+  const float mv = b1 * m + (1.f - b1) * gv;
+  const float vv = b2 * v + (1.f - b2) * gv * gv;
+  m = mv; v = vv;
+  return w - lr_t * mv / (sqrtf(vv) + eps);
+}
+
 // state = {beta1_power, beta2_power}
 __global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ w, const float* __restrict__ g,
                                                         float* __restrict__ m, float* __restrict__ v, long long n,
@@ -89,17 +101,67 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ w, c
   const float lr_t = lr * sqrtf(1.f - state[1]) / (1.f - state[0]);
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float gv = g[i] * gscale;
-    if (clip > 0.f) gv = fminf(fmaxf(gv, -clip), clip);
-    const float mv = b1 * m[i] + (1.f - b1) * gv;
-    const float vv = b2 * v[i] + (1.f - b2) * gv * gv;
+    float mv = m[i], vv = v[i];
+    w[i] = clip_adam_element(w[i], g[i], mv, vv, lr_t, b1, b2, eps, clip, gscale);
     m[i] = mv; v[i] = vv;
-    w[i] -= lr_t * mv / (sqrtf(vv) + eps);
+  }
+}
+
+// clip + Adam on the 4-float groups [lo4, hi4) of one model's weights, and the weight average on ALL of its n4 groups:
+//   ema -= (1 - d_t) * (ema - w),  d_t = min(decay, (1 + k) / (10 + k)),  k = ema_state[0] = averages taken so far
+// (tf.train.ExponentialMovingAverage(decay, num_updates)).  d_t is computed here, from the device counter: a captured graph bakes
+// launch scalars in, a replayed step still walks the ramp.  Outside [lo4, hi4) nothing but w and ema is touched: on a partition
+// step the gradients there are stale and were not all-reduced.  16-byte accesses; the caller guarantees the alignment.
+__global__ __launch_bounds__(256) void clip_adam_ema_kernel(float* __restrict__ w, const float* __restrict__ g,
+                                                            float* __restrict__ m, float* __restrict__ v,
+                                                            float* __restrict__ ema, long long n4, long long lo4, long long hi4,
+                                                            const float* __restrict__ state, const int* __restrict__ ema_state,
+                                                            float lr, float b1, float b2, float eps, float clip, float gscale,
+                                                            float decay) {
+  const float lr_t = lr * sqrtf(1.f - state[1]) / (1.f - state[0]);
+  const float kf = (float)ema_state[0];
+  const float omd = 1.f - fminf(decay, (1.f + kf) / (10.f + kf));
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    f32x4 wv = *reinterpret_cast<const f32x4*>(w + i * 4);
+    if (i >= lo4 && i < hi4) {
+      const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
+      f32x4 mv = *reinterpret_cast<const f32x4*>(m + i * 4);
+      f32x4 vv = *reinterpret_cast<const f32x4*>(v + i * 4);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float mk = mv[k], vk = vv[k];
+        wv[k] = clip_adam_element(wv[k], gv[k], mk, vk, lr_t, b1, b2, eps, clip, gscale);
+        mv[k] = mk; vv[k] = vk;
+      }
+      *reinterpret_cast<f32x4*>(m + i * 4) = mv;
+      *reinterpret_cast<f32x4*>(v + i * 4) = vv;
+      *reinterpret_cast<f32x4*>(w + i * 4) = wv;
+    }
+    f32x4 ev = *reinterpret_cast<const f32x4*>(ema + i * 4);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ev[k] -= omd * (ev[k] - wv[k]);
+    *reinterpret_cast<f32x4*>(ema + i * 4) = ev;
   }
 }
 
 __global__ void adam_advance_kernel(float* state, float b1, float b2) {
   if (threadIdx.x == 0 && blockIdx.x == 0) { state[0] *= b1; state[1] *= b2; }
+}
+
+// the count of averages taken: once per step, after the last launch that read it; saturates
+__global__ void ema_advance_kernel(int* ema_state) {
+  if (threadIdx.x == 0 && blockIdx.x == 0 && ema_state[0] < 0x7fffffff) ema_state[0] += 1;
+}
+
+__global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float* __restrict__ b, long long n4) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const f32x4 av = *reinterpret_cast<const f32x4*>(a + i * 4);
+    const f32x4 bv = *reinterpret_cast<const f32x4*>(b + i * 4);
+    *reinterpret_cast<f32x4*>(a + i * 4) = bv;
+    *reinterpret_cast<f32x4*>(b + i * 4) = av;
+  }
 }
 
 __global__ __launch_bounds__(256) void axpby_kernel(float* __restrict__ y, const float* __restrict__ x, float a, float b,
@@ -159,6 +221,48 @@ extern "C" int lg_adam_advance(float* state, float b1, float b2, void* stream) {
   LG_CHECK_ARG(state, "lg_adam_advance: null pointer");
   hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, b1, b2);
   LG_CHECK_LAUNCH("lg_adam_advance");
+  return LG_OK;
+}
+
+// clip + Adam on [lo, hi) of one model's range [0, n) and the weight average over all of it (lo == hi: the average alone); no
+// reference counterpart: tf.train.ExponentialMovingAverage(decay, num_updates) semantics, num_updates = ema_state[0] on the device
+extern "C" int lg_clip_adam_ema_update(float* w, const float* g, float* m, float* v, float* ema, long long n, long long lo,
+                                       long long hi, const float* adam_state, const int* ema_state, float lr, float b1, float b2,
+                                       float eps, float clip, float gscale, float decay, void* stream) {
+  LG_CHECK_ARG(w && g && m && v && ema && adam_state && ema_state, "lg_clip_adam_ema_update: null pointer");
+  LG_CHECK_ARG(n > 0 && n % 4 == 0, "lg_clip_adam_ema_update: n=%lld must be a positive multiple of 4", n);
+  LG_CHECK_ARG(lo >= 0 && lo <= hi && hi <= n && lo % 4 == 0 && hi % 4 == 0,
+               "lg_clip_adam_ema_update: need 0 <= lo <= hi <= n, both multiples of 4 (lo=%lld hi=%lld n=%lld)", lo, hi, n);
+  LG_CHECK_ARG(((uintptr_t)w | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) % 16 == 0,
+               "lg_clip_adam_ema_update: w, g, m, v, ema must be 16-byte aligned");
+  LG_CHECK_ARG(decay >= 0.f && decay < 1.f, "lg_clip_adam_ema_update: decay=%g outside [0, 1)", (double)decay);
+  const long long n4 = n / 4;
+  long long nb = (n4 + 255) / 256;
+  if (nb > 4096) nb = 4096;
+  hipLaunchKernelGGL(clip_adam_ema_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, w, g, m, v, ema, n4, lo / 4, hi / 4,
+                     adam_state, ema_state, lr, b1, b2, eps, clip, gscale, decay);
+  LG_CHECK_LAUNCH("lg_clip_adam_ema_update");
+  return LG_OK;
+}
+
+extern "C" int lg_ema_advance(int* ema_state, void* stream) {
+  LG_CHECK_ARG(ema_state, "lg_ema_advance: null pointer");
+  hipLaunchKernelGGL(ema_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ema_state);
+  LG_CHECK_LAUNCH("lg_ema_advance");
+  return LG_OK;
+}
+
+// a <-> b in place (raw weights <-> their average: no address a captured graph holds changes)
+extern "C" int lg_swap_f32(float* a, float* b, long long n, void* stream) {
+  LG_CHECK_ARG(a && b, "lg_swap_f32: null pointer");
+  LG_CHECK_ARG(a != b, "lg_swap_f32: a and b are the same buffer");
+  LG_CHECK_ARG(n > 0 && n % 4 == 0, "lg_swap_f32: n=%lld must be a positive multiple of 4", n);
+  LG_CHECK_ARG(((uintptr_t)a | (uintptr_t)b) % 16 == 0, "lg_swap_f32: a, b must be 16-byte aligned");
+  const long long n4 = n / 4;
+  long long nb = (n4 + 255) / 256;
+  if (nb > 4096) nb = 4096;
+  hipLaunchKernelGGL(swap_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, a, b, n4);
+  LG_CHECK_LAUNCH("lg_swap_f32");
   return LG_OK;
 }
 

@@ -8,6 +8,7 @@ flat buffer and are all-reduced (RCCL) on a side stream while the next tape's ba
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import os
 import time
@@ -45,6 +46,14 @@ def train_weight_range(args, model: str, batch_no: int):
     return (0, n_all)
 
 
+def validate_ema_decay(decay) -> float:
+    """ema_decay of the configuration: 0 (off) or a decay in (0, 1)."""
+    d = float(decay)
+    if not 0.0 <= d < 1.0:
+        raise ValueError(f"ema_decay must satisfy 0 <= ema_decay < 1 (0 = off), got {decay}")
+    return d
+
+
 class EagerTrainer:
     def __init__(self, args, generator: Generator, discriminator: Discriminator, adjuster: Adjuster, dataset):
         self.args = args
@@ -67,7 +76,13 @@ class EagerTrainer:
         if self.dropout and self.use_gp:
             raise ValueError("use_gp and dropout_train exclude each other: the penalty's double backward through a masked norm "
                              "is not built (DESIGN.md §15)")
+        # weight average for sampling (the reference has none): on when ema_decay > 0
+        self.ema_decay = validate_ema_decay(getattr(args, "ema_decay", 0.0))
+        self.sample_ema = bool(getattr(args, "sample_ema", True))
+        self._ema_live = False   # inside ema_weights(): `flat` holds the average
         self.store = ParamStore(generator, discriminator, adjuster)
+        if self.ema_decay > 0.0:
+            self.store.enable_ema()
         # tf.compat.v1.train.AdamOptimizer x3 (eager_trainer.py:28-30): {beta1_power, beta2_power} per optimizer
         self.opt_cfg = {"G": (args.lr, args.beta_1, args.beta_2), "D": (args.lr, args.beta_1, args.beta_2),
                         "A": (args.lr, 0.9, 0.999)}
@@ -102,6 +117,8 @@ class EagerTrainer:
         Returns (fake_image, adj_image|None, gen_loss, disc_loss, adj_loss|None) — losses are 1-element device tensors
         (no host sync on the hot path)."""
         a = self.args
+        if self._ema_live:
+            raise RuntimeError("train_step_from_inputs inside ema_weights(): the store holds the averaged weights")
         G, D, A = self.generator, self.discriminator, self.adjuster
         img1, c1, img2, c2 = inp["real_image_1"], inp["real_cond_1"], inp["real_image_2"], inp["real_cond_2"]
         noise, new_image = inp["noise"], inp["new_image"]
@@ -192,22 +209,69 @@ class EagerTrainer:
         # test_adam_order_is_immaterial, tests/test_dp_cpu.py).  Here: the order the all-reduces were launched in, each set
         # waited for on its own right before its Adam — D and G are applied while A's all-reduce (launched last) is on the
         # wire.  D-grads are clipped after the all-reduce, inside the Adam kernel.
-        gscale = 1.0 / self.sync.world_size
-        for m in self.adam_order:
-            if m == "A" and not run_adj:
-                continue
-            self.sync.wait(m)
-            lo, hi = train_weight_range(a, m, batch_no)
-            s, e = self.store.model_range(m, lo, hi)
-            lr, b1, b2 = self.opt_cfg[m]
-            clip = a.clip_range if (m == "D" and a.use_clip) else 0.0
-            st = self.store
-            ops.clip_adam_update(st.flat[s:e], st.grad[s:e], st.m[s:e], st.v[s:e], self.opt_state[m], lr, b1, b2,
-                                 ADAM_EPS, clip, gscale)
-            ops.adam_advance(self.opt_state[m], b1, b2)
+        self._apply_optimizers(batch_no, run_adj)
         self.sync.wait_all()
         self.store.bump()
         return (fake, adj_image, self.losses["gen"], self.losses["disc"], self.losses["adj"] if run_adj else None)
+
+    def _apply_optimizers(self, batch_no: int, run_adj: bool):
+        a, st = self.args, self.store
+        gscale = 1.0 / self.sync.world_size
+        for m in self.adam_order:
+            trained = m != "A" or run_adj
+            if not trained and st.ema is None:
+                continue
+            lr, b1, b2 = self.opt_cfg[m]
+            clip = a.clip_range if (m == "D" and a.use_clip) else 0.0
+            lo, hi = train_weight_range(a, m, batch_no)
+            s, e = st.model_range(m, lo, hi)
+            if trained:
+                self.sync.wait(m)
+            if st.ema is None:
+                ops.clip_adam_update(st.flat[s:e], st.grad[s:e], st.m[s:e], st.v[s:e], self.opt_state[m], lr, b1, b2,
+                                     ADAM_EPS, clip, gscale)
+            else:
+                # the same Adam on [s, e) fused with the weight average over the model's WHOLE range: outside the
+                # trained group only w and ema are read; an Adjuster that does not train this step gets the average alone (lo == hi)
+                s0, e0 = st.model_range(m)
+                t_lo, t_hi = (s - s0, e - s0) if trained else (0, 0)
+                ops.clip_adam_ema_update(st.flat[s0:e0], st.grad[s0:e0], st.m[s0:e0], st.v[s0:e0], st.ema[s0:e0], t_lo, t_hi,
+                                         self.opt_state[m], st.ema_updates, lr, b1, b2, ADAM_EPS, clip, gscale, self.ema_decay)
+            if trained:
+                ops.adam_advance(self.opt_state[m], b1, b2)
+        if st.ema is not None:
+            ops.ema_advance(st.ema_updates)   # after the last launch that read the counter: one average per step
+
+    # ------------------------------------------------------------------ the weight average
+    def reset_ema(self):
+        """The average restarts from the present weights (count 0): after weights were loaded from outside a training step."""
+        if self.store.ema is not None:
+            self.store.ema.copy_(self.store.flat)
+            self.store.ema_updates.zero_()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block every model computes with the AVERAGED weights: `flat` and `ema` are exchanged in place (lg_swap_f32: no
+        address changes, captured graphs stay valid) and exchanged back on exit.  A no-op when ema_decay == 0.  Nested use is a
+        no-op too: the inner block finds the average already in place and leaves the way back to the outer one.  Training inside
+        the block is refused."""
+        st = self.store
+        if st.ema is None or self._ema_live:
+            yield
+            return
+        ops.swap_f32(st.flat, st.ema)
+        st.bump()
+        self._ema_live = True
+        try:
+            yield
+        finally:
+            ops.swap_f32(st.flat, st.ema)
+            st.bump()
+            self._ema_live = False
+
+    def sampling_weights(self):
+        """ema_weights() when the configuration samples from the average (ema_decay > 0 and sample_ema), else the raw weights."""
+        return self.ema_weights() if (self.ema_decay > 0.0 and self.sample_ema) else contextlib.nullcontext()
 
     # ------------------------------------------------------------------ the same step as a replayed HIP graph
     def step_kind(self, batch_no: int):
@@ -409,7 +473,13 @@ class EagerTrainer:
             _barrier()  # the other ranks do not run ahead into the next epoch while rank 0 writes
 
     # ------------------------------------------------------------------ eager_trainer.py:265-298
-    def predict(self, noise, cond, image, gen_image_save_path=None, json_save_path=None, adj_image_save_path=None):
+    def predict(self, noise, cond, image, gen_image_save_path=None, json_save_path=None, adj_image_save_path=None, ema=None):
+        """ema: compute with the averaged weights (DESIGN.md §16).  None = the configuration's choice (ema_decay > 0 and sample_ema);
+        True without an average (ema_decay == 0) is the raw weights."""
+        with (self.sampling_weights() if ema is None else self.ema_weights() if ema else contextlib.nullcontext()):
+            return self._predict(noise, cond, image, gen_image_save_path, json_save_path, adj_image_save_path)
+
+    def _predict(self, noise, cond, image, gen_image_save_path, json_save_path, adj_image_save_path):
         start_time = time.time()
         gen_image = self.generator([noise, cond])
         torch.cuda.synchronize()
@@ -520,11 +590,14 @@ class EagerTrainer:
     # tf.train.Checkpoint(discriminator, generator, adjuster, three optimizers) eager_trainer.py:31-35)
     def checkpoint_state(self) -> dict:
         st = self.store
-        return {"format": "littlegan_amd-ckpt-1",
-                "names": {m: st.names(m) for m in "GDA"},
-                "flat": st.flat.detach().cpu(), "adam_m": st.m.detach().cpu(), "adam_v": st.v.detach().cpu(),
-                "beta_powers": {m: t.detach().cpu() for m, t in self.opt_state.items()},
-                "epoch": self.global_epoch, "input_step": int(self._input_step)}
+        ck = {"format": "littlegan_amd-ckpt-1",
+              "names": {m: st.names(m) for m in "GDA"},
+              "flat": st.flat.detach().cpu(), "adam_m": st.m.detach().cpu(), "adam_v": st.v.detach().cpu(),
+              "beta_powers": {m: t.detach().cpu() for m, t in self.opt_state.items()},
+              "epoch": self.global_epoch, "input_step": int(self._input_step)}
+        if st.ema is not None:   # the weight average and the count of averages taken (absent with ema_decay == 0; same format)
+            ck["ema"], ck["ema_updates"] = st.ema.detach().cpu(), int(st.ema_updates.item())
+        return ck
 
     def save_checkpoint(self, tag: str) -> str:
         """Rank 0 writes (weights are identical on every rank after the all-reduced step); other ranks return the path."""
@@ -565,11 +638,21 @@ class EagerTrainer:
         for m, t in ck["beta_powers"].items():
             self.opt_state[m].copy_(t)
         self._input_step = int(ck.get("input_step", 0))  # a resumed run continues the Philox input stream
+        if st.ema is not None:   # (a checkpoint's average is ignored when this run keeps none)
+            if "ema" in ck and "ema_updates" in ck:
+                st.ema.copy_(ck["ema"])
+                st.ema_updates.fill_(int(ck["ema_updates"]))
+            else:
+                print(f"{path}: no weight average in this checkpoint; it restarts from the loaded weights (0 updates)")
+                self.reset_ema()
         st.bump()
 
     def export_model_checkpoint(self):
         path = os.path.join(self.args.result_dir, "model", "model.pt")
-        torch.save({"names": {m: self.store.names(m) for m in "GDA"}, "flat": self.store.flat.cpu()}, path)
+        out = {"names": {m: self.store.names(m) for m in "GDA"}, "flat": self.store.flat.cpu()}
+        if self.store.ema is not None:
+            out["ema_flat"] = self.store.ema.cpu()
+        torch.save(out, path)
         return path
 
     def plot(self):

@@ -748,7 +748,7 @@ class Adjuster(_Module):
 class ParamStore:
     """Re-homes every weight of (G, D, A-own) into ONE flat fp32 buffer, in the order
     [Generator.weights (22) | Discriminator.weights (20) | Adjuster.weights[16:20] (4)], each weight
-    16-byte aligned, with same-layout gradient and Adam-slot buffers.  The three optimizers, the
+    16-byte aligned, with same-layout gradient and Adam-slot buffers (and, with ema_decay > 0, the weight average).  The three optimizers, the
     partition groups (eager_trainer.py:48-52) and the data-parallel all-reduce buckets then are
     contiguous ranges of it."""
 
@@ -777,6 +777,14 @@ class ParamStore:
             part._g[name] = self.grad[o:o + n].view(shp)
             self.ranges.setdefault(m, []).append((o, o + (n + 3) // 4 * 4))
         self._stacks = [discriminator.encoder, generator.decoder, generator.conv]
+        # weight average for sampling: same layout as `flat`, allocated by enable_ema() only; the count of averages
+        # taken lives on the device (the kernel computes the decay ramp from it, so a replayed graph walks the ramp)
+        self.ema = None
+        self.ema_updates = None
+
+    def enable_ema(self):
+        self.ema = self.flat.clone()
+        self.ema_updates = torch.zeros(1, dtype=torch.int32, device=self.flat.device)
 
     def model_range(self, m, idx_lo=None, idx_hi=None):
         r = self.ranges[m]

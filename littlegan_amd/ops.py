@@ -851,6 +851,38 @@ def adam_advance(state, b1, b2):
     check(_lib.load().lg_adam_advance(_p(state), float(b1), float(b2), _stream()), "lg_adam_advance")
 
 
+def _chk_counter(t, name):
+    if not (t.is_cuda and t.dtype == torch.int32 and t.numel() == 1):
+        raise ValueError(f"{name}: need a 1-element int32 CUDA tensor, got {t.dtype} {t.device} numel={t.numel()}")
+    return t
+
+
+def clip_adam_ema_update(w, g, m, v, ema, lo, hi, state, ema_state, lr, b1, b2, eps, clip, gscale, decay):
+    """clip + Adam on [lo, hi) of one model's weights `w` and the weight average `ema` over all of them (lo == hi: the average
+    alone): ema -= (1 - d_t)(ema - w), d_t = min(decay, (1 + k) / (10 + k)), k = ema_state[0] (lg_clip_adam_ema_update)."""
+    n = w.numel()
+    for t, nm in ((w, "w"), (g, "g"), (m, "m"), (v, "v"), (ema, "ema")):
+        _chk(t, name=nm)
+        if t.numel() != n:
+            raise ValueError("clip_adam_ema_update: size mismatch")
+    _chk(state, (2,), "state")
+    _chk_counter(ema_state, "ema_state")
+    check(_lib.load().lg_clip_adam_ema_update(_p(w), _p(g), _p(m), _p(v), _p(ema), n, int(lo), int(hi), _p(state), _p(ema_state),
+                                              float(lr), float(b1), float(b2), float(eps), float(clip), float(gscale),
+                                              float(decay), _stream()), "lg_clip_adam_ema_update")
+
+
+def ema_advance(ema_state):
+    check(_lib.load().lg_ema_advance(_p(_chk_counter(ema_state, "ema_state")), _stream()), "lg_ema_advance")
+
+
+def swap_f32(a, b):
+    """a <-> b in place (lg_swap_f32)."""
+    _chk(a, name="a")
+    _chk(b, a.shape, "b")
+    check(_lib.load().lg_swap_f32(_p(a), _p(b), a.numel(), _stream()), "lg_swap_f32")
+
+
 # ------------------------------------------------------------------ conv forward with fused InstanceNorm moments
 def _fwd_stats(fn_name, x, x16, pack, bias, out, B, Hs, Ws, cb, cs, dtype, gamma, beta, tag, flops, up, defer=False):
     """Runs the conv (`out` fp32, or bf16 = the bf16 activation path); if its kernel produced per-block moment partials,

@@ -101,7 +101,8 @@ elif args.mode == "condition-sample":
                          [1., 1., 1., 0., 1., 0., 1.], [1., 1., 1., 1., 1., 0., 1.]], device=model.device)
     for i in range(1, 1 + args.condition_sample_batch):
         noise = torch.randn(1, args.noise_dim, device=model.device).repeat(8, 1)
-        img = model.generator([noise, cond])
+        with model.sampling_weights():   # the averaged weights when ema_decay > 0 and sample_ema
+            img = model.generator([noise, cond])
         save_image(img, path.join(args.result_dir, "sample", "condition-gen-%d.jpg" % i), (1, 8))
 elif args.mode == "export-model":
     args.reuse = True
