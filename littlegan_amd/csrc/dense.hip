@@ -148,6 +148,7 @@ extern "C" int lg_concat_cols(const float* a, int ka, const float* c, int kc, fl
   const long long nb = (total + 255) / 256;
   hipLaunchKernelGGL(concat_cols_kernel, dim3((int)(nb < 1024 ? nb : 1024)), dim3(256), 0, (hipStream_t)stream, a, ka, c, kc, out, total);
   LG_CHECK_LAUNCH("lg_concat_cols");
+  lg_note_kernel("concat_cols_kernel");
   return LG_OK;
 }
 
@@ -157,6 +158,7 @@ extern "C" int lg_adj_conditions(const float* first, const float* second, float*
   const long long nb = (2 * half + 255) / 256;
   hipLaunchKernelGGL(adj_conditions_kernel, dim3((int)(nb < 1024 ? nb : 1024)), dim3(256), 0, (hipStream_t)stream, first, second, t, u, half);
   LG_CHECK_LAUNCH("lg_adj_conditions");
+  lg_note_kernel("adj_conditions_kernel");
   return LG_OK;
 }
 
@@ -178,6 +180,7 @@ extern "C" int lg_dense_fwd(const float* x, const float* w, const float* bias, f
   hipLaunchKernelGGL(dense_fwd_kernel<TB>, grid, dim3(256), TB * K * sizeof(float), (hipStream_t)stream, x, w, bias, y,
                      B, K, N);
   LG_CHECK_LAUNCH("lg_dense_fwd");
+  lg_note_kernel("dense_fwd_kernel");
   return LG_OK;
 }
 
@@ -200,6 +203,7 @@ extern "C" int lg_dense_wgrad(const float* x, const float* dy, float* dw, float*
   dim3 grid(lg_cdiv(N, 256), lg_cdiv(K, KT));
   hipLaunchKernelGGL(dense_wgrad_kernel<KT>, grid, dim3(256), lds, (hipStream_t)stream, x, dy, dw, db, B, K, N, accumulate);
   LG_CHECK_LAUNCH("lg_dense_wgrad");
+  lg_note_kernel("dense_wgrad_kernel");
   return LG_OK;
 }
 
@@ -208,5 +212,6 @@ extern "C" int lg_dense_dgrad(const float* dy, const float* w, float* dx, int B,
   LG_CHECK_ARG(B > 0 && B <= 65535 && K > 0 && N > 0 && N % 4 == 0, "lg_dense_dgrad: bad shape B=%d K=%d N=%d", B, K, N);
   hipLaunchKernelGGL(dense_dgrad_kernel, dim3(lg_cdiv(K, 4), B), dim3(256), 0, (hipStream_t)stream, dy, w, dx, K, N);
   LG_CHECK_LAUNCH("lg_dense_dgrad");
+  lg_note_kernel("dense_dgrad_kernel");
   return LG_OK;
 }

@@ -217,10 +217,11 @@ extern "C" int lg_heads_fwd(const float* x, const float* wpr, const float* bpr, 
     hipLaunchKernelGGL(heads_fwd_kernel, dim3(nkc, lg_cdiv(B, FS)), dim3(256), 0, (hipStream_t)stream, x, wpr, wc, part,
                        B, K, c);
     LG_CHECK_LAUNCH("lg_heads_fwd");
+    lg_note_kernel("heads_fwd_kernel");
   }
   hipLaunchKernelGGL(heads_final_kernel, dim3(lg_cdiv(B * (c + 1), 256)), dim3(256), 0, (hipStream_t)stream, part, bpr,
                      bc, p, B, c, nkc);
-  LG_CHECK_LAUNCH("lg_heads_fwd(final)");
+  LG_CHECK_LAUNCH("lg_heads_fwd(final)");  // (the name noted stays that of the GEMM kernel: heads_final_kernel follows both)
   return LG_OK;
 }
 
@@ -236,6 +237,7 @@ extern "C" int lg_heads_dgrad(const float* dz, const float* wpr, const float* wc
   const size_t lds = (size_t)((256 * (c | 1) + 3) / 4 * 4 + DB * (c + 1)) * sizeof(float);
   hipLaunchKernelGGL(heads_dgrad_kernel, grid, dim3(256), lds, (hipStream_t)stream, dz, wpr, wc, dx, B, K, c);
   LG_CHECK_LAUNCH("lg_heads_dgrad");
+  lg_note_kernel("heads_dgrad_kernel");
   return LG_OK;
 }
 
@@ -250,5 +252,6 @@ extern "C" int lg_heads_wgrad(const float* x, const float* dz, float* dwpr, floa
   hipLaunchKernelGGL(heads_wgrad_kernel, dim3(lg_cdiv(K, WK)), dim3(256), 0, (hipStream_t)stream, x, dz, dwpr, dbpr,
                      dwc, dbc, B, K, c, accumulate);
   LG_CHECK_LAUNCH("lg_heads_wgrad");
+  lg_note_kernel("heads_wgrad_kernel");
   return LG_OK;
 }

@@ -5,14 +5,18 @@
 //                                                           over blocks AND over the 4 waves of a block -> partials
 //   heads_wgrad dW[k][j] = sum_b x[b][k] dz[b][j]           M = k, N = j, contraction b split over the 4 waves of a block
 //   heads_dgrad dx[b][k] = sum_j dz[b][j] W[k][j]           M = b, N = k, contraction j (<= 41 -> 21 steps)
-//   dense_fwd   y[b][n]  = sum_k x[b][k] w[k][n] + bias[n]  M = b, N = n (wide), contraction k (133 -> 67 steps)
-//   dense_wgrad dw[k][n] = sum_b x[b][k] dy[b][n]           M = k (133 -> 5 tiles), N = n, contraction b
+//   dense_fwd   y[b][n]  = sum_k x[b][k] w[k][n] + bias[n]  M = b, N = n (wide), contraction k (133 -> 67 steps; K <= 144)
+//   dense_wgrad dw[k][n] = sum_b x[b][k] dy[b][n]           M = k (133 -> 5 tiles; K <= 160), N = n, contraction b
 // W = [wpr | wc]: column 0 is dense_pr.kernel [K][1], columns 1..c dense_cond.kernel [K][c]  (/root/reference/model.py:62-63).
 // Operand layout of the instruction: lane (r = lane & 31, h = lane >> 5) supplies A[row r][k = h] and B[k = h][col r];
 // accumulator register e holds row (e & 3) + 8 (e >> 2) + 4 h, column r.  The contraction index may be visited in any
 // order as long as A and B agree, so a lane that owns 8 consecutive k (two 16-B loads of a row) simply uses them in 8
 // successive instructions: its partner lane (h ^ 1) owns the other 8 of the 16.
-// Entry points return LG_ERR_UNSUPPORTED for ragged shapes; the callers then run the VALU kernels.
+// Entry points return LG_ERR_UNSUPPORTED outside these shapes (and under LG_NO_SKINNY_MFMA); the callers then run the VALU kernels:
+//   heads_fwd   B % 32 == 0 && K % 512 == 0          heads_wgrad B % 64 == 0 && K % 32 == 0
+//   heads_dgrad B % 32 == 0 && K % 128 == 0 and the block's sample tiles fit 48 KiB of LDS (c = 40: B <= 1152)
+//   dense_fwd   B % 32 == 0 && N % 128 == 0 && K <= 144          dense_wgrad B % 32 == 0 && N % 32 == 0 && K <= 160
+// Every launcher names its kernel through lg_note_kernel (tests/test_skinny_gpu.py asserts the route of each shape).
 #include <stdlib.h>
 #include "lg_common.h"
 
@@ -296,6 +300,7 @@ extern "C" int lg_heads_fwd_mfma_try(const float* x, const float* wpr, const flo
   if (!skinny_on() || B % 32 || K % 512 || c < 1 || c > 40) return LG_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(heads_fwd_mfma_kernel, dim3(K / 512, B / 32), dim3(256), 0, (hipStream_t)stream, x, wpr, wc, part, B, K, c);
   LG_CHECK_LAUNCH("lg_heads_fwd(mfma)");
+  lg_note_kernel("heads_fwd_mfma_kernel");
   *nkc_out = K / 512;
   return LG_OK;
 }
@@ -306,6 +311,7 @@ extern "C" int lg_heads_wgrad_mfma_try(const float* x, const float* dz, float* d
   hipLaunchKernelGGL(heads_wgrad_mfma_kernel, dim3(K / 32), dim3(256), 0, (hipStream_t)stream, x, dz, dwpr, dbpr, dwc, dbc, B, K, c,
                      accumulate);
   LG_CHECK_LAUNCH("lg_heads_wgrad(mfma)");
+  lg_note_kernel("heads_wgrad_mfma_kernel");
   return LG_OK;
 }
 
@@ -317,6 +323,7 @@ extern "C" int lg_heads_dgrad_mfma_try(const float* dz, const float* wpr, const 
   if (lds > 48 * 1024) return LG_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(heads_dgrad_mfma_kernel, dim3(K / 128, gy), dim3(256), lds, (hipStream_t)stream, dz, wpr, wc, dx, B, K, c);
   LG_CHECK_LAUNCH("lg_heads_dgrad(mfma)");
+  lg_note_kernel("heads_dgrad_mfma_kernel");
   return LG_OK;
 }
 
@@ -326,6 +333,7 @@ extern "C" int lg_dense_fwd_mfma_try(const float* x, const float* w, const float
   hipLaunchKernelGGL(dense_fwd_mfma_kernel, dim3(N / 128, B / 32), dim3(256), (size_t)32 * (K | 1) * sizeof(float),
                      (hipStream_t)stream, x, w, bias, y, B, K, N);
   LG_CHECK_LAUNCH("lg_dense_fwd(mfma)");
+  lg_note_kernel("dense_fwd_mfma_kernel");
   return LG_OK;
 }
 
@@ -339,5 +347,7 @@ extern "C" int lg_dense_wgrad_mfma_try(const float* x, const float* dy, float* d
   if (mt == 1) LG_DW(1); else if (mt == 2) LG_DW(2); else if (mt == 3) LG_DW(3); else if (mt == 4) LG_DW(4); else LG_DW(5);
 #undef LG_DW
   LG_CHECK_LAUNCH("lg_dense_wgrad(mfma)");
+  lg_note_kernel(mt == 1 ? "dense_wgrad_mfma_kernel<1>" : mt == 2 ? "dense_wgrad_mfma_kernel<2>" : mt == 3 ? "dense_wgrad_mfma_kernel<3>"
+                 : mt == 4 ? "dense_wgrad_mfma_kernel<4>" : "dense_wgrad_mfma_kernel<5>");
   return LG_OK;
 }

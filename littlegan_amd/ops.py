@@ -86,7 +86,8 @@ def pin_workspaces():
 
 
 def last_kernel() -> str:
-    """Name of the kernel the most recent conv-class C-ABI call launched on this thread (lg_last_kernel)."""
+    """Name of the kernel the most recent conv-class, dense or head C-ABI call launched on this thread (lg_last_kernel; sticky:
+    lg_clear_kernel in front of a call whose route is to be read)."""
     return _lib.load().lg_last_kernel().decode()
 
 

@@ -90,4 +90,6 @@ def short(name):
         return "conv_up4_kernel<PAIR>" if t(2) == "true" else "conv_up4_kernel"
     if base in ("up_p16_kernel", "s1t_fwd_p16_kernel"):
         return base
+    if base in ("dense_fwd_kernel", "dense_wgrad_kernel"):   # <TB> / <KT>: one instance each; dense_wgrad_mfma_kernel<MT> keeps its argument
+        return base
     return base + ("<" + ",".join(a) + ">" if a else "")

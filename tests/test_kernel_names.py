@@ -42,6 +42,13 @@ CASES = [
     ("_ZN12_GLOBAL__N_118bwd_apply16_kernelILb0ELb1EEEvPKDF16bPKvPKfS6_PfPDF16bxxiifS7_i", "bwd_apply16_kernel<false,true>"),
     ("apply16_kernel<0>", "apply16_kernel<0>"),
     ("bwd_final_kernel", "bwd_final_kernel"),
+    ("void (anonymous namespace)::dense_wgrad_mfma_kernel<3>(float const*, float const*, float*, float*, int, int, int, int)", "dense_wgrad_mfma_kernel<3>"),
+    ("_ZN12_GLOBAL__N_123dense_wgrad_mfma_kernelILi5EEEvPKfS2_PfS3_iiii", "dense_wgrad_mfma_kernel<5>"),
+    ("dense_wgrad_kernel<16>", "dense_wgrad_kernel"),
+    ("_ZN12_GLOBAL__N_116dense_fwd_kernelILi8EEEvPKfS2_S2_Pfiii", "dense_fwd_kernel"),
+    ("dense_fwd_mfma_kernel", "dense_fwd_mfma_kernel"),
+    ("_ZN12_GLOBAL__N_123heads_dgrad_mfma_kernelEPKfS1_S1_Pfiii", "heads_dgrad_mfma_kernel"),
+    ("void (anonymous namespace)::heads_wgrad_kernel(float const*, float const*, float*, float*, float*, float*, int, int, int, int)", "heads_wgrad_kernel"),
 ]
 
 
