@@ -10,6 +10,7 @@
 // the fused AdjustHue op — a rotation of the hue angle that keeps each pixel's min and max channel values, defined for
 // any value range (the images here live in [-1, 1]).
 // The generator, the per-pixel transform and the kernels shared with the packed uint8 input path are in augment_core.h.
+#include "lg_internal.h"
 #include "augment_core.h"
 
 namespace {

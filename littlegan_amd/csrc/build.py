@@ -1,4 +1,5 @@
 """Builds liblittlegan_hip.so (gfx950) in-tree with hipcc.  `python -m littlegan_amd.csrc.build`"""
+import glob
 import os
 import subprocess
 import sys
@@ -12,8 +13,10 @@ LIB = os.path.join(PKG, "liblittlegan_hip.so")
 # different results lost the low half of a packed fp32 subtraction (VGPR pair, high-register select) with a second wave on the SIMD; without
 # packed fp32 instructions the same source is deterministic, and the whole library is as fast (C3 10.944 / 10.948 against 10.955 / 10.958 ms,
 # C2 8.912 / 8.906, C5 39.89 / 39.96: scripts/probe/nopk_ab.sh) — the instruction class is simply not generated.
+# -Werror=missing-prototypes: a non-static function must be declared in a header before it is defined (lg_internal.h, or the public
+# include/littlegan_hip.h), so every cross-file call is checked against the one declaration its definition was checked against.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
-         "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+         "-Wmissing-prototypes", "-Werror=missing-prototypes", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 
 def _stale(out, deps):
@@ -37,14 +40,8 @@ def build(force=False, verbose=True, variant=None):
     if not variant and os.environ.get("LG_EXTRA_FLAGS"):
         raise SystemExit("LG_EXTRA_FLAGS needs --variant NAME: ablation builds never replace the product library")
     os.makedirs(objdir, exist_ok=True)
-    common_h, public_h = os.path.join(HERE, "lg_common.h"), os.path.join(os.path.dirname(PKG), "include", "littlegan_hip.h")
-    augment_h, philox_h = os.path.join(HERE, "augment_core.h"), os.path.join(HERE, "philox.h")
-
-    def hdrs_of(path):   # the public header is a dependency of the sources that include it (capi.hip, runtime.hip), not of every kernel file
-        text = open(path).read()   # augment_core.h: the device code augment.hip and input_u8.hip share; philox.h: those and norm.hip
-        aug = "augment_core.h" in text
-        return ([common_h] + ([public_h] if "littlegan_hip.h" in text else []) + ([augment_h] if aug else [])
-                + ([philox_h] if aug or "philox.h" in text else []))
+    # every source includes lg_internal.h, and through it lg_common.h and the public header: all headers are every object's dependencies
+    headers = sorted(glob.glob(os.path.join(HERE, "*.h"))) + [os.path.join(os.path.dirname(PKG), "include", "littlegan_hip.h")]
 
     # LG_EXTRA_FLAGS carries the ablation macros of scripts/probe/*.sh ("results wrong, timing only"): the flag set an object
     # was built with is recorded beside it, and an object (hence the library) built with OTHER flags is stale — a probe build
@@ -66,7 +63,7 @@ def build(force=False, verbose=True, variant=None):
         o = os.path.join(objdir, src.replace(".hip", ".o"))
         fl = o + ".flags"
         same_flags = os.path.exists(fl) and open(fl).read() == flag_line
-        if force or not same_flags or _stale(o, [s] + hdrs_of(s)):
+        if force or not same_flags or _stale(o, [s] + headers):
             cmd = [hipcc] + flags + ["-c", s, "-o", o]
             if verbose:
                 print(" ".join(cmd), flush=True)

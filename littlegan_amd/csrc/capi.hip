@@ -2,8 +2,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include "lg_common.h"
-#include "../../include/littlegan_hip.h"
+#include "lg_internal.h"
 
 static thread_local char g_err[512] = "";
 
@@ -20,30 +19,6 @@ extern "C" const char* lg_last_kernel(void) { return g_kernel; }
 extern "C" int lg_clear_kernel(void) { g_kernel = ""; return LG_OK; }
 extern "C" int lg_abi_version(void) { return LG_ABI_VERSION; }
 
-extern "C" int lg_conv_igemm(int mode, int dtype, const float* src, const void* wpack, const float* bias, float* out,
-                             int B, int Hm, int Wm, int Cs, int N, int act, int pstride, int ppad, void* stream);
-extern "C" int lg_conv_igemm_ex(int mode, int dtype, const float* src, const void* src16, const void* wpack,
-                                const float* bias, float* out, void* out16, int B, int Hm, int Wm, int Cs, int N, int act,
-                                int pstride, int ppad, void* spart, size_t spart_bytes, int* nparts_out, void* stream);
-extern "C" int lg_conv_wgrad_m16(const float* big, const void* big16, const float* small, const void* small16, float* dw,
-                                 void* workspace, size_t ws_bytes, int B, int Hm, int Wm, int cb, int cs, int pstride,
-                                 int ppad, int accumulate, int dtype, void* stream);
-extern "C" size_t lg_conv_pack_up_offset(int cb, int cs, int dtype);
-extern "C" size_t lg_conv_pack_raw_offset(int cb, int cs, int dtype);
-extern "C" int lg_n3_s1t_fwd_try(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int C,
-                                 void* stream);
-extern "C" int lg_n3_up_try(const float* src, const float* w, float* out, int B, int H, int W, int C, void* stream);
-extern "C" int lg_n3_p16_supported(int H, int W, int C);
-extern "C" int lg_n3_s1t_fwd_p16_try(const void* x16, const float* w, const float* bias, float* y, int B, int H, int W,
-                                     int C, void* stream);
-extern "C" int lg_n3_up_p16_try(const void* src16, const float* w, float* out, int B, int H, int W, int C, void* stream);
-extern "C" int lg_n3_conv1_fwd_p16_try(const float* img, const float* w, const float* bias, float* z, void* z16, int B, int H,
-                                       int W, int N, void* spart, size_t spart_bytes, int* nparts, void* stream);
-extern "C" int lg_n3_s1_dgrad_p16_try(const float* dpre, const float* w, float* dx, void* dx16, int B, int H, int W, int N,
-                                      void* stream);
-extern "C" int lg_n3_rows_supported(int H, int W, int C);
-extern "C" int lg_n3_s1t_fwd_rows_try(const void* x16, const float* stats, float alpha, const float* w, const float* bias, float* y,
-                                      int B, int H, int W, int C, void* stream);
 extern "C" int lg_n3_enabled(void) {
   static int v = -1;
   if (v < 0) v = lg_env_flag("LG_NO_N3") ? 0 : 1;  // kill switch of the 3-channel kernels (cached: per-launch path)
@@ -52,18 +27,9 @@ extern "C" int lg_n3_enabled(void) {
 static inline const float* raw_pack(const void* pack, int cb, int cs, int dtype) {
   return (const float*)((const char*)pack + lg_conv_pack_raw_offset(cb, cs, dtype));
 }
-extern "C" int lg_conv_wgrad(const float* big, const float* small, float* dw, void* workspace, size_t ws_bytes, int B,
-                             int Hm, int Wm, int cb, int cs, int pstride, int ppad, int accumulate, int dtype,
-                             void* stream);
-
-enum { MODE_DOWN = 0, MODE_UP = 1, MODE_S1T = 2, MODE_PATCH = 3 };
-
 static inline const void* up_pack(const void* pack, int cb, int cs, int dtype) {
   return (const char*)pack + lg_conv_pack_up_offset(cb, cs, dtype);
 }
-
-extern "C" int lg_conv_halo_supported(int mode, int dtype, int B, int Hm, int Wm, int Cs, int N);
-extern "C" int lg_n3_conv1_p16_supported(int H, int W, int N);
 
 // 1 if lg_conv2d_s2_fwd_stats (up == 0) / lg_convT_s2_fwd_stats (up == 1) on this shape returns fused moment partials
 // (*nparts > 0) when given a workspace of lg_conv_stats_workspace_bytes: the kernel's tiling puts one sample per block.
@@ -123,9 +89,6 @@ extern "C" int lg_conv2d_s2_fwd_stats(const float* x, const void* x16, const voi
 // lg_instnorm_leaky_apply_z16's output), the normalised map is never written.  For passes whose normalised maps have no other
 // reader (no weight gradient of this layer, no skip use): the discriminator run on the Adjuster's output.  The result is bf16
 // (y16) with fused moment partials, as lg_conv2d_s2_fwd_stats on the bf16 path.  LG_ERR_UNSUPPORTED unless ..._zn_supported.
-extern "C" int lg_conv_down3_zn_supported(int B, int Hm, int Wm, int Cs, int N);
-extern "C" int lg_conv_down3_zn_try(const void* z16, const float* zstats, float alpha, const void* wpack, const float* bias, void* out16,
-                                    int B, int Hm, int Wm, int Cs, int N, void* spart, size_t spart_bytes, int* nparts_out, void* stream);
 extern "C" int lg_conv2d_s2_fwd_stats_zn_supported(int B, int Hs, int Ws, int cb, int cs, int dtype) {
   return (dtype == LG_DT_BF16 && cb != 3 && lg_halo_enabled() && lg_conv_down3_zn_supported(B, Hs, Ws, cb, cs)) ? 1 : 0;
 }
@@ -175,18 +138,6 @@ extern "C" int lg_convT_s2_dgrad_m16(const float* dy, const void* dy16, const vo
 // per-sample sums over (z, g).  Given that layer's bf16 conv output z16 and statistics records, the kernels that cover
 // the shape add the sums to their epilogue: *nparts > 0 records per sample in part ([B][*nparts][2] doubles), to be
 // handed to lg_instnorm_leaky_bwd_z16_p.  *nparts == 0: not produced (shape not covered) - run the ordinary backward.
-extern "C" int lg_conv_up3_nf_try(const void* src16, const void* wpack_up, const float* bias, void* out16, int B, int Hm, int Wm,
-                                  int Cs, int N, void* spart, size_t spart_bytes, int* nparts_out, const LgNormFuse* nf,
-                                  size_t nf_bytes, void* stream);
-extern "C" int lg_conv_up4_nf_try(const void* src16, const void* wpack_up, const float* bias, void* out16, int B, int Hm, int Wm,
-                                  int Cs, int N, void* spart, size_t spart_bytes, int* nparts_out, const LgNormFuse* nf,
-                                  size_t nf_bytes, void* stream);
-extern "C" int lg_conv_down3_nf_try(const void* src16, const void* wpack, const float* bias, void* out16, int B, int Hm, int Wm,
-                                    int Cs, int N, void* spart, size_t spart_bytes, int* nparts_out, const LgNormFuse* nf,
-                                    size_t nf_bytes, void* stream);
-extern "C" int lg_n3_s1_dgrad_p16_nf_try(const float* dpre, const float* w, float* dx, void* dx16, int B, int H, int W, int N,
-                                         const LgNormFuse* nf, size_t nf_bytes, int* nparts_out, void* stream);
-
 extern "C" int lg_conv2d_s2_dgrad_nf(const void* dy16, const void* pack, void* dx16, int B, int Hs, int Ws, int cb, int cs,
                                      const void* z16, const float* stats, float alpha, void* part, size_t part_bytes,
                                      int* nparts, void* stream) {
@@ -219,10 +170,6 @@ extern "C" int lg_convT_s2_dgrad_nf(const void* dy16, const void* pack, void* dx
   return lg_convT_s2_dgrad_m16(nullptr, dy16, pack, nullptr, dx16, B, Hs, Ws, cb, cs, LG_DT_BF16, stream);
 }
 
-extern "C" int lg_conv_down3_bn_supported(int B, int Hm, int Wm, int Cs, int N);
-extern "C" int lg_conv_down3_bn_try(const void* z16, const void* g16, const float* bcoef, float alpha, const void* wpack, void* out16,
-                                    int B, int Hm, int Wm, int Cs, int N, int* nparts_out, const LgNormFuse* nf, size_t nf_bytes,
-                                    void* stream);
 extern "C" int lg_convT_s2_dgrad_bn_supported(int B, int Hs, int Ws, int cb, int cs) {
   return cb != 3 ? lg_conv_down3_bn_supported(B, Hs, Ws, cb, cs) : 0;
 }
@@ -348,10 +295,6 @@ extern "C" size_t lg_convT_s1_bwd_workspace_bytes(int B, int H, int W, int cb, i
   size_t b = 512 * 3 * sizeof(float);
   return a > b ? a : b;
 }
-
-extern "C" int lg_convT_s1_tanh_bwd_m16(const float* x, const void* x16, const float* dpre, const void* pack, float* dx,
-                                        void* dx16, float* dw, float* db, void* workspace, size_t ws_bytes, int B, int H,
-                                        int W, int cb, int cs, int accumulate, int dtype, void* stream);
 
 extern "C" int lg_convT_s1_tanh_bwd(const float* x, const float* dpre, const void* pack, float* dx, float* dw, float* db,
                                     void* workspace, size_t ws_bytes, int B, int H, int W, int cb, int cs,

@@ -21,7 +21,7 @@
 //   * the InstanceNormalization moments of the tile ({count, mean, M2}, instance.py:114-115) come out of the same
 //     registers, so no pass re-reads the output.
 #include <type_traits>
-#include "lg_common.h"
+#include "lg_internal.h"
 
 namespace {
 

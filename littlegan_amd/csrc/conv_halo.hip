@@ -11,13 +11,10 @@
 // operand of an MFMA with one coalesced global_load_dwordx4 per lane, two taps ahead, and the tap loop has NO
 // barrier — the only block-wide synchronisation is the halo restage once per channel chunk.
 // Falls back (LG_ERR_UNSUPPORTED) to the per-tap gather kernel for shapes the tiling does not cover.
-#include "lg_common.h"
-
-extern "C" int lg_device_cus(void);
+#include "lg_internal.h"
 
 namespace {
 
-enum { MODE_DOWN = 0, MODE_UP = 1, MODE_S1T = 2 };
 // DOWN from the bf16 mirror with 32-channel chunks keeps its halo rows UNPADDED (64 B) and XOR-swizzled instead of
 // padded to 80 B: 665 rows x 64 B = 42.5 KB, so THREE blocks fit a CU's 160 KB (the padded image allowed two), and the
 // 128x32 wave tile of that variant is compiled for 3 waves per SIMD (161 VGPRs, no spills).  The A fragments of
@@ -694,8 +691,6 @@ int dispatch(const HaloParams& p, int dtype, hipStream_t st) {
 inline bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
 }  // namespace
-
-extern "C" int lg_npad(int n);
 
 // Returns LG_OK if the halo kernel was launched, LG_ERR_UNSUPPORTED if the caller must use the gather kernel.
 // spart/spart_bytes/nparts_out (optional): if the tiling puts ONE sample per block, the kernel also writes per-block

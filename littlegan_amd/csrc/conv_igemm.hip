@@ -18,11 +18,9 @@
 // bf16 one v_mfma_f32_32x32x16_bf16; A and B use the same k assignment, so the sum is exact.
 // Register-prefetch double buffering: tile k+1's global loads are in flight during tile k's MFMAs.
 #include <stdlib.h>
-#include "lg_common.h"
+#include "lg_internal.h"
 
 namespace {
-
-enum { MODE_DOWN = 0, MODE_UP = 1, MODE_S1T = 2, MODE_PATCH = 3 };
 
 struct ConvParams {
   const float* src;
@@ -329,10 +327,6 @@ int dispatch_dtype(const ConvParams& p, int dtype, hipStream_t st) {
 
 }  // namespace
 
-extern "C" int lg_conv_halo_try(int mode, int dtype, const float* src, const void* src16, const void* wpack,
-                                const float* bias, float* out, void* out16, int B, int Hm, int Wm, int Cs, int N, int act, void* spart,
-                                size_t spart_bytes, int* nparts_out, void* stream);
-
 extern "C" int lg_halo_enabled(void) {
   static int v = -1;
   if (v < 0) v = lg_env_flag("LG_NO_HALO") ? 0 : 1;  // kill switch: LG_NO_HALO=1 forces the per-tap gather kernel (cached: per-launch path)
@@ -350,16 +344,6 @@ extern "C" int lg_npad(int n) {
 //   mode 1 UP  : src [B,Hm,Wm,Cs]   -> out [B,2Hm,2Wm,N]
 //   mode 2 S1T : src [B,Hm,Wm,Cs]   -> out [B,Hm,Wm,N]   (+ optional tanh)
 //   mode 3 PATCH: src [B,Hs,Ws,3], stride s, pad p -> out [B,Hm,Wm,N]; wp = [5][Npad][16]
-extern "C" int lg_conv_igemm_ex(int mode, int dtype, const float* src, const void* src16, const void* wpack,
-                                const float* bias, float* out, void* out16, int B, int Hm, int Wm, int Cs, int N, int act,
-                                int pstride, int ppad, void* spart, size_t spart_bytes, int* nparts_out, void* stream);
-extern "C" int lg_conv_up4_try(const void* src16, const void* wpack_up, const float* bias, void* out16, int B, int Hm, int Wm,
-                               int Cs, int N, void* spart, size_t spart_bytes, int* nparts_out, void* stream);
-extern "C" int lg_conv_up3_try(const void* src16, const void* wpack_up, const float* bias, void* out16, int B, int Hm, int Wm,
-                               int Cs, int N, void* spart, size_t spart_bytes, int* nparts_out, void* stream);
-extern "C" int lg_conv_down3_try(const void* src16, const void* wpack, const float* bias, void* out16, int B, int Hm, int Wm,
-                                 int Cs, int N, void* spart, size_t spart_bytes, int* nparts_out, void* stream);
-
 extern "C" int lg_conv_igemm(int mode, int dtype, const float* src, const void* wpack, const float* bias, float* out,
                              int B, int Hm, int Wm, int Cs, int N, int act, int pstride, int ppad, void* stream) {
   return lg_conv_igemm_ex(mode, dtype, src, nullptr, wpack, bias, out, nullptr, B, Hm, Wm, Cs, N, act, pstride, ppad,

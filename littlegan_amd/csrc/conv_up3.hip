@@ -30,7 +30,7 @@
 //     153.6 us), a start delay of the second workgroup of a CU (141.6 / 143.2 / 143.0 / 145.1 us for 0 / 5 / 9 / 13 k cycles).
 #include <type_traits>
 #include <utility>
-#include "lg_common.h"
+#include "lg_internal.h"
 
 namespace {
 
@@ -522,9 +522,6 @@ static U3Tiling up3_tiling(int B, int Hm, int Wm, int Cs, int N) {
 extern "C" int lg_conv_up3_supported(int B, int Hm, int Wm, int Cs, int N) { return up3_tiling(B, Hm, Wm, Cs, N) != U3_NONE ? 1 : 0; }
 
 // LG_OK: launched.  LG_ERR_UNSUPPORTED: the caller falls back to conv_halo.hip.  *nparts_out = records per sample (tiles).
-extern "C" int lg_conv_up3_nf_try(const void* src16, const void* wpack_up, const float* bias, void* out16, int B, int Hm, int Wm,
-                                  int Cs, int N, void* spart, size_t spart_bytes, int* nparts_out, const LgNormFuse* nf,
-                                  size_t nf_bytes, void* stream);
 extern "C" int lg_conv_up3_try(const void* src16, const void* wpack_up, const float* bias, void* out16, int B, int Hm, int Wm,
                                int Cs, int N, void* spart, size_t spart_bytes, int* nparts_out, void* stream) {
   return lg_conv_up3_nf_try(src16, wpack_up, bias, out16, B, Hm, Wm, Cs, N, spart, spart_bytes, nparts_out, nullptr, 0, stream);

@@ -19,7 +19,7 @@
 //   * the ring holds 8 fragments (12 for the 9-tap class, whose 36 fragments per slice are not a multiple of 8), so the ring
 //     position of a fragment is a compile-time register.
 #include <type_traits>
-#include "lg_common.h"
+#include "lg_internal.h"
 
 namespace {
 

@@ -5,7 +5,7 @@
 //   dense_fwd    : y[B,N] = x[B,K] @ w[K,N] + bias          (K small, N wide)
 //   dense_wgrad  : dw[K,N] = x^T @ dy, db[N] = colsum(dy)
 // (the D heads live in heads.hip)
-#include "lg_common.h"
+#include "lg_internal.h"
 
 namespace {
 
@@ -161,11 +161,6 @@ extern "C" int lg_adj_conditions(const float* first, const float* second, float*
   lg_note_kernel("adj_conditions_kernel");
   return LG_OK;
 }
-
-extern "C" int lg_dense_fwd_mfma_try(const float* x, const float* w, const float* bias, float* y, int B, int K, int N,
-                                     void* stream);
-extern "C" int lg_dense_wgrad_mfma_try(const float* x, const float* dy, float* dw, float* db, int B, int K, int N, int accumulate,
-                                       void* stream);
 
 extern "C" int lg_dense_fwd(const float* x, const float* w, const float* bias, float* y, int B, int K, int N,
                             void* stream) {

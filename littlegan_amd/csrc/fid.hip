@@ -6,7 +6,7 @@
 // of its 4 waves accumulates a 32 x 32 sub-tile (2 x 2 MFMA tiles, 4 fp64 accumulators per lane each).
 // The D x D matrix square root of the Fréchet distance (fid.py:144-163) stays on the host (scipy), as in the reference, unless the
 // caller asks for the device iteration of fid_sqrt.hip.  fid_accum_kernel / fid_finalize_kernel below are the streamed, mergeable form.
-#include "lg_common.h"
+#include "lg_internal.h"
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 

@@ -4,7 +4,7 @@
 // Only the trace is needed.  The work is a general fp64 D x D x D GEMM on v_mfma_f64_16x16x4_f64 (64 x 64 output tiles, 4 waves of
 // 32 x 32, epilogue C = alpha A B + beta I so that T is one launch; Y T and T Z share a launch) plus fixed-order trace / norm kernels:
 // no atomics anywhere, the result is bit-reproducible.
-#include "lg_common.h"
+#include "lg_internal.h"
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 

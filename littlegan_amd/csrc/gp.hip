@@ -10,10 +10,7 @@
 // InstanceNormalization per sample (axis=None): c = z - mu, sigma = sqrt(mean c^2), s = sigma + 1e-3, n = gamma c / s + beta,
 // x = leaky(n), m = leaky'(n), gn = m g.  Statistics records [B][8] = {mu_hi, sigma, a, beta, mu_lo, ...} (norm.hip).
 // Every reduction has a fixed order (per-block fp64 partials, merged in index order): bit-deterministic, no atomics.
-#include "lg_common.h"
-
-#define LG_IN_EPS 1e-3f
-#define LG_NSTAT 8
+#include "lg_internal.h"
 
 namespace {
 

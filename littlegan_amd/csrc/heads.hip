@@ -6,7 +6,7 @@
 //   heads_fwd   : block = 16 samples x 256 k (split-K over blocks), x tile in LDS; partials + heads_final (bias, sigmoid)
 //   heads_dgrad : dx[b][k] = dz[b][:] . [wpr[k] | wc[k][:]]          (thread per k)
 //   heads_wgrad : lanes = k, dz rows wave-uniform; block owns 64 k's, its 4 waves split the batch
-#include "lg_common.h"
+#include "lg_internal.h"
 
 namespace {
 
@@ -192,13 +192,6 @@ __global__ __launch_bounds__(256) void heads_wgrad_kernel(const float* __restric
 }
 
 }  // namespace
-
-extern "C" int lg_heads_fwd_mfma_try(const float* x, const float* wpr, const float* wc, float* part, int B, int K, int c,
-                                     int* nkc_out, void* stream);
-extern "C" int lg_heads_wgrad_mfma_try(const float* x, const float* dz, float* dwpr, float* dbpr, float* dwc, float* dbc, int B,
-                                       int K, int c, int accumulate, void* stream);
-extern "C" int lg_heads_dgrad_mfma_try(const float* dz, const float* wpr, const float* wc, float* dx, int B, int K, int c,
-                                       void* stream);
 
 extern "C" size_t lg_heads_fwd_workspace_bytes(int B, int K, int c) {
   return (size_t)lg_cdiv(K, FKC) * (size_t)B * (size_t)(c + 1) * sizeof(float);

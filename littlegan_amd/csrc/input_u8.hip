@@ -7,6 +7,7 @@
 // All three produce, bit for bit, what the float32 path produces from the rescaled copy of the same rows; the shared
 // device code and the argument for the augmentation are in augment_core.h.  HBM-bound streaming work: no MFMA, no LDS
 // beyond the mean pass's staging tile.
+#include "lg_internal.h"
 #include "augment_core.h"
 
 namespace {

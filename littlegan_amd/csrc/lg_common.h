@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/littlegan_hip.h"   // LG_OK / LG_ERR_* / LG_DT_* and the public entry points: every definition sees its declaration
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -12,13 +13,9 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-#define LG_OK 0
-#define LG_ERR_ARG (-1)
-#define LG_ERR_LAUNCH (-2)
-#define LG_ERR_UNSUPPORTED (-3)
-
-#define LG_DT_F32 0
-#define LG_DT_BF16 1
+// InstanceNormalization (norm.hip, gp.hip): floats per statistics record, and the epsilon of a = gamma / (sigma + eps)
+#define LG_NSTAT 8
+#define LG_IN_EPS 1e-3f
 
 extern "C" void lg_set_error(const char* fmt, ...);
 // Names the kernel template a conv / weight-gradient / dense / head entry point has just launched (thread-local, static strings only):
@@ -34,8 +31,6 @@ extern "C" int lg_env_flag(const char* name);
 // every shape of conv_halo.hip), LG_NO_N3 (capi.hip: the generic kernels take the 3-channel layers).  1 = the kernels are in use.
 extern "C" int lg_halo_enabled(void);
 extern "C" int lg_n3_enabled(void);
-// CUs the persistent kernels may fill: device CUs minus those reserved for communication kernels (lg_set_reserved_cus)
-extern "C" int lg_grid_cus(void);
 
 #define LG_CHECK_ARG(cond, ...)            \
   do {                                     \

@@ -9,7 +9,7 @@
 //   clip_adam : tf.clip_by_value (eager_trainer.py:146-148) + tf.compat.v1.train.AdamOptimizer
 //               (eager_trainer.py:28-30,164-168): lr_t = lr*sqrt(1-b2^t)/(1-b1^t), eps outside sqrt,
 //               one beta-power pair per optimizer kept on the device so the step replays as a graph.
-#include "lg_common.h"
+#include "lg_internal.h"
 
 #define LG_BCE_EPS 1e-7f
 

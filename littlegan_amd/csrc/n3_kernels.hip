@@ -5,7 +5,7 @@
 //   n3_s1t_fwd : y[B,H,W,3] = tanh(convT_s1(x[B,H,W,C]) + b)            /root/reference/model.py:86-87,104
 //   n3_up      : dimg[B,2H,2W,3] = conv2d_backprop_input(dz[B,H,W,C])   (gradient of Encoder.conv1, model.py:15)
 //   n3_wgrad   : dW[5][5][3][C] (+)= sum big3[s*o + k - pad][c3] * small[o][c]   (conv1: s=2,pad=1; final: s=1,pad=2)
-#include "lg_common.h"
+#include "lg_internal.h"
 
 namespace {
 

@@ -13,7 +13,7 @@
 // Weights come from the verbatim fp32 copy in the pack (pack.hip, cb == 3) and are rounded to bf16 (RNE) here, the
 // same rounding the packed MFMA operands get; accumulation is fp32 throughout.
 #include <type_traits>
-#include "lg_common.h"
+#include "lg_internal.h"
 
 #ifndef LG_P16_DBG
 #define LG_P16_DBG 0   // compile-time ablation bits (timing only, results wrong).  patch_p16: 1 no image loads, 2 no output stores, 4 no MFMA, 8 no moments;
@@ -465,8 +465,6 @@ extern "C" int lg_n3_conv1_fwd_p16_try(const float* img, const float* w, const f
 }
 
 // data gradient of the final stride-1 layer: dpre [B,H,W,3] fp32 -> dx [B,H,W,32] as bf16 (dx16) or fp32 (dx)
-extern "C" int lg_n3_s1_dgrad_p16_nf_try(const float* dpre, const float* w, float* dx, void* dx16, int B, int H, int W, int N,
-                                         const LgNormFuse* nf, size_t nf_bytes, int* nparts_out, void* stream);
 extern "C" int lg_n3_s1_dgrad_p16_try(const float* dpre, const float* w, float* dx, void* dx16, int B, int H, int W, int N,
                                       void* stream) {
   return lg_n3_s1_dgrad_p16_nf_try(dpre, w, dx, dx16, B, H, W, N, nullptr, 0, nullptr, stream);

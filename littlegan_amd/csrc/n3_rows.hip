@@ -16,7 +16,7 @@
 // formed while staging (same arithmetic, same rounding as apply16_kernel in norm.hip) — the stand-alone apply pass and the
 // h16 tensor of the 128x128x32 map disappear.
 #include <type_traits>
-#include "lg_common.h"
+#include "lg_internal.h"
 
 namespace {
 

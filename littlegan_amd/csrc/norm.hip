@@ -15,11 +15,8 @@
 // All kernels are HBM-bound: 16-B vector loads, one pass over x for the moments (values kept in registers).
 // The encoder's live dropout (dropout_train) rides on the same passes: dropped twins of apply / bwd regenerate the mask from a
 // Philox counter in registers (DropK below); the mask-free kernels are the DROP = false instances of the shared bodies.
-#include "lg_common.h"
+#include "lg_internal.h"
 #include "philox.h"
-
-#define LG_IN_EPS 1e-3f
-#define LG_NSTAT 8
 
 namespace {
 
@@ -846,7 +843,6 @@ constexpr long long EW_MAX_BLOCKS = 8192;
 // the backward apply (71 VGPRs: 7 blocks per CU = 1792 resident) was launched as 2046 blocks = one round + 254 blocks, 14 % of a
 // round at the price of one (1533 = six per CU beat both 2046 and 1023; C3 step -0.9 %).  A grid
 // beyond one round is cut to a whole number of rounds of the kernel's own residency (occupancy query, once per kernel).
-extern "C" int lg_device_cus(void);
 #define LG_RESIDENT_BLOCKS(kern)                                                                                       \
   ([]() -> long long {                                                                                                 \
     static long long r = 0;                                                                                            \
@@ -890,6 +886,10 @@ int drop_args(const char* who, const long long* key, int call, int level, int r0
   return LG_OK;
 }
 
+__global__ void dropout_key_kernel(unsigned long long* __restrict__ key, unsigned long long seed, unsigned long long key_offset) {
+  if (threadIdx.x == 0) { key[0] = seed; key[1] = key_offset; }
+}
+
 }  // namespace
 
 extern "C" int lg_instnorm_stats_stride(void) { return LG_NSTAT; }
@@ -900,9 +900,6 @@ extern "C" size_t lg_instnorm_workspace_bytes(int B, long long L) {
 }
 
 // stats[B][8] = {mu_hi, sigma, a, beta, mu_lo, 0,0,0} of (pre_leaky ? leaky(x) : x), x = [B][L]
-extern "C" int lg_instnorm_leaky_stats_z16(const float* x, float* stats, const float* gamma, const float* beta,
-                                           void* workspace, size_t ws_bytes, int B, long long L, int pre_leaky,
-                                           float alpha, void* x16_out, void* stream);
 extern "C" int lg_instnorm_leaky_stats(const float* x, float* stats, const float* gamma, const float* beta,
                                        void* workspace, size_t ws_bytes, int B, long long L, int pre_leaky,
                                        float alpha, void* stream) {
@@ -972,10 +969,6 @@ constexpr int DB_MAX_BLOCKS = 2046;  // multiple of 3: gridDim*256 must be a mul
 extern "C" size_t lg_instnorm_bwd_db_workspace_bytes(int B, long long L, int C) {
   return lg_instnorm_workspace_bytes(B, L) + (size_t)DB_MAX_BLOCKS * (size_t)C * sizeof(float);
 }
-
-extern "C" int lg_instnorm_leaky_bwd_db(const float* x, const float* stats, const void* g, int g_is_bf16, float* dx, void* dx16,
-                                        float* dgamma, float* dbeta, float* db, int C, void* workspace, size_t ws_bytes, int B,
-                                        long long L, int pre_leaky, int post_leaky, float alpha, int accumulate, void* stream);
 
 extern "C" int lg_instnorm_leaky_bwd(const float* x, const float* stats, const void* g, int g_is_bf16, float* dx, void* dx16,
                                      float* dgamma, float* dbeta, void* workspace, size_t ws_bytes, int B, long long L, int pre_leaky,
@@ -1146,10 +1139,6 @@ extern "C" int lg_instnorm_leaky_apply_z16_p_drop(const void* z16, const void* p
   return apply16p_impl(z16, partials, nparts, gamma, beta, stats, nullptr, 0, y, y16, B, L, 1, alpha, &dk, stream);
 }
 
-extern "C" int lg_instnorm_leaky_bwd_z16_p(const void* z16, const float* stats, const void* g, int g_is_bf16, float* dx,
-                                           void* dx16, float* dgamma, float* dbeta, float* db, int C, const void* partials,
-                                           int nparts_in, void* workspace, size_t ws_bytes, int B, long long L, int pre_leaky,
-                                           int post_leaky, float alpha, int accumulate, void* stream);
 // as lg_instnorm_leaky_bwd_db with x given as bf16 (workspace: lg_instnorm_bwd_db_workspace_bytes)
 extern "C" int lg_instnorm_leaky_bwd_z16(const void* z16, const float* stats, const void* g, int g_is_bf16, float* dx,
                                          void* dx16, float* dgamma, float* dbeta, float* db, int C, void* workspace,
@@ -1274,9 +1263,6 @@ extern "C" int lg_instnorm_leaky_bwd_z16_drop(const void* z16, const float* stat
                     accumulate, &dk, stream);
 }
 
-__global__ void dropout_key_kernel(unsigned long long* __restrict__ key, unsigned long long seed, unsigned long long key_offset) {
-  if (threadIdx.x == 0) { key[0] = seed; key[1] = key_offset; }
-}
 // key[2] = {seed, key_offset} written on the device from launch scalars: the step's key without a host-to-device copy (no sync)
 extern "C" int lg_dropout_key(long long* key, unsigned long long seed, unsigned long long key_offset, void* stream) {
   LG_CHECK_ARG(key && ((uintptr_t)key & 7) == 0, "lg_dropout_key: null or misaligned pointer");

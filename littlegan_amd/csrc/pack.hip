@@ -5,9 +5,7 @@
 //              Cb == 3: patch form [5][npad(Cs)][16] row-major, k = kx*3+c, k=15 zero
 //   up pack  : n = Cb index, k = Cs index   (convT fwd / conv dgrad)
 // One pack per layer per step (weights change every step); ~90 MB of traffic for the whole model.
-#include "lg_common.h"
-
-extern "C" int lg_npad(int n);
+#include "lg_internal.h"
 
 namespace {
 

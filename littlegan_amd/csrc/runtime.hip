@@ -9,8 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <mutex>
-#include "lg_common.h"
-#include "../../include/littlegan_hip.h"
+#include "lg_internal.h"
 
 static int g_reserved_cus = 0;
 static unsigned long long* g_clock_census = nullptr;

@@ -18,7 +18,7 @@
 //   dense_fwd   B % 32 == 0 && N % 128 == 0 && K <= 144          dense_wgrad B % 32 == 0 && N % 32 == 0 && K <= 160
 // Every launcher names its kernel through lg_note_kernel (tests/test_skinny_gpu.py asserts the route of each shape).
 #include <stdlib.h>
-#include "lg_common.h"
+#include "lg_internal.h"
 
 namespace {
 

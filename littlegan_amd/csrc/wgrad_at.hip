@@ -13,7 +13,7 @@
 //     A fragment read once, used twice); tap 24 rotates — wave w runs it on k step w of every item and the 8 partial
 //     tiles are summed through LDS at the end — so every wave issues exactly 50 MFMAs per item.
 //   * output: slab[split][tap][cb][cs] (fp32), reduced in fixed order by slab_reduce4_kernel (deterministic, no atomics).
-#include "lg_common.h"
+#include "lg_internal.h"
 
 #ifndef LG_WGAT_DBG
 #define LG_WGAT_DBG 0   // timing ablations (results wrong): 1 no MFMA, 2 no fragment reads in the k loop, 4 no staging after the first item
@@ -242,7 +242,6 @@ __global__ __launch_bounds__(512) void wgrad_at_kernel(const WgAtParams p) {
   }
 }
 
-extern "C" int lg_device_cus(void);
 // The split-K plan — and with it the fp32 summation order of dW — is a function of the DEVICE, not of the CU reservation (lg_set_reserved_cus):
 // weight gradients stay bit-reproducible across reservation settings and across hipGraphs captured before a reservation changed.  With CUs
 // reserved the grid is a few blocks larger than the free CUs: a short tail, not a different result.

@@ -15,7 +15,7 @@
 //     construction, 5 LDS reads per 384 matrix cycles);
 //   * output: slab[split][tap][cb][cs] (fp32), reduced in fixed order by slab_reduce4_kernel (deterministic, no atomics).
 #include <stdlib.h>
-#include "lg_common.h"
+#include "lg_internal.h"
 
 namespace {
 
@@ -187,7 +187,6 @@ __global__ __launch_bounds__(512) void wgrad_at32_kernel(const Wg32Params p) {
   }
 }
 
-extern "C" int lg_device_cus(void);
 inline int at32_cus() { return lg_device_cus(); }   // the split plan (= summation order) depends on the device alone, see wgrad_at.hip
 
 // 0: not applicable, else the strip width (16: 16 x 4 strips; 8: whole 8-column maps, 8 rows)

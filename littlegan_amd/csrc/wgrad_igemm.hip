@@ -9,7 +9,7 @@
 // v_mfma_f32_32x32x2_f32 operand shape: lane (r,h) reads LDS[pixel 2kk+h][channel r].
 // bf16 variant: LDS holds bf16 [pixel][channel]; fragments come from ds_read_b64_tr_b16.
 #include <stdlib.h>
-#include "lg_common.h"
+#include "lg_internal.h"
 
 namespace {
 
@@ -397,15 +397,6 @@ inline int pick_nsplit(int tiles, int M, int KP, int slots) {
 
 }  // namespace
 
-extern "C" size_t lg_n3_wgrad_workspace_bytes(int B, int H, int W, int Cs);
-extern "C" int lg_n3_wgrad_try(const float* big3, const float* small, const void* small16, float* dw, void* workspace,
-                               size_t ws_bytes, int B, int H, int W, int Cs, int s, int pad, int accumulate, void* stream);
-extern "C" size_t lg_wgrad_at_workspace_bytes(int B, int Hm, int Wm, int cb, int cs);
-extern "C" int lg_wgrad_at_try(const void* big16, const void* small16, void* workspace, size_t ws_bytes, int B, int Hm, int Wm,
-                               int cb, int cs, int* nsplit_out, void* stream);
-extern "C" size_t lg_wgrad_at32_workspace_bytes(int B, int Hm, int Wm, int cb, int cs);
-extern "C" int lg_wgrad_at32_try(const float* big, const float* small, void* workspace, size_t ws_bytes, int B, int Hm, int Wm,
-                                 int cb, int cs, int* nsplit_out, void* stream);
 static size_t wgrad_ws_generic(int B, int Hm, int Wm, int cb, int cs, int dtype);
 
 extern "C" size_t lg_wgrad_workspace_bytes(int B, int Hm, int Wm, int cb, int cs, int dtype) {
@@ -428,10 +419,6 @@ static size_t wgrad_ws_generic(int B, int Hm, int Wm, int cb, int cs, int dtype)
 // dW[5][5][cb][cs] (+)= big (x) small ; big [B,s*Hm,s*Wm,cb], small [B,Hm,Wm,cs].
 // cb == 3 selects the patch form with source stride `pstride` and pad-before `ppad`
 // (conv1: 2,1 ; stride-1 final layer: 1,2); otherwise stride 2 / pad 1.
-extern "C" int lg_conv_wgrad_m16(const float* big, const void* big16, const float* small, const void* small16, float* dw,
-                                 void* workspace, size_t ws_bytes, int B, int Hm, int Wm, int cb, int cs, int pstride,
-                                 int ppad, int accumulate, int dtype, void* stream);
-
 extern "C" int lg_conv_wgrad(const float* big, const float* small, float* dw, void* workspace, size_t ws_bytes,
                              int B, int Hm, int Wm, int cb, int cs, int pstride, int ppad, int accumulate, int dtype,
                              void* stream) {
@@ -557,8 +544,6 @@ extern "C" size_t lg_bias_grad_workspace_bytes(long long M, int C) {
   return (size_t)nb * C * sizeof(float);
 }
 
-extern "C" int lg_bias_grad_m16(const float* dy, const void* dy16, float* db, void* workspace, size_t ws_bytes, long long M,
-                                int C, int accumulate, void* stream);
 // db[C] (+)= column sums of dy[M][C]
 extern "C" int lg_bias_grad(const float* dy, float* db, void* workspace, size_t ws_bytes, long long M, int C,
                             int accumulate, void* stream) {

@@ -1,8 +1,11 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library builds/loads here (no GPU needed) and
 exports every symbol include/littlegan_hip.h declares, with the parameter lists the ctypes table uses."""
 import ctypes as C
+import glob
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
@@ -92,3 +95,43 @@ def test_library_holds_no_packed_fp32_instruction(lib):
         pytest.skip("llvm-objdump not found")
     tot, per, _ = scan_pk_opsel.scan_library(os.path.join(ROOT, "littlegan_amd", "liblittlegan_hip.so"))
     assert not tot, f"packed fp32 instructions in the product library: {dict(tot)} (kernels with the failing operand form: {len(per)})"
+
+
+CSRC = os.path.join(ROOT, "littlegan_amd", "csrc")
+
+
+def _declared(path):
+    """Names of the `extern "C"` prototypes of a csrc header (a declaration ends in `;`, a definition opens a body)."""
+    text = re.sub(r"//[^\n]*", "", open(path).read())
+    return set(re.findall(r'^extern "C" [^;{]*?\b(lg_\w+)\s*\([^;{]*\)\s*;', text, flags=re.M))
+
+
+def test_kernel_files_declare_nothing_themselves():
+    """A function used across files is declared in a header (lg_internal.h, lg_common.h or the public header), nowhere else: no .hip
+    file holds a prototype of an lg_* function, and every one of them includes lg_internal.h — so each definition and each call is
+    compiled against the same declaration."""
+    files = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+    assert len(files) >= 24, files
+    for path in files:
+        text = open(path).read()
+        code = re.sub(r"//[^\n]*", "", text)
+        protos = re.findall(r"^(?![ \t#])[^;{}()=\n]*\blg_\w+\s*\([^;{}]*\)\s*;", code, flags=re.M)   # at file scope, with or without extern "C"
+        assert not protos, (os.path.basename(path), protos)
+        assert not re.search(r'^extern "C" [^{;]*;', code, flags=re.M), os.path.basename(path)
+        assert re.search(r'^#include "lg_internal\.h"', text, flags=re.M), os.path.basename(path)
+
+
+def test_exported_symbols_are_the_declared_ones(lib):
+    """The lg_* symbols the library defines are exactly the names declared in the public header, lg_internal.h and lg_common.h:
+    nothing is exported that no header declares, and no declaration is left without its definition."""
+    nm = os.path.join("/opt/rocm/lib/llvm/bin", "llvm-nm")
+    nm = nm if os.path.exists(nm) else (shutil.which("llvm-nm") or shutil.which("nm"))
+    if not nm:
+        pytest.skip("nm not found")
+    out = subprocess.run([nm, "-D", "--defined-only", os.path.join(ROOT, "littlegan_amd", "liblittlegan_hip.so")],
+                         stdout=subprocess.PIPE, text=True, check=True).stdout
+    exported = {line.split()[-1] for line in out.splitlines() if line.split() and line.split()[-1].startswith("lg_")}
+    internal = _declared(os.path.join(CSRC, "lg_internal.h")) | _declared(os.path.join(CSRC, "lg_common.h"))
+    public = set(_protos())
+    assert len(internal) >= 40 and not internal & public, internal & public
+    assert exported == public | internal, exported ^ (public | internal)
