@@ -430,6 +430,33 @@ int lg_gp_heads_seed(const float* p, const float* wpr, float* g, int B, int K, i
 int lg_gp_heads_2nd(const float* p, const float* wpr, const float* x, const float* u, float* t, float* g2, float* dwpr,
                     float* dbpr, int B, int K, int c, void* stream);
 
+/* ---- differentiable augmentation of D's inputs (diff_augment; Zhao et al. 2020; the reference has none) ---------------------- *
+ * THIS PROJECT's definition.  Per sample: image x[S][S][3] fp32 NHWC (square, S % 8 == 0, S >= 8) and a record of 8
+ * fp32 words {b, s, c, ty, tx, cy, cx, cut}, the last five small integers stored exactly.  T is, in this order,
+ *   brightness u = x + b;  saturation v = (u - mean_k u) s + mean_k u (mean over the pixel's 3 channels);  contrast
+ *   w = (v - mean v) c + mean v (mean over the sample);  translation t(y,x) = w(y+ty, x+tx) inside the image, else 0;  cutout
+ *   out(y,x) = 0 for cy - cut/2 <= y < cy - cut/2 + cut and cx - cut/2 <= x < cx - cut/2 + cut (clipped to the image), else t.
+ * The kernels evaluate the closed form, with xv = x(y+ty, x+tx), m = mean of x over the sample, K = keep(y,x) inside(y+ty, x+tx):
+ *   out_k = K (c s xv_k + c (1-s) mean_k(xv) + (1-c) m + b)
+ * and the exact adjoint, h = K g moved back to the source position, h'(y',x') = h(y'-ty, x'-tx) (0 outside):
+ *   gx_k(y',x') = c s h'_k + c (1-s) mean_k(h') + (1-c) / (3 S^2) sum_sample h.
+ * The identity record {0, 1, 1, 0, 0, 0, 0, 0} returns x and g bit for bit.  Sums are taken in a fixed order (no float atomics): the
+ * same call gives the same bits, and rows r0.. of a batch with their records give the bits those rows have in the whole batch.
+ * All arguments are checked on the host before any launch; images, records and outputs 16-byte aligned, out != in. */
+/* params[rows][8] = the records of rows r0 .. r0+rows-1 of call slot `call` (0..3; the step uses 0: D on [new_image ; fake], 1: D on
+ * the Adjuster's output) under key = {seed, key_offset} (two 64-bit words in DEVICE memory, as lg_dropout_key writes them).  Row r
+ * reads Philox blocks key_offset + ((call << 24) + r) 2 + {0, 1}; with w_j = bits_j >> 8 and u_j = w_j / 2^24 of their words 0..6:
+ *   b = u0 - 0.5, s = 2 u1, c = u2 + 0.5, ty = (w3 (2M+1) >> 24) - M, tx likewise from w4, cy = w5 (S+1 - cut%2) >> 24, cx likewise
+ *   from w6, M = S/8, cut = S/2.
+ * policy_bits: 1 color (b, s, c), 2 translation (ty, tx), 4 cutout (cy, cx, cut); a component that is not named gets its identity
+ * values (0, 1, 1 / 0, 0 / 0, 0, 0).  r0 + rows <= 2^24. */
+int lg_diffaug_draw(const long long* key, int call, int r0, int rows, int S, int policy_bits, float* params, void* stream);
+size_t lg_diffaug_workspace_bytes(int rows, int S);
+/* out[rows][S][S][3] = T(x) under params[rows][8] */
+int lg_diffaug_fwd(const float* x, const float* params, float* out, int rows, int S, void* workspace, size_t ws_bytes, void* stream);
+/* gx[rows][S][S][3] = T^T(g): the gradient w.r.t. x of <T(x), g> */
+int lg_diffaug_bwd(const float* g, const float* params, float* gx, int rows, int S, void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- run-time services (no reference counterpart: the reference has no distributed code and no clock to report) ---- */
 /* CU budget of the persistent kernels.  Under data parallelism RCCL's ring kernels occupy CUs on a side stream while the
  * backward convs run (littlegan_amd/dist.py); every persistent launcher sizes its grid to lg_grid_cus() = CUs - reserved

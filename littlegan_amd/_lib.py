@@ -127,6 +127,11 @@ SIGNATURES = {
     "lg_gp_norm_dd": (I, [P, P, P, P, P, P, P, P, P, P, Z, I, L, F, P]),
     "lg_gp_heads_seed": (I, [P, P, P, I, I, I, P]),
     "lg_gp_heads_2nd": (I, [P, P, P, P, P, P, P, P, I, I, I, P]),
+    # differentiable augmentation of D's inputs (diffaug.hip): per-row draws, T and its adjoint
+    "lg_diffaug_draw": (I, [P, I, I, I, I, I, P, P]),
+    "lg_diffaug_workspace_bytes": (Z, [I, I]),
+    "lg_diffaug_fwd": (I, [P, P, P, I, I, P, Z, P]),
+    "lg_diffaug_bwd": (I, [P, P, P, I, I, P, Z, P]),
     # packed uint8 data set: gather + rescale, labels, fused augmentation (input_u8.hip)
     "lg_rescale_u8": (I, [P, P, I, L, P, P]),
     "lg_soft_labels": (I, [P, P, P, I, I, I, P, P]),

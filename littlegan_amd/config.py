@@ -3,7 +3,9 @@ attribute, derived cond_dim / result_dir / gpu / prefetch.  Extra keys of this b
 "bf16"), synthetic (bool: use the synthetic CelebA-shaped dataset), seed, packed_path / data_resident / fuse_input
 (the packed uint8 data set, dataset.py), fid_chunk_rows / fid_device_sqrt (streamed FID statistics, device square root, fid.py), dropout_train (bool: make the encoder's
 dropout(dropout_rate) live in the training step — the reference's, and the default here, is the identity),
-ema_decay / sample_ema (exponential moving average of the weights, used for sampling and kept in checkpoints)."""
+ema_decay / sample_ema (exponential moving average of the weights, used for sampling and kept in checkpoints),
+diff_augment (comma list out of color,translation,cutout: differentiable augmentation of every image the Discriminator sees in the
+training step, the generator-side tapes differentiated through it; "" = off, the reference's step)."""
 import json
 import os
 from argparse import ArgumentParser
@@ -64,7 +66,28 @@ DEFAULTS = {
     # semantics of tf.train.ExponentialMovingAverage(ema_decay, num_updates); 0 = off.  sample_ema: predict and the sampling modes read
     # the average instead of the raw last-step weights (only when ema_decay > 0).
     'ema_decay': 0.0, 'sample_ema': True,
+    # differentiable augmentation of D's inputs (Zhao et al. 2020): a comma list out of color, translation, cutout.  The
+    # real batch, the Generator's fakes and the Adjuster's outputs are transformed per sample before D reads them, and the gen / adj
+    # tapes are differentiated through the transform.  "" = off.  Excludes use_gp and dropout_train.
+    'diff_augment': '',
 }
+
+DIFF_AUGMENT_BITS = {"color": 1, "translation": 2, "cutout": 4}
+
+
+def diff_augment_bits(policy) -> int:
+    """The diff_augment key as the policy bits of lg_diffaug_draw (1 color, 2 translation, 4 cutout); "" or None = 0 (off).
+    Raises ValueError for anything but a comma list of the three names."""
+    if policy is None:
+        return 0
+    if not isinstance(policy, str):
+        raise ValueError(f"diff_augment must be a string (a comma list out of {', '.join(DIFF_AUGMENT_BITS)}), got {policy!r}")
+    bits = 0
+    for name in (n.strip() for n in policy.split(",")) if policy.strip() else ():
+        if name not in DIFF_AUGMENT_BITS:
+            raise ValueError(f"diff_augment: unknown component {name!r} in {policy!r} (a comma list out of {', '.join(DIFF_AUGMENT_BITS)})")
+        bits |= DIFF_AUGMENT_BITS[name]
+    return bits
 
 MODES = ["train", "pack", "plot", "visual", "random-sample", "evaluate", "condition-sample", "evaluate-sample", "export-model"]
 
@@ -92,6 +115,7 @@ class Arg:
                 raise FileNotFoundError(fp)
         for k, v in vars(args).items():
             setattr(self, k, v)
+        diff_augment_bits(self.diff_augment)   # a misspelt component fails here, not at the first training step
         self.cond_dim = len(self.attr)
         self.result_dir = os.path.join(self.all_result_dir, args.exp_name)
         # the reference sets CUDA_VISIBLE_DEVICES (config.py:35); with one process per GPU the launcher

@@ -17,6 +17,7 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
+from .config import diff_augment_bits
 from .dist import GradSync
 from .model import Adjuster, Discriminator, Generator, ParamStore
 from .utils import save_image, soft
@@ -76,6 +77,16 @@ class EagerTrainer:
         if self.dropout and self.use_gp:
             raise ValueError("use_gp and dropout_train exclude each other: the penalty's double backward through a masked norm "
                              "is not built (DESIGN.md §15)")
+        # differentiable augmentation of D's inputs (the reference has none): on when diff_augment names a component
+        self.diffaug = diff_augment_bits(getattr(args, "diff_augment", ""))
+        if self.diffaug and self.use_gp:
+            raise ValueError("diff_augment and use_gp exclude each other: the penalty's double backward through the augmentation T "
+                             "is not built (DESIGN.md §18)")
+        if self.diffaug and self.dropout:
+            raise ValueError("diff_augment and dropout_train exclude each other: under diff_augment the Adjuster encodes `fake` itself "
+                             "and the masks of the rows D used to hand over are not built for that pass (DESIGN.md §18)")
+        if self.diffaug and int(getattr(args, "image_channel", 3)) != 3:
+            raise ValueError("diff_augment needs 3-channel images")
         # weight average for sampling (the reference has none): on when ema_decay > 0
         self.ema_decay = validate_ema_decay(getattr(args, "ema_decay", 0.0))
         self.sample_ema = bool(getattr(args, "sample_ema", True))
@@ -113,7 +124,7 @@ class EagerTrainer:
     def train_step_from_inputs(self, batch_no: int, inp: Dict[str, torch.Tensor]):
         """inp: real_image_1, real_cond_1, real_image_2, real_cond_2, noise, new_image (device fp32, NHWC); with use_gp also
         gp_eps [B] (the penalty's interpolation weights, U[0,1)); with dropout_train also dropout_key (int64 [2] = {seed, key_offset} of
-        the step's mask stream, draw_dropout_key).
+        the step's mask stream, draw_dropout_key); with diff_augment also diffaug_key (the same kind of pair, draw_diffaug_key).
         Returns (fake_image, adj_image|None, gen_loss, disc_loss, adj_loss|None) — losses are 1-element device tensors
         (no host sync on the hot path)."""
         a = self.args
@@ -136,6 +147,15 @@ class EagerTrainer:
                                  "{seed, key_offset}: draw_dropout_key)")
             drop = [ops.Drop(inp["dropout_key"], call, rate=self.dropout_rate) for call in range(3)]
 
+        # differentiable augmentation call slots: 0 = D on [new_image ; fake], 1 = D on the Adjuster's output.  D reads
+        # T(image); `fake` itself (the L1 term, the Adjuster's input, the returned image) stays un-augmented.
+        aug_key, S = None, img1.shape[1]
+        if self.diffaug:
+            aug_key = inp.get("diffaug_key")
+            if aug_key is None:
+                raise ValueError("train_step_from_inputs: diff_augment is on and inp has no 'diffaug_key' (int64 [2] device tensor "
+                                 "{seed, key_offset}: draw_diffaug_key)")
+
         # ---- forward: fake = G(noise, c2); D on the [new_image ; fake] batch (eager_trainer.py:134-137)
         ctx_g: dict = {}
         # D's input batch [new_image ; fake].  A caller that owns the step inputs hands the 2B-image buffer over as
@@ -154,7 +174,11 @@ class EagerTrainer:
         ctx_d: dict = {}
         run_adj = bool(a.train_adj and batch_no > 10)
         # the Adjuster reuses D's encoder maps of `fake` as its skip inputs: keep the fp32 maps only then
-        p = D.forward_packed(d_in, ctx_d, keep_maps=run_adj, drop=drop[0])  # [2B, 1+c]: rows [0,B) real, [B,2B) fake
+        if self.diffaug:
+            par0 = ops.diffaug_draw(aug_key, 0, 0, 2 * B, S, self.diffaug)
+            p = D.forward_packed(ops.diffaug_fwd(d_in, par0), ctx_d, keep_maps=False)   # the maps are those of T(fake): not handed over
+        else:
+            p = D.forward_packed(d_in, ctx_d, keep_maps=run_adj, drop=drop[0])  # [2B, 1+c]: rows [0,B) real, [B,2B) fake
 
         # ---- disc tape (eager_trainer.py:139,145): 2*BCE(c1,real_c) + BCE(.98,real_pr) + BCE(.02,fake_pr)
         dz = torch.empty(2 * B, 1 + c, dtype=torch.float32, device=self.device)
@@ -175,6 +199,8 @@ class EagerTrainer:
         dz_g = torch.empty(B, 1 + c, dtype=torch.float32, device=self.device)
         ops.bce_heads_loss(p[B:], c2, soft(1.0), 1.0, 1.0, self.losses["gen"], dz_g, False)
         g_img = D.backward(ctx_d, dz_g, need_wgrad=False, need_input_grad=True, rows=slice(B, 2 * B))
+        if self.diffaug:
+            g_img = ops.diffaug_bwd(g_img, par0[B:])   # the gen tape is differentiated through T: rows B..2B of slot 0
         dpre = torch.empty_like(g_img)
         ops.l1_tanh_loss(img2, fake, g_img, dpre, self.losses["gen"], a.l1_lambda, True)
         rng_g = train_weight_range(a, "G", batch_no)
@@ -186,16 +212,26 @@ class EagerTrainer:
         if run_adj:
             adj_t_cond, adj_in_cond = ops.adj_conditions(c2, c1)   # concat([c2, c1], 0) and (that + 1) * 0.5, one launch
             ctx_a: dict = {}
-            # encoder(fake) was computed by D above with the same weights: hand its 4 maps to the Adjuster
-            tails = [m[B:] for m in ctx_d["enc_maps"]]  # fp32 maps (f32 path) / bf16 mirrors + the fp32 top map (bf16 path)
+            # encoder(fake) was computed by D above with the same weights: hand its 4 maps to the Adjuster.  Under diff_augment D
+            # encoded T(fake), so `fake` is encoded here, by one more B-row pass whose maps take the same place
+            if self.diffaug:
+                tails = A.encoder(fake)
+            else:
+                tails = [m[B:] for m in ctx_d["enc_maps"]]  # fp32 maps (f32 path) / bf16 mirrors + the fp32 top map (bf16 path)
             # Adjuster input = [img1 ; fake]: with the encoder maps of `fake` handed over, only img1 is encoded here (dropout: the
             # handed-over maps keep the masks call 0 drew for them — no tape differentiates through the skips)
             adj_image = A([img1, adj_in_cond], ctx_a, enc_tails=tails, drop=drop[1])
             ctx_d2: dict = {}
-            p_a = D.forward_packed(adj_image, ctx_d2, keep_maps=False, top_only=True, drop=drop[2])
+            if self.diffaug:
+                par1 = ops.diffaug_draw(aug_key, 1, 0, 2 * B, S, self.diffaug)
+                p_a = D.forward_packed(ops.diffaug_fwd(adj_image, par1), ctx_d2, keep_maps=False, top_only=True)
+            else:
+                p_a = D.forward_packed(adj_image, ctx_d2, keep_maps=False, top_only=True, drop=drop[2])
             dz_a = torch.empty(2 * B, 1 + c, dtype=torch.float32, device=self.device)
             ops.bce_heads_loss(p_a, adj_t_cond, soft(1.0), 1.0, 1.0, self.losses["adj"], dz_a, False)
             g_adj = D.backward(ctx_d2, dz_a, need_wgrad=False, need_input_grad=True)
+            if self.diffaug:
+                g_adj = ops.diffaug_bwd(g_adj, par1)
             dpre_a = torch.empty_like(g_adj)
             # target = [img2 ; img1]: one call per half instead of a 2B-image concatenation (lambda / 2 over half the elements is
             # the same scale, exactly: the element count is a multiple of a power of two)
@@ -344,6 +380,8 @@ class EagerTrainer:
             inp["gp_eps"] = self.draw_gp_eps(real_image_1.shape[0])
         if self.dropout:
             inp["dropout_key"] = self.draw_dropout_key()
+        if self.diffaug:
+            inp["diffaug_key"] = self.draw_diffaug_key()
         fake, adj, lg, ld, la = self.train_step_from_inputs(batch_no, inp)
         return True, fake, adj, lg, ld, la
 
@@ -371,6 +409,8 @@ class EagerTrainer:
             inp["gp_eps"] = self.draw_gp_eps(B)
         if self.dropout:
             inp["dropout_key"] = self.draw_dropout_key()
+        if self.diffaug:
+            inp["diffaug_key"] = self.draw_diffaug_key()
         fake, adj, lg, ld, la = self.train_step_from_inputs(batch_no, inp)
         return True, fake, adj, lg, ld, la
 
@@ -420,6 +460,18 @@ class EagerTrainer:
         """dropout_key_words as the int64 [2] device tensor the norm kernels read, written on the device from launch scalars
         (lg_dropout_key): like the other draws of the step, no host-to-device copy and no host synchronisation."""
         return ops.dropout_key(*self.dropout_key_words(), device=self.device)
+
+    def diffaug_key_words(self):
+        """(seed, key_offset) of the augmentation draws of the step draw_step_inputs last drew for: the block window at 2^35 of that
+        step's counter window (0, 2^39, 2^38, 2^37 and 2^36 are the other draws').  input_step is part of the checkpoint, so a resumed
+        run continues the stream."""
+        seed = (int(getattr(self.args, "seed", 0)) << 20) ^ self.rank
+        return seed, (self._input_step << 40) + (1 << 35)
+
+    def draw_diffaug_key(self):
+        """diffaug_key_words as the int64 [2] device tensor lg_diffaug_draw reads, written on the device from launch scalars (the
+        kernel of the dropout key): no host-to-device copy and no host synchronisation."""
+        return ops.dropout_key(*self.diffaug_key_words(), device=self.device)
 
     # ------------------------------------------------------------------ eager_trainer.py:180-229
     def _interrupted(self, signum, f_name):

@@ -1067,6 +1067,50 @@ def augment_drawn(img, db_max, c_lo, c_hi, dh_max, noise_scale, seed, draw_offse
     return out
 
 
+# ------------------------------------------------------------------ differentiable augmentation of D's inputs (diffaug.hip)
+def _chk_key(key, what):
+    if not (isinstance(key, torch.Tensor) and key.is_cuda and key.dtype == torch.int64 and key.numel() == 2 and key.is_contiguous()):
+        raise ValueError(f"{what}: key must be a contiguous int64 CUDA tensor {{seed, key_offset}}")
+
+
+def diffaug_draw(key, call, r0, rows, S, policy, out=None):
+    """params [rows, 8] fp32 = the records {b, s, c, ty, tx, cy, cx, cut} of rows r0 .. r0+rows-1 of call slot `call` under the step's
+    key (int64 [2] device tensor {seed, key_offset}: dropout_key writes such a pair); policy: the diff_augment string or its bits."""
+    from .config import diff_augment_bits
+    bits = int(policy) if isinstance(policy, int) else diff_augment_bits(policy)
+    _chk_key(key, "diffaug_draw")
+    if out is None:
+        out = torch.empty(int(rows), 8, dtype=torch.float32, device=key.device)
+    _chk(out, (int(rows), 8), "out")
+    check(_lib.load().lg_diffaug_draw(_p(key), int(call), int(r0), int(rows), int(S), bits, _p(out), _stream()), "lg_diffaug_draw")
+    return out
+
+
+def _diffaug_map(fn_name, v, params, out):
+    _chk(v, name="image")
+    rows, S, W, c = v.shape
+    if W != S or c != 3:
+        raise ValueError(f"{fn_name}: square 3-channel NHWC images only, got {tuple(v.shape)}")
+    _chk(params, (rows, 8), "params")
+    if out is None:
+        out = torch.empty_like(v)
+    _chk(out, v.shape, "out")
+    lib = _lib.load()
+    ws = workspace(int(lib.lg_diffaug_workspace_bytes(rows, S)), v.device, "small")
+    check(getattr(lib, fn_name)(_p(v), _p(params), _p(out), rows, S, _p(ws), ws.numel(), _stream()), fn_name)
+    return out
+
+
+def diffaug_fwd(x, params, out=None):
+    """T(x): x [rows, S, S, 3] fp32 under params [rows, 8] (diffaug_draw, or hand-built records); see include/littlegan_hip.h"""
+    return _diffaug_map("lg_diffaug_fwd", x, params, out)
+
+
+def diffaug_bwd(g, params, out=None):
+    """The exact adjoint of diffaug_fwd: the gradient w.r.t. x of <T(x), g>"""
+    return _diffaug_map("lg_diffaug_bwd", g, params, out)
+
+
 
 # ------------------------------------------------------------------ packed uint8 data set (input_u8.hip, DESIGN.md §13)
 def _chk_rows(src, idx, name):
