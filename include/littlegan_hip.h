@@ -393,6 +393,29 @@ int lg_fid_distance(const double* mu1, const double* sigma1, const double* mu2, 
                     int D, int max_iter, double* result_host /* [4]: d2, tr_sqrt, iterations, status */,
                     void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- pairwise passes for the sample-based metrics: KID and precision / recall / density / coverage (pairs.hip) -- *
+ * The reference has no counterpart: its evaluation knows FID alone (evaluate.py, fid.py).  THIS PROJECT's definitions: KID is the
+ * unbiased MMD^2 with the polynomial kernel (Binkowski et al. 2018), precision / recall the k-NN manifold estimates of Kynkaanniemi
+ * et al. 2019, density / coverage those of Naeem et al. 2020 (metrics.py puts them together).  All three entry points walk 64 x 64
+ * tiles of dot(x_i, y_j) over x[n][D] against y[m][D] (fp32 on the device, read as fp64) on the fp64 matrix instruction; where a
+ * distance is needed, d2_ij = max(0, |x_i|^2 + |y_j|^2 - 2 dot(x_i, y_j)) with fp64 squared norms.  The n x m matrix never exists:
+ * the workspace (norms, tile partials, partial lists) is O(n + m + tiles).  No floating-point atomics: a call repeated on the same
+ * inputs gives the same bits.  n, m, D >= 1, D <= 65536; a pair of sets with more than 2^30 tiles is fed in row blocks. */
+size_t lg_pairs_workspace_bytes(long long n, long long m, int D);
+/* sums[0] += sum_ij k_ij, sums[1] += sum_i k_ii (only with diag), k_ij = (gamma dot(x_i, y_j) + coef0)^degree, 1 <= degree <= 8.
+ * diag = 1 says that x and y are the same rows (n == m).  gamma_coef0: 2 doubles in HOST memory; sums: 2 doubles on the device. */
+int lg_pairs_poly_sum(const float* x, long long n, const float* y, long long m, int D, int degree,
+                      const double* gamma_coef0 /* host [2] */, int diag, double* sums /* device [2], added to */,
+                      void* workspace, size_t ws_bytes, void* stream);
+/* best[i][0 .. kk) is the ascending list of the kk smallest d2 of row x_i over all columns seen so far: the caller sets it to +inf,
+ * every call merges the columns of its y into it.  The list is a set of smallest values: it does not depend on how the columns are
+ * divided over calls (or, inside a call, over blocks).  1 <= kk <= 16. */
+int lg_pairs_knn(const float* x, long long n, const float* y, long long m, int D, int kk,
+                 double* best /* device [n][kk], merged into */, void* workspace, size_t ws_bytes, void* stream);
+/* count[i] += #{ j : d2(q_i, ref_j) <= radius2[j] } (inclusive); int32 counters, integer adds in any order */
+int lg_pairs_ball_count(const float* q, long long n, const float* ref, long long m, const double* radius2 /* device [m] */,
+                        int D, int* count /* device [n], added to */, void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- discriminator gradient penalty (use_gp / gp_weight, sample.config.json:35-36) ------------------------------------ *
  * Replaces the NotImplementedError of eager_trainer.py:141-143 ("todo: explore how to gp on eager mode").  The reference never
  * defined the penalty; THIS PROJECT's definition (WGAN-GP, Gulrajani et al. 2017, on D's first output) is:

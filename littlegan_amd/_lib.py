@@ -110,6 +110,11 @@ SIGNATURES = {
     "lg_fid_gemm": (I, [P, P, P, I, P, P]),
     "lg_fid_distance_workspace_bytes": (Z, [I]),
     "lg_fid_distance": (I, [P, P, P, P, I, I, P, P, Z, P]),
+    # pairwise passes of KID / precision / recall / density / coverage (pairs.hip); no counterpart in the reference
+    "lg_pairs_workspace_bytes": (Z, [L, L, I]),
+    "lg_pairs_poly_sum": (I, [P, L, P, L, I, I, P, I, P, P, Z, P]),
+    "lg_pairs_knn": (I, [P, L, P, L, I, I, P, P, Z, P]),
+    "lg_pairs_ball_count": (I, [P, L, P, L, P, I, P, P, Z, P]),
     "lg_augment_drawn_workspace_bytes": (Z, [I]),
     "lg_device_cus": (I, []),
     "lg_set_reserved_cus": (I, [I]),

@@ -5,7 +5,9 @@ attribute, derived cond_dim / result_dir / gpu / prefetch.  Extra keys of this b
 dropout(dropout_rate) live in the training step — the reference's, and the default here, is the identity),
 ema_decay / sample_ema (exponential moving average of the weights, used for sampling and kept in checkpoints),
 diff_augment (comma list out of color,translation,cutout: differentiable augmentation of every image the Discriminator sees in the
-training step, the generator-side tapes differentiated through it; "" = off, the reference's step)."""
+training step, the generator-side tapes differentiated through it; "" = off, the reference's step),
+evaluate_metrics (list out of fid, kid, prdc: what `evaluate` computes; ["fid"] = the reference's run) / evaluate_real_activations (the
+real images' saved activations that kid and prdc need) / kid_subsets / kid_subset_size / prdc_k (metrics.py)."""
 import json
 import os
 from argparse import ArgumentParser
@@ -70,6 +72,10 @@ DEFAULTS = {
     # real batch, the Generator's fakes and the Adjuster's outputs are transformed per sample before D reads them, and the gen / adj
     # tapes are differentiated through the transform.  "" = off.  Excludes use_gp and dropout_train.
     'diff_augment': '',
+    # sample-based metrics beside FID: which metrics `evaluate` runs (a list out of fid, kid, prdc); the saved
+    # activations of the real images that kid / prdc compare against (the stats file holds only mu and sigma; a path, relative ones
+    # under test_data_dir); subsets and rows per subset of KID (0 subsets = one estimate over the full sets); k of the k-NN manifolds
+    'evaluate_metrics': ['fid'], 'evaluate_real_activations': None, 'kid_subsets': 100, 'kid_subset_size': 1000, 'prdc_k': 3,
 }
 
 DIFF_AUGMENT_BITS = {"color": 1, "translation": 2, "cutout": 4}
@@ -88,6 +94,22 @@ def diff_augment_bits(policy) -> int:
             raise ValueError(f"diff_augment: unknown component {name!r} in {policy!r} (a comma list out of {', '.join(DIFF_AUGMENT_BITS)})")
         bits |= DIFF_AUGMENT_BITS[name]
     return bits
+
+METRIC_NAMES = ("fid", "kid", "prdc")
+
+
+def metric_list(metrics):
+    """The evaluate_metrics key (a list of names, or a comma list in one string, as the CLI gives it) as a list without repeats.
+    Raises ValueError for an empty selection or a name outside fid, kid, prdc."""
+    if isinstance(metrics, str):
+        metrics = [n.strip() for n in metrics.split(",") if n.strip()]
+    if not isinstance(metrics, (list, tuple)) or not metrics:
+        raise ValueError(f"evaluate_metrics must be a non-empty list out of {', '.join(METRIC_NAMES)}, got {metrics!r}")
+    for name in metrics:
+        if name not in METRIC_NAMES:
+            raise ValueError(f"evaluate_metrics: unknown metric {name!r} in {metrics!r} (a list out of {', '.join(METRIC_NAMES)})")
+    return list(dict.fromkeys(metrics))
+
 
 MODES = ["train", "pack", "plot", "visual", "random-sample", "evaluate", "condition-sample", "evaluate-sample", "export-model"]
 
@@ -116,6 +138,9 @@ class Arg:
         for k, v in vars(args).items():
             setattr(self, k, v)
         diff_augment_bits(self.diff_augment)   # a misspelt component fails here, not at the first training step
+        self.evaluate_metrics = metric_list(self.evaluate_metrics)   # a misspelt metric fails here, not after the sampling run
+        if int(self.kid_subsets) < 0 or int(self.kid_subset_size) < 2 or not 1 <= int(self.prdc_k) <= 15:
+            raise ValueError("need kid_subsets >= 0, kid_subset_size >= 2 and 1 <= prdc_k <= 15")
         self.cond_dim = len(self.attr)
         self.result_dir = os.path.join(self.all_result_dir, args.exp_name)
         # the reference sets CUDA_VISIBLE_DEVICES (config.py:35); with one process per GPU the launcher

@@ -1258,6 +1258,62 @@ def fid_distance(mu1, s1, mu2, s2, max_iter=100):
     return float(res[0]), float(res[1]), int(res[2]), int(res[3])
 
 
+# ------------------------------------------------------------------ pairwise passes of the sample metrics (pairs.hip)
+def _chk_pair(x, y, who):
+    if x.dim() != 2 or y.dim() != 2 or x.shape[0] < 1 or y.shape[0] < 1 or x.shape[1] < 1 or x.shape[1] != y.shape[1]:
+        raise ValueError(f"{who}: need [n >= 1, D] and [m >= 1, D] matrices with the same D >= 1, got {tuple(x.shape)} and {tuple(y.shape)}")
+    _chk(x, name="x")
+    _chk(y, name="y")
+    return x.shape[0], y.shape[0], x.shape[1]
+
+
+def pairs_workspace_bytes(n, m, D):
+    return int(_lib.load().lg_pairs_workspace_bytes(int(n), int(m), int(D)))
+
+
+def pairs_poly_sum(x, y, sums, degree=3, gamma=None, coef0=1.0, diag=False):
+    """sums [2] (fp64 CUDA) += (sum_ij k_ij, sum_i k_ii when diag) with k_ij = (gamma x_i . y_j + coef0)^degree over x [n, D] against
+    y [m, D] (fp32 CUDA); gamma None = 1 / D.  diag says that x and y are the same rows.  Bit-reproducible."""
+    n, m, D = _chk_pair(x, y, "pairs_poly_sum")
+    if not 1 <= int(degree) <= 8:
+        raise ValueError(f"pairs_poly_sum: degree {degree} outside 1..8")
+    if diag and n != m:
+        raise ValueError(f"pairs_poly_sum: diag needs the same rows on both sides, got n={n} m={m}")
+    _chk64(sums, (2,), "sums")
+    import ctypes
+    lib = _lib.load()
+    gc = (ctypes.c_double * 2)(1.0 / D if gamma is None else float(gamma), float(coef0))
+    ws = workspace(int(lib.lg_pairs_workspace_bytes(n, m, D)), x.device, "pairs")
+    check(lib.lg_pairs_poly_sum(_p(x), n, _p(y), m, D, int(degree), ctypes.addressof(gc), int(bool(diag)), _p(sums), _p(ws), ws.numel(),
+                                _stream()), "lg_pairs_poly_sum")
+    return sums
+
+
+def pairs_knn(x, y, best):
+    """best [n, kk] (fp64 CUDA, ascending, +inf before the first call) <- the kk smallest squared distances of every row of x [n, D]
+    over its present entries and the rows of y [m, D] (fp32 CUDA).  1 <= kk <= 16."""
+    n, m, D = _chk_pair(x, y, "pairs_knn")
+    if best.dim() != 2 or not 1 <= best.shape[1] <= 16:
+        raise ValueError(f"pairs_knn: best must be [n, 1 <= kk <= 16], got {tuple(best.shape)}")
+    _chk64(best, (n, best.shape[1]), "best")
+    lib = _lib.load()
+    ws = workspace(int(lib.lg_pairs_workspace_bytes(n, m, D)), x.device, "pairs")
+    check(lib.lg_pairs_knn(_p(x), n, _p(y), m, D, int(best.shape[1]), _p(best), _p(ws), ws.numel(), _stream()), "lg_pairs_knn")
+    return best
+
+
+def pairs_ball_count(q, ref, radius2, count):
+    """count [n] (int32 CUDA) += #{ j : |q_i - ref_j|^2 <= radius2[j] } over q [n, D] against ref [m, D] (fp32 CUDA), radius2 [m] fp64."""
+    n, m, D = _chk_pair(q, ref, "pairs_ball_count")
+    _chk64(radius2, (m,), "radius2")
+    if not (count.is_cuda and count.dtype == torch.int32 and count.is_contiguous()) or tuple(count.shape) != (n,):
+        raise ValueError(f"count: need a contiguous int32 CUDA tensor of shape ({n},), got {count.dtype} {count.device} {tuple(count.shape)}")
+    lib = _lib.load()
+    ws = workspace(int(lib.lg_pairs_workspace_bytes(n, m, D)), q.device, "pairs")
+    check(lib.lg_pairs_ball_count(_p(q), n, _p(ref), m, _p(radius2), D, _p(count), _p(ws), ws.numel(), _stream()), "lg_pairs_ball_count")
+    return count
+
+
 # ------------------------------------------------------------------ discriminator gradient penalty (gp.hip)
 def gp_draw_eps(B, seed, offset, device="cuda"):
     """eps [B] ~ U[0, 1) from the counter-based generator (lg_gp_draw_eps): the interpolation weights of the penalty."""

@@ -87,12 +87,27 @@ elif args.mode == "evaluate-sample":
 elif args.mode == "evaluate":
     # main.py:82-104: FID of the evaluate-sample images (gen, and adj when the Adjuster is trained) against the pre-calculated
     # statistics <test_data_dir>/<evaluate_pre_calculated>; one log line per call in evaluate/fid-{gen,adj}.log
+    # evaluate_metrics adds KID (evaluate/kid-<kind>.log) and precision / recall / density / coverage (evaluate/prdc-<kind>.log)
+    # against the real activations evaluate_real_activations; the default ["fid"] runs the calls above and nothing else
     from littlegan_amd import fid
+    if set(args.evaluate_metrics) & {"kid", "prdc"} and not args.evaluate_real_activations:
+        raise SystemExit("evaluate_metrics kid / prdc need evaluate_real_activations (the real images' saved activations)")
     for kind in ["gen"] + (["adj"] if args.train_adj else []):
         print("Running: \"evaluate calc %s\"" % kind)
-        fid.calc(path.join(args.result_dir, "evaluate", kind), path.join(args.test_data_dir, args.evaluate_pre_calculated),
-                 path.join(args.result_dir, "evaluate", "fid-%s.log" % kind),
-                 chunk_rows=args.fid_chunk_rows, device_sqrt=args.fid_device_sqrt)   # under torchrun: each rank its share, all-reduced
+        act = path.join(args.result_dir, "evaluate", kind)
+        if "fid" in args.evaluate_metrics:
+            fid.calc(act, path.join(args.test_data_dir, args.evaluate_pre_calculated),
+                     path.join(args.result_dir, "evaluate", "fid-%s.log" % kind),
+                     chunk_rows=args.fid_chunk_rows, device_sqrt=args.fid_device_sqrt)   # under torchrun: each rank its share, all-reduced
+        if "kid" in args.evaluate_metrics:
+            from littlegan_amd import metrics
+            metrics.calc_kid(act, path.join(args.test_data_dir, args.evaluate_real_activations),
+                             path.join(args.result_dir, "evaluate", "kid-%s.log" % kind), subsets=args.kid_subsets,
+                             subset_size=args.kid_subset_size, seed=args.seed, chunk_rows=args.fid_chunk_rows)
+        if "prdc" in args.evaluate_metrics:
+            from littlegan_amd import metrics
+            metrics.calc_prdc(act, path.join(args.test_data_dir, args.evaluate_real_activations),
+                              path.join(args.result_dir, "evaluate", "prdc-%s.log" % kind), k=args.prdc_k, chunk_rows=args.fid_chunk_rows)
 elif args.mode == "condition-sample":
     args.reuse = True
     model = EagerTrainer(args, generator, discriminator, adjuster, None)
