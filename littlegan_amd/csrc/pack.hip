@@ -34,7 +34,8 @@ __global__ void pack_kernel(const float* __restrict__ w, T* __restrict__ down, T
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_down + n_up + n_raw; i += stride) {
     if (i >= n_down + n_up) {  // 3-channel layers: the verbatim fp32 copy (same launch: no runtime copy kernel in the step)
-      raw[i - n_down - n_up] = w[i - n_down - n_up];
+      const long long r = i - n_down - n_up;
+      raw[r] = r < 25ll * Cb * Cs ? w[r] : 0.f;   // n_raw counts the section's 256-byte padding: zeros, so that every byte of the pack is defined
     } else if (i < n_down) {
       float v = 0.f;
       if (Cb == 3) {  // [5][npad_s][16]
@@ -89,7 +90,7 @@ extern "C" int lg_conv_pack(const float* w, void* pack, int cb, int cs, int dtyp
   LG_CHECK_ARG(dtype == LG_DT_F32 || dtype == LG_DT_BF16, "lg_conv_pack: bad dtype %d", dtype);
   const long long nd = down_elems(cb, cs), nu = up_elems(cb, cs);
   char* up = (char*)pack + lg_conv_pack_up_offset(cb, cs, dtype);
-  const long long nr = cb == 3 ? 75ll * cs : 0;
+  const long long nr = cb == 3 ? (long long)((lg_conv_pack_bytes(cb, cs, dtype) - lg_conv_pack_raw_offset(cb, cs, dtype)) / sizeof(float)) : 0;
   float* raw = cb == 3 ? (float*)((char*)pack + lg_conv_pack_raw_offset(cb, cs, dtype)) : nullptr;
   const int blocks = (int)((nd + nu + nr + 255) / 256 < 4096 ? (nd + nu + nr + 255) / 256 : 4096);
   hipStream_t st = (hipStream_t)stream;
