@@ -1,4 +1,4 @@
-"""ctypes binding of liblittlegan_hip.so (C ABI: include/littlegan_hip.h).
+"""ctypes binding of liblittlegan_hip.so (C ABI: include/littlegan_hip.h, and include/littlegan_hip_ext.h for the lgx_ extensions).
 
 The product path has NO fallback: if the shared library is missing this module raises at
 import of the symbol table, and every op raises `LittleGanHipError` on a non-zero return.
@@ -144,6 +144,15 @@ SIGNATURES = {
     "lg_augment_drawn_u8": (I, [P, P, P, P, I, I, I, F, F, F, F, F, L, L, L, P, Z, P]),
 }
 
+# training-control extensions (include/littlegan_hip_ext.h, prefix lgx_): exported by the same library, bound beside SIGNATURES
+EXT_SIGNATURES = {
+    # adaptive augmentation probability (ada.hip): the gated draw and the controller of p; state = 16 device bytes
+    "lgx_diffaug_draw_gated": (I, [P, I, I, I, I, I, P, P, P]),
+    "lgx_ada_init": (I, [P, F, P]),
+    "lgx_ada_accumulate": (I, [P, P, I, I, P]),
+    "lgx_ada_adjust": (I, [P, I, F, F, P]),
+}
+
 
 class LittleGanHipError(RuntimeError):
     pass
@@ -177,7 +186,7 @@ def load():
     # before torch, the system runtime it links against would come in as a SECOND runtime and its kernels would see no device.
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -6,6 +6,8 @@ dropout(dropout_rate) live in the training step — the reference's, and the def
 ema_decay / sample_ema (exponential moving average of the weights, used for sampling and kept in checkpoints),
 diff_augment (comma list out of color,translation,cutout: differentiable augmentation of every image the Discriminator sees in the
 training step, the generator-side tapes differentiated through it; "" = off, the reference's step),
+diff_augment_p / ada_target / ada_interval / ada_kimg (adaptive augmentation probability: each diff_augment component is applied per
+row with probability p, fixed or driven on the device towards ada_target; null / null = every component always),
 evaluate_metrics (list out of fid, kid, prdc: what `evaluate` computes; ["fid"] = the reference's run) / evaluate_real_activations (the
 real images' saved activations that kid and prdc need) / kid_subsets / kid_subset_size / prdc_k (metrics.py)."""
 import json
@@ -72,6 +74,12 @@ DEFAULTS = {
     # real batch, the Generator's fakes and the Adjuster's outputs are transformed per sample before D reads them, and the gen / adj
     # tapes are differentiated through the transform.  "" = off.  Excludes use_gp and dropout_train.
     'diff_augment': '',
+    # adaptive augmentation probability on top of diff_augment (Karras et al. 2020): each named component is applied to
+    # each row with probability p.  diff_augment_p: the fixed (or, with ada_target, the initial) p; null = 1.0, today's path, or 0.0
+    # when ada_target is set.  ada_target: null = p stays fixed; else p is driven on the device so that E[sign(D_logit(real))] meets it
+    # (the paper uses 0.6), adjusted every ada_interval steps at a rate that takes p from 0 to 1 while D sees ada_kimg thousand real
+    # images.  Both need diff_augment to name a component.
+    'diff_augment_p': None, 'ada_target': None, 'ada_interval': 4, 'ada_kimg': 500,
     # sample-based metrics beside FID: which metrics `evaluate` runs (a list out of fid, kid, prdc); the saved
     # activations of the real images that kid / prdc compare against (the stats file holds only mu and sigma; a path, relative ones
     # under test_data_dir); subsets and rows per subset of KID (0 subsets = one estimate over the full sets); k of the k-NN manifolds
@@ -94,6 +102,38 @@ def diff_augment_bits(policy) -> int:
             raise ValueError(f"diff_augment: unknown component {name!r} in {policy!r} (a comma list out of {', '.join(DIFF_AUGMENT_BITS)})")
         bits |= DIFF_AUGMENT_BITS[name]
     return bits
+
+
+def ada_settings(diff_augment, diff_augment_p=None, ada_target=None, ada_interval=4, ada_kimg=500.0):
+    """The four keys of the adaptive augmentation probability, validated: None when the step is the plain diff_augment
+    one (diff_augment_p null or 1.0 and ada_target null: every component applied to every row), else a dict {p0, target (None = a fixed
+    p), interval, per_row} of the gated path.  Raises ValueError for a value out of range, and for diff_augment_p or ada_target set
+    while diff_augment names no component."""
+    def number(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
+            raise ValueError(f"{name} must be a number, got {v!r}")
+        return float(v)
+    if diff_augment_p is not None and not 0.0 <= number("diff_augment_p", diff_augment_p) <= 1.0:
+        raise ValueError(f"diff_augment_p must be null or satisfy 0 <= diff_augment_p <= 1, got {diff_augment_p!r}")
+    if ada_target is not None and not 0.0 < number("ada_target", ada_target) < 1.0:
+        raise ValueError(f"ada_target must be null or satisfy 0 < ada_target < 1, got {ada_target!r}")
+    if isinstance(ada_interval, bool) or not isinstance(ada_interval, int) or ada_interval < 1:
+        raise ValueError(f"ada_interval must be an integer >= 1, got {ada_interval!r}")
+    if not 0.0 < number("ada_kimg", ada_kimg) < float("inf"):
+        raise ValueError(f"ada_kimg must be a positive number, got {ada_kimg!r}")
+    import numpy as np
+    with np.errstate(over="ignore"):
+        per_row = float(np.float32(1.0 / (float(ada_kimg) * 1000.0)))
+    if not 0.0 < per_row < float("inf"):
+        raise ValueError(f"ada_kimg {ada_kimg!r}: 1 / (ada_kimg * 1000) must be a positive finite fp32 number")
+    if (diff_augment_p is not None or ada_target is not None) and not diff_augment_bits(diff_augment):
+        raise ValueError("diff_augment_p / ada_target need diff_augment to name a component: there is nothing to gate "
+                         f"(diff_augment = {diff_augment!r})")
+    if ada_target is None and (diff_augment_p is None or float(diff_augment_p) == 1.0):
+        return None
+    return {"p0": float(np.float32(0.0 if diff_augment_p is None else diff_augment_p)),
+            "target": None if ada_target is None else float(np.float32(ada_target)), "interval": int(ada_interval), "per_row": per_row}
+
 
 METRIC_NAMES = ("fid", "kid", "prdc")
 
@@ -138,6 +178,7 @@ class Arg:
         for k, v in vars(args).items():
             setattr(self, k, v)
         diff_augment_bits(self.diff_augment)   # a misspelt component fails here, not at the first training step
+        ada_settings(self.diff_augment, self.diff_augment_p, self.ada_target, self.ada_interval, self.ada_kimg)
         self.evaluate_metrics = metric_list(self.evaluate_metrics)   # a misspelt metric fails here, not after the sampling run
         if int(self.kid_subsets) < 0 or int(self.kid_subset_size) < 2 or not 1 <= int(self.prdc_k) <= 15:
             raise ValueError("need kid_subsets >= 0, kid_subset_size >= 2 and 1 <= prdc_k <= 15")

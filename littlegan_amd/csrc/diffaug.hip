@@ -21,7 +21,7 @@
 // key_offset + ((q << 24) + r) 2 + {0, 1} under the step's key {seed, key_offset} (device memory, like the dropout key); the policy acts
 // there alone — a component that is not named gets its identity values, and the passes below know no policy.
 #include "lg_internal.h"
-#include "philox.h"
+#include "diffaug_draw.h"
 
 namespace {
 
@@ -39,29 +39,13 @@ __device__ __forceinline__ bool kept(const Rec& r, int y, int x) {
 }
 __device__ __forceinline__ bool inside(int y, int x, int S) { return (unsigned)y < (unsigned)S && (unsigned)x < (unsigned)S; }
 
-// params[i] = the record of row r0 + i of call slot `call`.  w_j = bits_j >> 8 (24 bits), u_j = w_j 2^-24:
-//   b = u0 - 0.5, s = 2 u1, c = u2 + 0.5, ty = (w3 (2M+1) >> 24) - M, tx from w4, cy = w5 (S+1 - cut%2) >> 24, cx from w6; M = S/8, cut = S/2.
-// The integers come from integer arithmetic: u n in fp32 can round up to n.
+// params[i] = the record of row r0 + i of call slot `call` (diffaug_record, diffaug_draw.h)
 __global__ __launch_bounds__(256) void diffaug_draw_kernel(const unsigned long long* __restrict__ key, int call, int r0, int rows, int S,
                                                            int policy, float* __restrict__ params) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= rows) return;
-  const unsigned long long seed = key[0];
-  const unsigned long long ctr = key[1] + ((((unsigned long long)call << 24) + (unsigned long long)(r0 + i)) << 1);
-  const u4 A = philox4x32_10(u4{(unsigned)ctr, (unsigned)(ctr >> 32), 0u, 0u}, (unsigned)seed, (unsigned)(seed >> 32));
-  const u4 C = philox4x32_10(u4{(unsigned)(ctr + 1), (unsigned)((ctr + 1) >> 32), 0u, 0u}, (unsigned)seed, (unsigned)(seed >> 32));
-  const float k24 = 1.0f / 16777216.0f;
-  const int M = S / 8, cut = S / 2;
-  const bool color = policy & 1, trans = policy & 2, cutout = policy & 4;
   f32x4 p0, p1;
-  p0[0] = color ? (float)(A.x >> 8) * k24 - 0.5f : 0.f;
-  p0[1] = color ? 2.0f * ((float)(A.y >> 8) * k24) : 1.f;
-  p0[2] = color ? (float)(A.z >> 8) * k24 + 0.5f : 1.f;
-  p0[3] = trans ? (float)((int)(((unsigned long long)(A.w >> 8) * (unsigned)(2 * M + 1)) >> 24) - M) : 0.f;
-  p1[0] = trans ? (float)((int)(((unsigned long long)(C.x >> 8) * (unsigned)(2 * M + 1)) >> 24) - M) : 0.f;
-  p1[1] = cutout ? (float)(int)(((unsigned long long)(C.y >> 8) * (unsigned)(S + 1 - cut % 2)) >> 24) : 0.f;
-  p1[2] = cutout ? (float)(int)(((unsigned long long)(C.z >> 8) * (unsigned)(S + 1 - cut % 2)) >> 24) : 0.f;
-  p1[3] = cutout ? (float)cut : 0.f;
+  diffaug_record(key[0], diffaug_row_ctr(key[1], call, r0 + i), S, policy, p0, p1);
   reinterpret_cast<f32x4*>(params)[2 * i] = p0;
   reinterpret_cast<f32x4*>(params)[2 * i + 1] = p1;
 }

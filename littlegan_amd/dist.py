@@ -107,6 +107,12 @@ class GradSync:
         else:
             self._pending[name] = dist.all_reduce(buf, op=dist.ReduceOp.SUM, async_op=True)
 
+    def all_reduce_now(self, buf):
+        """All-reduce(sum) a small tensor in line with the compute stream: what is enqueued after it sees the result (the counters of
+        the augmentation controller, 8 bytes once per interval: nothing to overlap)."""
+        if self.enabled:
+            dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+
     def _wait(self, names):
         todo = [(n, self._pending.pop(n)) for n in names if n in self._pending]
         timed = self.time_waits and self.on_gpu and todo

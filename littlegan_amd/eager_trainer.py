@@ -17,7 +17,7 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from .config import diff_augment_bits
+from .config import ada_settings, diff_augment_bits
 from .dist import GradSync
 from .model import Adjuster, Discriminator, Generator, ParamStore
 from .utils import save_image, soft
@@ -87,6 +87,10 @@ class EagerTrainer:
                              "and the masks of the rows D used to hand over are not built for that pass (DESIGN.md §18)")
         if self.diffaug and int(getattr(args, "image_channel", 3)) != 3:
             raise ValueError("diff_augment needs 3-channel images")
+        # adaptive augmentation probability (the reference has none): None = every named component on every row, the
+        # plain diff_augment step with no state and no launch of its own; else the gated draw, with the controller when a target is set
+        self.ada = ada_settings(getattr(args, "diff_augment", ""), getattr(args, "diff_augment_p", None), getattr(args, "ada_target", None),
+                                getattr(args, "ada_interval", 4), getattr(args, "ada_kimg", 500.0))
         # weight average for sampling (the reference has none): on when ema_decay > 0
         self.ema_decay = validate_ema_decay(getattr(args, "ema_decay", 0.0))
         self.sample_ema = bool(getattr(args, "sample_ema", True))
@@ -106,6 +110,11 @@ class EagerTrainer:
         self.global_epoch = 1
         self._input_step = 0  # counter window of the device-side step inputs (draw_step_inputs); part of the checkpoint
         self.rank, self.world = _dist_rank_world()
+        if self.ada is not None:
+            # {p, sum of signs, rows, steps} on the device (lgx_ada_init: written from a launch scalar); _ada_steps mirrors its last
+            # word on the host, which only needs it to place the data-parallel all-reduce of the counters (_ada_control)
+            self.ada_state = ops.ada_init(self.ada["p0"], device=self.device)
+            self._ada_steps, self._ada_due, self._ada_ticked = 0, False, False
         self._init_dir()
         # eager_trainer.py:36-43: restore the newest checkpoint (weights, the three optimizers' slots and beta powers)
         # and the epoch from status.json when args.restore is set
@@ -173,10 +182,15 @@ class EagerTrainer:
         fake = G([noise, c2], ctx_g, out=d_in[B:])
         ctx_d: dict = {}
         run_adj = bool(a.train_adj and batch_no > 10)
+        adaptive = self.ada is not None and self.ada["target"] is not None
+        if adaptive and not self._ada_ticked:   # (graph_step has counted this step already, whichever way it runs it)
+            self._ada_tick()
         # the Adjuster reuses D's encoder maps of `fake` as its skip inputs: keep the fp32 maps only then
         if self.diffaug:
-            par0 = ops.diffaug_draw(aug_key, 0, 0, 2 * B, S, self.diffaug)
+            par0 = self._diffaug_draw(aug_key, 0, 2 * B, S)
             p = D.forward_packed(ops.diffaug_fwd(d_in, par0), ctx_d, keep_maps=False)   # the maps are those of T(fake): not handed over
+            if adaptive and not run_adj:   # after the step's last draw: step n + 1 is the first to see a new p
+                self._ada_control(p, B)
         else:
             p = D.forward_packed(d_in, ctx_d, keep_maps=run_adj, drop=drop[0])  # [2B, 1+c]: rows [0,B) real, [B,2B) fake
 
@@ -223,7 +237,9 @@ class EagerTrainer:
             adj_image = A([img1, adj_in_cond], ctx_a, enc_tails=tails, drop=drop[1])
             ctx_d2: dict = {}
             if self.diffaug:
-                par1 = ops.diffaug_draw(aug_key, 1, 0, 2 * B, S, self.diffaug)
+                par1 = self._diffaug_draw(aug_key, 1, 2 * B, S)
+                if adaptive:   # both draws of the step have read p: the real rows of slot 0 feed the controller
+                    self._ada_control(p, B)
                 p_a = D.forward_packed(ops.diffaug_fwd(adj_image, par1), ctx_d2, keep_maps=False, top_only=True)
             else:
                 p_a = D.forward_packed(adj_image, ctx_d2, keep_maps=False, top_only=True, drop=drop[2])
@@ -249,6 +265,35 @@ class EagerTrainer:
         self.sync.wait_all()
         self.store.bump()
         return (fake, adj_image, self.losses["gen"], self.losses["disc"], self.losses["adj"] if run_adj else None)
+
+    # ------------------------------------------------------------------ adaptive augmentation probability
+    def _diffaug_draw(self, key, call, rows, S):
+        """The records of a call slot: every named component on every row, or (gated path) each with the probability in ada_state"""
+        if self.ada is None:
+            return ops.diffaug_draw(key, call, 0, rows, S, self.diffaug)
+        return ops.diffaug_draw_gated(key, call, 0, rows, S, self.diffaug, self.ada_state)
+
+    def _ada_tick(self):
+        """Advances the host mirror of the state's step counter, once per training step: at the top of train_step_from_inputs, or at
+        the top of graph_step for a step that goes through it (eager, captured or replayed).  _ada_due: this step completes an interval."""
+        self._ada_steps += 1
+        self._ada_due = self._ada_steps >= self.ada["interval"]
+        if self._ada_due:
+            self._ada_steps = 0
+
+    def _ada_control(self, heads, B):
+        """One step of the controller on the compute stream: accumulate sign(real_pr - 0.5) over the B real rows of D's output, then
+        adjust (a no-op on the device until the interval is full).  Data parallel: on the step that completes the interval the two
+        counters {sum, rows} are all-reduced in between (8 bytes), so every rank computes the same p from the global statistic."""
+        ops.ada_accumulate(self.ada_state, heads, B)
+        if self._ada_due and self.sync.enabled:
+            self.sync.all_reduce_now(self.ada_state.view(torch.int32)[1:3])
+        ops.ada_adjust(self.ada_state, self.ada["interval"], self.ada["target"], self.ada["per_row"])
+
+    def ada_p(self):
+        """The present augmentation probability: the 1-element device view of the state's first word on the gated path (no
+        synchronisation; float() of it waits like float() of a loss), None when every component is always applied."""
+        return None if self.ada is None else self.ada_state[:1]
 
     def _apply_optimizers(self, batch_no: int, run_adj: bool):
         a, st = self.args, self.store
@@ -330,6 +375,15 @@ class EagerTrainer:
                               RuntimeWarning, stacklevel=2)
                 self._graph_dp_warned = True
             return self.train_step_from_inputs(batch_no, inp)
+        if self.ada is not None and self.ada["target"] is not None:
+            self._ada_tick()   # one training step, whether it runs eagerly, is captured and replayed, or is a replay alone
+            self._ada_ticked = True
+        try:
+            return self._graph_step(batch_no, inp)
+        finally:
+            self._ada_ticked = False
+
+    def _graph_step(self, batch_no: int, inp: Dict[str, torch.Tensor]):
         kind = self.step_kind(batch_no)
         if not hasattr(self, "_graphs"):
             self._graphs, self._graph_pool, self._graph_seen = {}, None, set()
@@ -512,7 +566,8 @@ class EagerTrainer:
                             save_image(result[2], os.path.join(a.result_dir, "train", "adj", "%d-%d.jpg" % (e, b)))
                     lg, ld = float(result[3]), float(result[4])
                     la = float(result[5]) if result[5] is not None else float("nan")
-                    print(f"  [{seen}] LossG {lg:.4f} LossD {ld:.4f} LossA {la:.4f}")
+                    aug_p = "" if self.ada is None else f" AugP {float(self.ada_p()):.4f}"   # read where the losses are: no sync of its own
+                    print(f"  [{seen}] LossG {lg:.4f} LossD {ld:.4f} LossA {la:.4f}{aug_p}")
                 if b % a.freq_test == 0 and io and self.test_cond is not None:
                     self.predict(self.test_noise, self.test_cond, self.test_image,
                                  os.path.join(a.result_dir, "test", "gen", "%d-%d.jpg" % (e, b)),
@@ -649,6 +704,8 @@ class EagerTrainer:
               "epoch": self.global_epoch, "input_step": int(self._input_step)}
         if st.ema is not None:   # the weight average and the count of averages taken (absent with ema_decay == 0; same format)
             ck["ema"], ck["ema_updates"] = st.ema.detach().cpu(), int(st.ema_updates.item())
+        if self.ada is not None:   # {p, sum, rows, steps} as its four 32-bit words (absent on the plain diff_augment path)
+            ck["ada_state"] = self.ada_state.detach().cpu().view(torch.int32)
         return ck
 
     def save_checkpoint(self, tag: str) -> str:
@@ -684,6 +741,13 @@ class EagerTrainer:
                 raise ValueError(f"{path}: weight list of {m} does not match this model configuration")
         if ck["flat"].numel() != st.flat.numel():
             raise ValueError(f"{path}: {ck['flat'].numel()} parameters, this configuration has {st.flat.numel()}")
+        ada_words = None
+        if self.ada is not None and "ada_state" in ck:   # checked before anything is loaded: the draw turns p into an integer threshold
+            ada_words = ck["ada_state"].to(torch.int32).reshape(-1)
+            p = float(ada_words[:1].view(torch.float32)) if ada_words.numel() == 4 else float("nan")
+            if not (0.0 <= p <= 1.0 and int(ada_words[2]) >= 0 and int(ada_words[3]) >= 0):
+                raise ValueError(f"{path}: ada_state {ada_words.tolist()} is not a controller state (four words with 0 <= p <= 1, "
+                                 f"rows >= 0, steps >= 0; p read as {p})")
         st.flat.copy_(ck["flat"])
         st.m.copy_(ck["adam_m"])
         st.v.copy_(ck["adam_v"])
@@ -697,6 +761,12 @@ class EagerTrainer:
             else:
                 print(f"{path}: no weight average in this checkpoint; it restarts from the loaded weights (0 updates)")
                 self.reset_ema()
+        if self.ada is not None:   # (a checkpoint's p is ignored when this run gates nothing; without one p starts as configured)
+            if "ada_state" in ck:
+                self.ada_state.view(torch.int32).copy_(ada_words)
+                self._ada_steps = int(ada_words[3])
+            else:
+                print(f"{path}: no augmentation probability in this checkpoint; it starts from the configured {self.ada['p0']}")
         st.bump()
 
     def export_model_checkpoint(self):

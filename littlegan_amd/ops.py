@@ -1111,6 +1111,65 @@ def diffaug_bwd(g, params, out=None):
     return _diffaug_map("lg_diffaug_bwd", g, params, out)
 
 
+# ------------------------------------------------------------------ adaptive augmentation probability (ada.hip)
+def _chk_ada(state, what):
+    if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype == torch.float32 and state.numel() == 4
+            and state.is_contiguous()):
+        raise ValueError(f"{what}: state must be a contiguous fp32 CUDA tensor of 4 words {{p, sum, rows, steps}} (ada_init)")
+
+
+def diffaug_draw_gated(key, call, r0, rows, S, policy, state, out=None):
+    """diffaug_draw with each named component of each row applied with probability p = state[0] (read on the device): a component that
+    is gated off gets its identity values.  p = 1 is diffaug_draw bit for bit.  See include/littlegan_hip_ext.h"""
+    from .config import diff_augment_bits
+    bits = int(policy) if isinstance(policy, int) else diff_augment_bits(policy)
+    _chk_key(key, "diffaug_draw_gated")
+    _chk_ada(state, "diffaug_draw_gated")
+    if out is None:
+        out = torch.empty(int(rows), 8, dtype=torch.float32, device=key.device)
+    _chk(out, (int(rows), 8), "out")
+    check(_lib.load().lgx_diffaug_draw_gated(_p(key), int(call), int(r0), int(rows), int(S), bits, _p(state), _p(out), _stream()),
+          "lgx_diffaug_draw_gated")
+    return out
+
+
+def ada_init(p0, device="cuda", out=None):
+    """The controller's state {p0, 0, 0, 0} (fp32 [4]: fp32 p, then the int32 sum of signs, rows and steps of the interval), written by a
+    one-block kernel from a launch scalar: no host-to-device copy."""
+    if out is None:
+        out = torch.empty(4, dtype=torch.float32, device=device)
+    _chk_ada(out, "ada_init")
+    check(_lib.load().lgx_ada_init(_p(out), float(p0), _stream()), "lgx_ada_init")
+    return out
+
+
+def ada_accumulate(state, heads, B):
+    """One step's statistic: sum += sum_i sign(heads[i, 0] - 0.5) over the first B rows of D's packed output [rows, 1 + c]; rows += B;
+    steps += 1"""
+    _chk_ada(state, "ada_accumulate")
+    _chk(heads, name="heads")
+    if heads.dim() != 2 or not 1 <= int(B) <= heads.shape[0]:
+        raise ValueError(f"ada_accumulate: heads must be [rows >= B, 1 + c], got {tuple(heads.shape)} with B = {B}")
+    check(_lib.load().lgx_ada_accumulate(_p(state), _p(heads), heads.shape[1], int(B), _stream()), "lgx_ada_accumulate")
+    return state
+
+
+def ada_adjust(state, interval, target, per_row):
+    """The controller: once `interval` steps are in, p moves by rows * per_row towards sum / rows == target, is clamped to [0, 1], and
+    the counters restart; before that nothing is written."""
+    _chk_ada(state, "ada_adjust")
+    check(_lib.load().lgx_ada_adjust(_p(state), int(interval), float(target), float(per_row), _stream()), "lgx_ada_adjust")
+    return state
+
+
+def ada_read(state):
+    """(p, sum, rows, steps) on the host.  Synchronises: for logs, checkpoints and tests, not for the step."""
+    _chk_ada(state, "ada_read")
+    host = state.detach().cpu()
+    w = host.view(torch.int32).tolist()
+    return float(host[0]), w[1], w[2], w[3]
+
+
 
 # ------------------------------------------------------------------ packed uint8 data set (input_u8.hip, DESIGN.md §13)
 def _chk_rows(src, idx, name):
