@@ -15,7 +15,7 @@
  *     Activation-sized tensors are fp32 with LG_DT_F32; with LG_DT_BF16 the entry points that take `*16` pointers
  *     (x16 / dy16 / z16 / out16 ...: bf16 tensors of the same shape) read and write them as bf16 ONLY — raw conv outputs,
  *     activated maps and inter-layer gradients then never exist in fp32 (the "bf16 activation path").
- *   - the thread-local strings of lg_last_error / lg_last_kernel are the only global state;
+ *   - the thread-local strings of lg_last_error / lg_last_kernel / lg_instnorm_last_launches are the only global state;
  * Stride-2 layers are described by (cb, cs, Hs, Ws): cb = channels of the BIG (2Hs x 2Ws) tensor,
  * cs = channels of the SMALL (Hs x Ws) tensor.  tf Conv2D kernels (HWIO, in=cb, out=cs) and
  * Conv2DTranspose kernels (HWOI, out=cb, in=cs) then share ONE memory layout [5][5][cb][cs].
@@ -43,6 +43,12 @@ const char* lg_last_error(void);
 const char* lg_last_kernel(void);
 /* Resets that name to "": the name is sticky, so a timing harness clears it before a call whose launch path may name no kernel. */
 int lg_clear_kernel(void);
+/* What the calling thread's most recent lg_instnorm_* / lg_dropout_* call launched, in launch order, as
+ * "kernel[gridDim.x,gridDim.y];kernel[gridDim.x,gridDim.y];..." — the kernel as norm.hip names it, template arguments included; ""
+ * if the call was refused before its first launch.  Independent of lg_last_kernel (which these entry points never set).  The launch
+ * path only records a static string and two integers per launch; the text is formatted here.  Test aid (tests/test_norm_exact_gpu.py
+ * asserts the launch geometry of every case); no reference counterpart. */
+const char* lg_instnorm_last_launches(void);
 
 /* ---- weight packing (once per layer per step; weights change every step) ------------------------
  * master kernel w[5][5][cb][cs] -> MFMA B-operand images in `dtype` (down pack + up pack). */

@@ -15,6 +15,7 @@
 // All kernels are HBM-bound: 16-B vector loads, one pass over x for the moments (values kept in registers).
 // The encoder's live dropout (dropout_train) rides on the same passes: dropped twins of apply / bwd regenerate the mask from a
 // Philox counter in registers (DropK below); the mask-free kernels are the DROP = false instances of the shared bodies.
+#include <stdio.h>
 #include "lg_internal.h"
 #include "philox.h"
 
@@ -867,8 +868,28 @@ inline int ew_blocks(long long total4) {
 inline size_t part_bytes(int B, long long L) { return ((size_t)B * nchunks(L) * 3 * sizeof(double) + 255) / 256 * 256; }
 inline size_t bst_bytes(int B) { return ((size_t)B * 4 * sizeof(float) + 255) / 256 * 256; }
 
+// What the current entry point launched (lg_instnorm_last_launches): every launch of this file goes through NORM_LAUNCH, which
+// records the kernel as it is spelled at the launch site (a string literal: nothing is formatted here) and its grid.  Reset on
+// entry of every function below that can launch, BEFORE its argument checks: a refused call reports no launch.
+struct LaunchNote { const char* name; unsigned gx, gy; };
+constexpr int NL_MAX = 8;  // the longest chain is 5: partial, final, affine, apply + bias, colsum
+thread_local LaunchNote g_nl[NL_MAX];
+thread_local int g_nl_n = 0;
+inline void nl_reset() { g_nl_n = 0; }
+inline void nl_note(const char* name, const dim3& g) {
+  if (g_nl_n < NL_MAX) g_nl[g_nl_n] = LaunchNote{name, g.x, g.y};
+  ++g_nl_n;
+}
+#define NORM_LAUNCH(kern, grid, block, shmem, st, ...)                  \
+  do {                                                                  \
+    const dim3 nl_grid_ = (grid);                                       \
+    nl_note(#kern, nl_grid_);                                           \
+    hipLaunchKernelGGL(kern, nl_grid_, block, shmem, st, __VA_ARGS__);  \
+  } while (0)
+
 // host-side checks of a dropout launch + its kernel argument (see DropK)
 int drop_args(const char* who, const long long* key, int call, int level, int r0, int B, long long L, float rate, DropK* dk) {
+  nl_reset();
   LG_CHECK_ARG(key, "%s: null pointer (dropout key)", who);
   LG_CHECK_ARG(L > 0 && L % 8 == 0, "%s: dropout needs L %% 8 == 0 (one Philox block per 8 elements), got L=%lld", who, L);
   LG_CHECK_ARG(rate >= 0.f && rate < 1.f, "%s: dropout rate %g outside [0, 1)", who, (double)rate);
@@ -892,6 +913,20 @@ __global__ void dropout_key_kernel(unsigned long long* __restrict__ key, unsigne
 
 }  // namespace
 
+extern "C" const char* lg_instnorm_last_launches(void) {
+  static thread_local char buf[NL_MAX * 96];
+  size_t o = 0;
+  buf[0] = 0;
+  for (int i = 0; i < g_nl_n && i < NL_MAX; ++i) {
+    if (i) buf[o++] = ';';
+    for (const char* p = g_nl[i].name; *p && o + 32 < sizeof(buf); ++p)   // "(kernel<a, b>)" at the launch site -> "kernel<a,b>"
+      if (*p != '(' && *p != ')' && *p != ' ') buf[o++] = *p;
+    o += (size_t)snprintf(buf + o, sizeof(buf) - o, "[%u,%u]", g_nl[i].gx, g_nl[i].gy);
+  }
+  if (g_nl_n > NL_MAX) snprintf(buf + o, sizeof(buf) - o, ";...");
+  return buf;
+}
+
 extern "C" int lg_instnorm_stats_stride(void) { return LG_NSTAT; }
 
 extern "C" size_t lg_instnorm_workspace_bytes(int B, long long L) {
@@ -910,15 +945,16 @@ extern "C" int lg_instnorm_leaky_stats(const float* x, float* stats, const float
 extern "C" int lg_instnorm_leaky_stats_z16(const float* x, float* stats, const float* gamma, const float* beta,
                                            void* workspace, size_t ws_bytes, int B, long long L, int pre_leaky,
                                            float alpha, void* x16_out, void* stream) {
+  nl_reset();
   LG_CHECK_ARG(x && stats && gamma && beta && workspace, "lg_instnorm_leaky_stats: null pointer");
   LG_CHECK_ARG(B > 0 && B <= 65535 && L > 0 && L % 4 == 0, "lg_instnorm_leaky_stats: bad shape B=%d L=%lld", B, L);
   LG_CHECK_ARG(ws_bytes >= lg_instnorm_workspace_bytes(B, L), "lg_instnorm_leaky_stats: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const int nc = nchunks(L);
-  hipLaunchKernelGGL(stats_partial_kernel, dim3(nc, B), dim3(256), 0, st, x, (double*)workspace, L, nc, pre_leaky, alpha,
+  NORM_LAUNCH(stats_partial_kernel, dim3(nc, B), dim3(256), 0, st, x, (double*)workspace, L, nc, pre_leaky, alpha,
                      (__bf16*)x16_out);
   LG_CHECK_LAUNCH("lg_instnorm_leaky_stats(partial)");
-  hipLaunchKernelGGL(stats_final_kernel, dim3(B), dim3(64), 0, st, (const double*)workspace, stats, gamma, beta, nc);
+  NORM_LAUNCH(stats_final_kernel, dim3(B), dim3(64), 0, st, (const double*)workspace, stats, gamma, beta, nc);
   LG_CHECK_LAUNCH("lg_instnorm_leaky_stats(final)");
   return LG_OK;
 }
@@ -926,8 +962,9 @@ extern "C" int lg_instnorm_leaky_stats_z16(const float* x, float* stats, const f
 // stats from moment partials [B][nparts][3] doubles {count, mean, M2} produced by a conv epilogue (conv_halo.hip)
 extern "C" int lg_instnorm_stats_finalize(const void* partials, int nparts, float* stats, const float* gamma,
                                           const float* beta, int B, void* stream) {
+  nl_reset();
   LG_CHECK_ARG(partials && stats && gamma && beta && nparts > 0 && B > 0, "lg_instnorm_stats_finalize: bad arguments");
-  hipLaunchKernelGGL(stats_final_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, (const double*)partials, stats, gamma,
+  NORM_LAUNCH(stats_final_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, (const double*)partials, stats, gamma,
                      beta, nparts);
   LG_CHECK_LAUNCH("lg_instnorm_stats_finalize");
   return LG_OK;
@@ -936,16 +973,17 @@ extern "C" int lg_instnorm_stats_finalize(const void* partials, int nparts, floa
 // y = [post_leaky] (a_n * ([pre_leaky](x) - mu_n) + beta) [+ skip]
 static int apply_impl(const float* x, const float* stats, const float* skip, float* y, void* y16, int B, long long L, int pre_leaky,
                       int post_leaky, float alpha, const DropK* dk, void* stream) {
+  nl_reset();
   LG_CHECK_ARG(x && stats && (y || y16), "lg_instnorm_leaky_apply: null pointer");
   LG_CHECK_ARG(B > 0 && L > 0 && L % 4 == 0 && (long long)B * L / 4 < (1LL << 31), "lg_instnorm_leaky_apply: bad shape B=%d L=%lld", B, L);
   const long long total4 = (long long)B * L / 4;
   if (dk) {
-    hipLaunchKernelGGL(apply_drop_kernel, dim3((int)fit_rounds(ew_blocks(total4), LG_RESIDENT_BLOCKS(apply_drop_kernel), EW_MAX_BLOCKS, 1)), dim3(256), 0,
+    NORM_LAUNCH(apply_drop_kernel, dim3((int)fit_rounds(ew_blocks(total4), LG_RESIDENT_BLOCKS(apply_drop_kernel), EW_MAX_BLOCKS, 1)), dim3(256), 0,
                        (hipStream_t)stream, x, stats, y, (__bf16*)y16, L / 4, total4, alpha, *dk);
     LG_CHECK_LAUNCH("lg_instnorm_leaky_apply_drop");
     return LG_OK;
   }
-  hipLaunchKernelGGL(apply_kernel, dim3((int)fit_rounds(ew_blocks(total4), LG_RESIDENT_BLOCKS(apply_kernel), EW_MAX_BLOCKS, 1)), dim3(256), 0, (hipStream_t)stream, x, stats, skip, y,
+  NORM_LAUNCH(apply_kernel, dim3((int)fit_rounds(ew_blocks(total4), LG_RESIDENT_BLOCKS(apply_kernel), EW_MAX_BLOCKS, 1)), dim3(256), 0, (hipStream_t)stream, x, stats, skip, y,
                      (__bf16*)y16, L / 4, total4, pre_leaky, post_leaky, alpha);
   LG_CHECK_LAUNCH("lg_instnorm_leaky_apply");
   return LG_OK;
@@ -982,6 +1020,7 @@ extern "C" int lg_instnorm_leaky_bwd(const float* x, const float* stats, const v
 static int bwd_impl(const float* x, const float* stats, const void* g, int g_is_bf16, float* dx, void* dx16,
                     float* dgamma, float* dbeta, float* db, int C, void* workspace, size_t ws_bytes, int B,
                     long long L, int pre_leaky, int post_leaky, float alpha, int accumulate, const DropK* dk, void* stream) {
+  nl_reset();
   LG_CHECK_ARG(x && stats && g && (dx || dx16) && workspace, "lg_instnorm_leaky_bwd: null pointer");
   LG_CHECK_ARG(B > 0 && B <= 65535 && L > 0 && L % 4 == 0 && (long long)B * L / 4 < (1LL << 31),
                "lg_instnorm_leaky_bwd: bad shape B=%d L=%lld", B, L);
@@ -1000,25 +1039,25 @@ static int bwd_impl(const float* x, const float* stats, const void* g, int g_is_
   float* bstats = (float*)(ws + part_bytes(B, L));
   double* gsum = (double*)(ws + part_bytes(B, L) + bst_bytes(B));
   if (dk)
-    hipLaunchKernelGGL(bwd_partial_drop_kernel, dim3(nc, B), dim3(256), 0, st, x, g, g_is_bf16, stats, partial, L, nc, alpha, *dk);
+    NORM_LAUNCH(bwd_partial_drop_kernel, dim3(nc, B), dim3(256), 0, st, x, g, g_is_bf16, stats, partial, L, nc, alpha, *dk);
   else
-    hipLaunchKernelGGL(bwd_partial_kernel, dim3(nc, B), dim3(256), 0, st, x, g, g_is_bf16, stats, partial, L, nc, pre_leaky,
+    NORM_LAUNCH(bwd_partial_kernel, dim3(nc, B), dim3(256), 0, st, x, g, g_is_bf16, stats, partial, L, nc, pre_leaky,
                        post_leaky, alpha);
   LG_CHECK_LAUNCH("lg_instnorm_leaky_bwd(partial)");
-  hipLaunchKernelGGL(bwd_final_kernel, dim3(B), dim3(64), 0, st, (const double*)partial, stats, bstats, gsum, L, nc);
+  NORM_LAUNCH(bwd_final_kernel, dim3(B), dim3(64), 0, st, (const double*)partial, stats, bstats, gsum, L, nc);
   LG_CHECK_LAUNCH("lg_instnorm_leaky_bwd(final)");
   if (dgamma && dbeta) {
-    hipLaunchKernelGGL(bwd_affine_grad_kernel, dim3(1), dim3(256), 0, st, (const double*)gsum, dgamma, dbeta, B,
+    NORM_LAUNCH(bwd_affine_grad_kernel, dim3(1), dim3(256), 0, st, (const double*)gsum, dgamma, dbeta, B,
                        accumulate);
     LG_CHECK_LAUNCH("lg_instnorm_leaky_bwd(affine)");
   }
   const long long total4 = (long long)B * L / 4;
   if (!db) {
     if (dk)
-      hipLaunchKernelGGL(bwd_apply_drop_kernel<false>, dim3((int)fit_rounds(ew_blocks(total4), LG_RESIDENT_BLOCKS(bwd_apply_drop_kernel<false>), EW_MAX_BLOCKS, 1)), dim3(256), 0, st, x, g,
+      NORM_LAUNCH(bwd_apply_drop_kernel<false>, dim3((int)fit_rounds(ew_blocks(total4), LG_RESIDENT_BLOCKS(bwd_apply_drop_kernel<false>), EW_MAX_BLOCKS, 1)), dim3(256), 0, st, x, g,
                          g_is_bf16, stats, (const float*)bstats, dx, (__bf16*)dx16, L / 4, total4, alpha, (float*)nullptr, 0, *dk);
     else
-      hipLaunchKernelGGL(bwd_apply_kernel<false>, dim3((int)fit_rounds(ew_blocks(total4), LG_RESIDENT_BLOCKS(bwd_apply_kernel<false>), EW_MAX_BLOCKS, 1)), dim3(256), 0, st, x, g, g_is_bf16, stats,
+      NORM_LAUNCH(bwd_apply_kernel<false>, dim3((int)fit_rounds(ew_blocks(total4), LG_RESIDENT_BLOCKS(bwd_apply_kernel<false>), EW_MAX_BLOCKS, 1)), dim3(256), 0, st, x, g, g_is_bf16, stats,
                          (const float*)bstats, dx, (__bf16*)dx16, L / 4, total4, pre_leaky, post_leaky, alpha, nullptr, 0);
     LG_CHECK_LAUNCH("lg_instnorm_leaky_bwd(apply)");
     return LG_OK;
@@ -1028,13 +1067,13 @@ static int bwd_impl(const float* x, const float* stats, const void* g, int g_is_
   long long nb = fit_rounds((total4 + 255) / 256, LG_RESIDENT_BLOCKS(bwd_apply_kernel<true>), DB_MAX_BLOCKS, unit);
   float* colpart = (float*)(ws + lg_instnorm_workspace_bytes(B, L));
   if (dk)
-    hipLaunchKernelGGL(bwd_apply_drop_kernel<true>, dim3((int)nb), dim3(256), 0, st, x, g, g_is_bf16, stats, (const float*)bstats, dx,
+    NORM_LAUNCH(bwd_apply_drop_kernel<true>, dim3((int)nb), dim3(256), 0, st, x, g, g_is_bf16, stats, (const float*)bstats, dx,
                        (__bf16*)dx16, L / 4, total4, alpha, colpart, C4, *dk);
   else
-    hipLaunchKernelGGL(bwd_apply_kernel<true>, dim3((int)nb), dim3(256), 0, st, x, g, g_is_bf16, stats, (const float*)bstats, dx,
+    NORM_LAUNCH(bwd_apply_kernel<true>, dim3((int)nb), dim3(256), 0, st, x, g, g_is_bf16, stats, (const float*)bstats, dx,
                        (__bf16*)dx16, L / 4, total4, pre_leaky, post_leaky, alpha, colpart, C4);
   LG_CHECK_LAUNCH("lg_instnorm_leaky_bwd_db(apply)");
-  hipLaunchKernelGGL(colsum_final_kernel, dim3((C + 15) / 16), dim3(1024), 0, st, (const float*)colpart, db, (int)nb, C,
+  NORM_LAUNCH(colsum_final_kernel, dim3((C + 15) / 16), dim3(1024), 0, st, (const float*)colpart, db, (int)nb, C,
                      accumulate);
   LG_CHECK_LAUNCH("lg_instnorm_leaky_bwd_db(bias)");
   return LG_OK;
@@ -1059,6 +1098,7 @@ extern "C" int lg_instnorm_leaky_bwd_drop(const float* x, const float* stats, co
 // skip (may be null): fp32, or bf16 when skip_is_bf16
 static int apply16_impl(const void* z16, const float* stats, const void* skip, int skip_is_bf16, float* y, void* y16, int B, long long L,
                         int pre_leaky, int post_leaky, float alpha, const DropK* dk, void* stream) {
+  nl_reset();
   LG_CHECK_ARG(z16 && stats && (y || y16), "lg_instnorm_leaky_apply_z16: null pointer");
   LG_CHECK_ARG(B > 0 && L > 0 && L % 8 == 0 && (long long)B * L / 8 < (1LL << 31),
                "lg_instnorm_leaky_apply_z16: bad shape B=%d L=%lld", B, L);
@@ -1069,18 +1109,18 @@ static int apply16_impl(const void* z16, const float* stats, const void* skip, i
   const __bf16* x = (const __bf16*)z16;
   if (dk) {
     nb = fit_rounds((total8 + 256 * EW8_UNR - 1) / (256 * EW8_UNR), LG_RESIDENT_BLOCKS(apply16_drop_kernel), EW_MAX_BLOCKS, 1);
-    hipLaunchKernelGGL(apply16_drop_kernel, dim3((int)nb), dim3(256), 0, st, x, stats, y, (__bf16*)y16, L / 8, total8, alpha, *dk);
+    NORM_LAUNCH(apply16_drop_kernel, dim3((int)nb), dim3(256), 0, st, x, stats, y, (__bf16*)y16, L / 8, total8, alpha, *dk);
     LG_CHECK_LAUNCH("lg_instnorm_leaky_apply_z16_drop");
     return LG_OK;
   }
   if (!skip)
-    hipLaunchKernelGGL(apply16_kernel<0>, dim3((int)nb), dim3(256), 0, st, x, stats, skip, y, (__bf16*)y16, L / 8, total8,
+    NORM_LAUNCH(apply16_kernel<0>, dim3((int)nb), dim3(256), 0, st, x, stats, skip, y, (__bf16*)y16, L / 8, total8,
                        pre_leaky, post_leaky, alpha);
   else if (!skip_is_bf16)
-    hipLaunchKernelGGL(apply16_kernel<1>, dim3((int)nb), dim3(256), 0, st, x, stats, skip, y, (__bf16*)y16, L / 8, total8,
+    NORM_LAUNCH(apply16_kernel<1>, dim3((int)nb), dim3(256), 0, st, x, stats, skip, y, (__bf16*)y16, L / 8, total8,
                        pre_leaky, post_leaky, alpha);
   else
-    hipLaunchKernelGGL(apply16_kernel<2>, dim3((int)nb), dim3(256), 0, st, x, stats, skip, y, (__bf16*)y16, L / 8, total8,
+    NORM_LAUNCH(apply16_kernel<2>, dim3((int)nb), dim3(256), 0, st, x, stats, skip, y, (__bf16*)y16, L / 8, total8,
                        pre_leaky, post_leaky, alpha);
   LG_CHECK_LAUNCH("lg_instnorm_leaky_apply_z16");
   return LG_OK;
@@ -1103,6 +1143,7 @@ extern "C" int lg_instnorm_leaky_apply_z16_drop(const void* z16, const float* st
 static int apply16p_impl(const void* z16, const void* partials, int nparts, const float* gamma, const float* beta, float* stats,
                          const void* skip, int skip_is_bf16, float* y, void* y16, int B, long long L, int post_leaky, float alpha,
                          const DropK* dk, void* stream) {
+  nl_reset();
   LG_CHECK_ARG(z16 && partials && gamma && beta && stats && (y || y16), "lg_instnorm_leaky_apply_z16_p: null pointer");
   LG_CHECK_ARG(nparts > 0 && B > 0 && B <= 65535 && L > 0 && L % 8 == 0 && L / 8 < (1LL << 31),
                "lg_instnorm_leaky_apply_z16_p: bad shape B=%d L=%lld nparts=%d", B, L, nparts);
@@ -1115,13 +1156,13 @@ static int apply16p_impl(const void* z16, const void* partials, int nparts, cons
   const __bf16* x = (const __bf16*)z16;
   const double* pr = (const double*)partials;
   if (dk)
-    hipLaunchKernelGGL(apply16p_drop_kernel, grid, dim3(256), 0, st, x, pr, nparts, gamma, beta, stats, y, (__bf16*)y16, (unsigned)L8, alpha, *dk);
+    NORM_LAUNCH(apply16p_drop_kernel, grid, dim3(256), 0, st, x, pr, nparts, gamma, beta, stats, y, (__bf16*)y16, (unsigned)L8, alpha, *dk);
   else if (!skip)
-    hipLaunchKernelGGL(apply16p_kernel<0>, grid, dim3(256), 0, st, x, pr, nparts, gamma, beta, stats, skip, y, (__bf16*)y16, (unsigned)L8, post_leaky, alpha);
+    NORM_LAUNCH(apply16p_kernel<0>, grid, dim3(256), 0, st, x, pr, nparts, gamma, beta, stats, skip, y, (__bf16*)y16, (unsigned)L8, post_leaky, alpha);
   else if (!skip_is_bf16)
-    hipLaunchKernelGGL(apply16p_kernel<1>, grid, dim3(256), 0, st, x, pr, nparts, gamma, beta, stats, skip, y, (__bf16*)y16, (unsigned)L8, post_leaky, alpha);
+    NORM_LAUNCH(apply16p_kernel<1>, grid, dim3(256), 0, st, x, pr, nparts, gamma, beta, stats, skip, y, (__bf16*)y16, (unsigned)L8, post_leaky, alpha);
   else
-    hipLaunchKernelGGL(apply16p_kernel<2>, grid, dim3(256), 0, st, x, pr, nparts, gamma, beta, stats, skip, y, (__bf16*)y16, (unsigned)L8, post_leaky, alpha);
+    NORM_LAUNCH(apply16p_kernel<2>, grid, dim3(256), 0, st, x, pr, nparts, gamma, beta, stats, skip, y, (__bf16*)y16, (unsigned)L8, post_leaky, alpha);
   LG_CHECK_LAUNCH("lg_instnorm_leaky_apply_z16_p");
   return LG_OK;
 }
@@ -1152,6 +1193,7 @@ extern "C" int lg_instnorm_leaky_bwd_z16(const void* z16, const float* stats, co
 static int bwd16_impl(const void* z16, const float* stats, const void* g, int g_is_bf16, float* dx, void* dx16, float* dgamma, float* dbeta,
                       float* db, int C, const void* partials, int nparts_in, void* workspace, size_t ws_bytes, int B, long long L,
                       int pre_leaky, int post_leaky, float alpha, int accumulate, const DropK* dk, void* stream) {
+  nl_reset();
   LG_CHECK_ARG(z16 && stats && g && (dx || dx16) && workspace, "lg_instnorm_leaky_bwd_z16: null pointer");
   // producer-fused sums are those of the UNMASKED gradient: with a mask they are right only when it keeps everything (T = 0)
   LG_CHECK_ARG(!(dk && partials && nparts_in > 0 && dk->T != 0), "lg_instnorm_leaky_bwd_z16_drop: fused partial sums know no dropout mask");
@@ -1182,21 +1224,21 @@ static int bwd16_impl(const void* z16, const float* stats, const void* g, int g_
     nc = nparts_in;
   } else {
     if (dk && g_is_bf16)
-      hipLaunchKernelGGL(bwd_partial16_drop_kernel<true>, dim3(nc, B), dim3(256), 0, st, x, g, stats, partial, L, nc, alpha, *dk);
+      NORM_LAUNCH(bwd_partial16_drop_kernel<true>, dim3(nc, B), dim3(256), 0, st, x, g, stats, partial, L, nc, alpha, *dk);
     else if (dk)
-      hipLaunchKernelGGL(bwd_partial16_drop_kernel<false>, dim3(nc, B), dim3(256), 0, st, x, g, stats, partial, L, nc, alpha, *dk);
+      NORM_LAUNCH(bwd_partial16_drop_kernel<false>, dim3(nc, B), dim3(256), 0, st, x, g, stats, partial, L, nc, alpha, *dk);
     else if (g_is_bf16)
-      hipLaunchKernelGGL(bwd_partial16_kernel<true>, dim3(nc, B), dim3(256), 0, st, x, g, stats, partial, L, nc, pre_leaky,
+      NORM_LAUNCH(bwd_partial16_kernel<true>, dim3(nc, B), dim3(256), 0, st, x, g, stats, partial, L, nc, pre_leaky,
                          post_leaky, alpha);
     else
-      hipLaunchKernelGGL(bwd_partial16_kernel<false>, dim3(nc, B), dim3(256), 0, st, x, g, stats, partial, L, nc, pre_leaky,
+      NORM_LAUNCH(bwd_partial16_kernel<false>, dim3(nc, B), dim3(256), 0, st, x, g, stats, partial, L, nc, pre_leaky,
                          post_leaky, alpha);
     LG_CHECK_LAUNCH("lg_instnorm_leaky_bwd_z16(partial)");
   }
-  hipLaunchKernelGGL(bwd_final_kernel, dim3(B), dim3(64), 0, st, (const double*)partial, stats, bstats, gsum, L, nc);
+  NORM_LAUNCH(bwd_final_kernel, dim3(B), dim3(64), 0, st, (const double*)partial, stats, bstats, gsum, L, nc);
   LG_CHECK_LAUNCH("lg_instnorm_leaky_bwd_z16(final)");
   if (dgamma && dbeta) {
-    hipLaunchKernelGGL(bwd_affine_grad_kernel, dim3(1), dim3(256), 0, st, (const double*)gsum, dgamma, dbeta, B, accumulate);
+    NORM_LAUNCH(bwd_affine_grad_kernel, dim3(1), dim3(256), 0, st, (const double*)gsum, dgamma, dbeta, B, accumulate);
     LG_CHECK_LAUNCH("lg_instnorm_leaky_bwd_z16(affine)");
   }
   const long long total8 = (long long)B * L / 8;
@@ -1207,16 +1249,16 @@ static int bwd16_impl(const void* z16, const float* stats, const void* g, int g_
     else
       nb = fit_rounds(nb, g_is_bf16 ? LG_RESIDENT_BLOCKS((bwd_apply16_kernel<false, true>)) : LG_RESIDENT_BLOCKS((bwd_apply16_kernel<false, false>)), EW_MAX_BLOCKS, 1);
     if (dk && g_is_bf16)
-      hipLaunchKernelGGL((bwd_apply16_drop_kernel<false, true>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
+      NORM_LAUNCH((bwd_apply16_drop_kernel<false, true>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
                          (__bf16*)dx16, L / 8, total8, alpha, (float*)nullptr, 0, *dk);
     else if (dk)
-      hipLaunchKernelGGL((bwd_apply16_drop_kernel<false, false>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
+      NORM_LAUNCH((bwd_apply16_drop_kernel<false, false>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
                          (__bf16*)dx16, L / 8, total8, alpha, (float*)nullptr, 0, *dk);
     else if (g_is_bf16)
-      hipLaunchKernelGGL((bwd_apply16_kernel<false, true>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
+      NORM_LAUNCH((bwd_apply16_kernel<false, true>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
                          (__bf16*)dx16, L / 8, total8, pre_leaky, post_leaky, alpha, (float*)nullptr, 0);
     else
-      hipLaunchKernelGGL((bwd_apply16_kernel<false, false>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
+      NORM_LAUNCH((bwd_apply16_kernel<false, false>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
                          (__bf16*)dx16, L / 8, total8, pre_leaky, post_leaky, alpha, (float*)nullptr, 0);
     LG_CHECK_LAUNCH("lg_instnorm_leaky_bwd_z16(apply)");
     return LG_OK;
@@ -1227,19 +1269,19 @@ static int bwd16_impl(const void* z16, const float* stats, const void* g, int g_
   float* colpart = (float*)(ws + lg_instnorm_workspace_bytes(B, L));   // [nb][C] floats, nb <= DB_MAX_BLOCKS (+2)
   // (the dropped twins take their plain twins' grid: the column sums then merge in the same order)
   if (dk && g_is_bf16)
-    hipLaunchKernelGGL((bwd_apply16_drop_kernel<true, true>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
+    NORM_LAUNCH((bwd_apply16_drop_kernel<true, true>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
                        (__bf16*)dx16, L / 8, total8, alpha, colpart, C8, *dk);
   else if (dk)
-    hipLaunchKernelGGL((bwd_apply16_drop_kernel<true, false>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
+    NORM_LAUNCH((bwd_apply16_drop_kernel<true, false>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
                        (__bf16*)dx16, L / 8, total8, alpha, colpart, C8, *dk);
   else if (g_is_bf16)
-    hipLaunchKernelGGL((bwd_apply16_kernel<true, true>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
+    NORM_LAUNCH((bwd_apply16_kernel<true, true>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
                        (__bf16*)dx16, L / 8, total8, pre_leaky, post_leaky, alpha, colpart, C8);
   else
-    hipLaunchKernelGGL((bwd_apply16_kernel<true, false>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
+    NORM_LAUNCH((bwd_apply16_kernel<true, false>), dim3((int)nb), dim3(256), 0, st, x, g, stats, (const float*)bstats, dx,
                        (__bf16*)dx16, L / 8, total8, pre_leaky, post_leaky, alpha, colpart, C8);
   LG_CHECK_LAUNCH("lg_instnorm_leaky_bwd_z16(apply+bias)");
-  hipLaunchKernelGGL(colsum_final_kernel, dim3((C + 15) / 16), dim3(1024), 0, st, (const float*)colpart, db, (int)nb, C,
+  NORM_LAUNCH(colsum_final_kernel, dim3((C + 15) / 16), dim3(1024), 0, st, (const float*)colpart, db, (int)nb, C,
                      accumulate);
   LG_CHECK_LAUNCH("lg_instnorm_leaky_bwd_z16(bias)");
   return LG_OK;
@@ -1265,8 +1307,9 @@ extern "C" int lg_instnorm_leaky_bwd_z16_drop(const void* z16, const float* stat
 
 // key[2] = {seed, key_offset} written on the device from launch scalars: the step's key without a host-to-device copy (no sync)
 extern "C" int lg_dropout_key(long long* key, unsigned long long seed, unsigned long long key_offset, void* stream) {
+  nl_reset();
   LG_CHECK_ARG(key && ((uintptr_t)key & 7) == 0, "lg_dropout_key: null or misaligned pointer");
-  hipLaunchKernelGGL(dropout_key_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<unsigned long long*>(key), seed, key_offset);
+  NORM_LAUNCH(dropout_key_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<unsigned long long*>(key), seed, key_offset);
   LG_CHECK_LAUNCH("lg_dropout_key");
   return LG_OK;
 }
@@ -1274,6 +1317,7 @@ extern "C" int lg_dropout_key(long long* key, unsigned long long seed, unsigned 
 // keep[B][L] bytes (1 = kept) of the rows r0 .. r0+B-1 of the (call, level) slot under `key` = device {seed, key_offset}
 extern "C" int lg_dropout_mask(const long long* key, int call, int level, int r0, int B, long long L, float rate, unsigned char* keep,
                                void* stream) {
+  nl_reset();
   LG_CHECK_ARG(keep, "lg_dropout_mask: null pointer");
   LG_CHECK_ARG(((uintptr_t)keep & 7) == 0, "lg_dropout_mask: keep must be 8-byte aligned (8 decisions per store)");
   LG_CHECK_ARG(B > 0 && L > 0 && (long long)B * L / 8 < (1LL << 31), "lg_dropout_mask: bad shape B=%d L=%lld", B, L);
@@ -1282,7 +1326,7 @@ extern "C" int lg_dropout_mask(const long long* key, int call, int level, int r0
   const long long total8 = (long long)B * L / 8;
   long long nb = (total8 + 255) / 256;
   if (nb > EW_MAX_BLOCKS) nb = EW_MAX_BLOCKS;
-  hipLaunchKernelGGL(dropout_mask_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, keep, total8, dk);
+  NORM_LAUNCH(dropout_mask_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, keep, total8, dk);
   LG_CHECK_LAUNCH("lg_dropout_mask");
   return LG_OK;
 }
@@ -1293,8 +1337,9 @@ extern "C" int lg_dropout_mask(const long long* key, int call, int level, int r0
 // ask the level for no weight gradient (dz then has ONE reader).  instance.py:105-128 differentiated; eager_trainer.py:158-163.
 extern "C" int lg_instnorm_bwd_coef(const float* stats, const void* partials, int nparts, float* coef, int B, long long L,
                                     void* stream) {
+  nl_reset();
   LG_CHECK_ARG(stats && partials && coef && nparts > 0 && B > 0 && B <= 65535 && L > 0, "lg_instnorm_bwd_coef: bad arguments");
-  hipLaunchKernelGGL(bwd_coef_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, (const double*)partials, stats, coef, L, nparts);
+  NORM_LAUNCH(bwd_coef_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, (const double*)partials, stats, coef, L, nparts);
   LG_CHECK_LAUNCH("lg_instnorm_bwd_coef");
   return LG_OK;
 }

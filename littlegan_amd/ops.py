@@ -91,6 +91,18 @@ def last_kernel() -> str:
     return _lib.load().lg_last_kernel().decode()
 
 
+def last_norm_launches():
+    """[(kernel, gridDim.x, gridDim.y), ...] of the most recent instance-norm / dropout C-ABI call on this thread, in launch order
+    (lg_instnorm_last_launches; [] if the call was refused before its first launch)."""
+    s = _lib.load().lg_instnorm_last_launches().decode()
+    out = []
+    for item in filter(None, s.split(";")):
+        name, _, grid = item.rpartition("[")
+        gx, gy = grid.rstrip("]").split(",")
+        out.append((name, int(gx), int(gy)))
+    return out
+
+
 def workspace(nbytes: int, device, tag="default") -> torch.Tensor:
     """Grow-only scratch buffer per (device, tag); kernels on one stream run in order so sharing is safe."""
     key = (str(device), tag)
