@@ -1,4 +1,5 @@
-"""ctypes binding of liblittlegan_hip.so (C ABI: include/littlegan_hip.h, and include/littlegan_hip_ext.h for the lgx_ extensions).
+"""ctypes binding of liblittlegan_hip.so (C ABI: include/littlegan_hip.h, include/littlegan_hip_ext.h for the lgx_ extensions and
+include/littlegan_hip_reg.h for the lgr_ regularisers).
 
 The product path has NO fallback: if the shared library is missing this module raises at
 import of the symbol table, and every op raises `LittleGanHipError` on a non-zero return.
@@ -155,6 +156,17 @@ EXT_SIGNATURES = {
 }
 
 
+# regularisers beyond the reference's recipe (include/littlegan_hip_reg.h, prefix lgr_): exported by the same library, bound beside them
+REG_SIGNATURES = {
+    # R1 gradient penalty (r1.hip): the top seed, the seed on the image gradient, the heads' column sum
+    "lgr_r1_workspace_bytes": (Z, [I, L]),
+    "lgr_r1_heads_seed": (I, [P, P, I, I, P]),
+    "lgr_r1_seed": (I, [P, P, P, P, P, F, P, Z, I, L, P]),
+    "lgr_r1_colsum_workspace_bytes": (Z, [I, I]),
+    "lgr_r1_heads_colsum": (I, [P, P, P, Z, I, I, P]),
+}
+
+
 class LittleGanHipError(RuntimeError):
     pass
 
@@ -187,7 +199,7 @@ def load():
     # before torch, the system runtime it links against would come in as a SECOND runtime and its kernels would see no device.
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(REG_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

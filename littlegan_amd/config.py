@@ -9,7 +9,9 @@ training step, the generator-side tapes differentiated through it; "" = off, the
 diff_augment_p / ada_target / ada_interval / ada_kimg (adaptive augmentation probability: each diff_augment component is applied per
 row with probability p, fixed or driven on the device towards ada_target; null / null = every component always),
 evaluate_metrics (list out of fid, kid, prdc: what `evaluate` computes; ["fid"] = the reference's run) / evaluate_real_activations (the
-real images' saved activations that kid and prdc need) / kid_subsets / kid_subset_size / prdc_k (metrics.py)."""
+real images' saved activations that kid and prdc need) / kid_subsets / kid_subset_size / prdc_k (metrics.py),
+r1_gamma / r1_interval (R1 gradient penalty on the Discriminator's real-image logit, (r1_gamma r1_interval / 2) mean |dlogit/dx|^2 added
+to the disc loss on every r1_interval-th step; 0 = off; excludes use_gp and dropout_train, allowed with diff_augment)."""
 import json
 import os
 from argparse import ArgumentParser
@@ -84,6 +86,10 @@ DEFAULTS = {
     # activations of the real images that kid / prdc compare against (the stats file holds only mu and sigma; a path, relative ones
     # under test_data_dir); subsets and rows per subset of KID (0 subsets = one estimate over the full sets); k of the k-NN manifolds
     'evaluate_metrics': ['fid'], 'evaluate_real_activations': None, 'kid_subsets': 100, 'kid_subset_size': 1000, 'prdc_k': 3,
+    # R1 gradient penalty (Mescheder et al. 2018, lazily as in Karras et al. 2020): on every r1_interval-th step
+    # (batch_no % r1_interval == 0) disc_loss += (r1_gamma r1_interval / 2) mean_b |d logit(x_b) / d x_b|^2 over the real rows D read (under
+    # diff_augment: the augmented rows, differentiated with respect to them).  r1_gamma 0 = off.  Excludes use_gp and dropout_train.
+    'r1_gamma': 0.0, 'r1_interval': 16,
 }
 
 DIFF_AUGMENT_BITS = {"color": 1, "translation": 2, "cutout": 4}
@@ -135,6 +141,24 @@ def ada_settings(diff_augment, diff_augment_p=None, ada_target=None, ada_interva
             "target": None if ada_target is None else float(np.float32(ada_target)), "interval": int(ada_interval), "per_row": per_row}
 
 
+def r1_settings(r1_gamma=0.0, r1_interval=16):
+    """The two keys of the R1 penalty, validated: None when it is off (r1_gamma == 0), else a dict {gamma, interval,
+    weight} with weight = gamma * interval, the factor a penalty step applies so that the lazily applied term averages to gamma.
+    Raises ValueError for an r1_gamma that is no finite number >= 0 and for an r1_interval that is no integer >= 1 (bools refused),
+    whether or not the penalty is on."""
+    import math
+    if isinstance(r1_gamma, bool) or not isinstance(r1_gamma, (int, float)) or not math.isfinite(r1_gamma) or r1_gamma < 0:
+        raise ValueError(f"r1_gamma must be a finite number >= 0 (0 = off), got {r1_gamma!r}")
+    if isinstance(r1_interval, bool) or not isinstance(r1_interval, int) or r1_interval < 1:
+        raise ValueError(f"r1_interval must be an integer >= 1, got {r1_interval!r}")
+    weight = float(r1_gamma) * r1_interval
+    if not weight <= 3.0e38:
+        raise ValueError(f"r1_gamma * r1_interval = {weight!r} does not fit fp32 (r1_gamma {r1_gamma!r}, r1_interval {r1_interval!r})")
+    if r1_gamma == 0:
+        return None
+    return {"gamma": float(r1_gamma), "interval": int(r1_interval), "weight": weight}
+
+
 METRIC_NAMES = ("fid", "kid", "prdc")
 
 
@@ -179,6 +203,7 @@ class Arg:
             setattr(self, k, v)
         diff_augment_bits(self.diff_augment)   # a misspelt component fails here, not at the first training step
         ada_settings(self.diff_augment, self.diff_augment_p, self.ada_target, self.ada_interval, self.ada_kimg)
+        r1_settings(self.r1_gamma, self.r1_interval)
         self.evaluate_metrics = metric_list(self.evaluate_metrics)   # a misspelt metric fails here, not after the sampling run
         if int(self.kid_subsets) < 0 or int(self.kid_subset_size) < 2 or not 1 <= int(self.prdc_k) <= 15:
             raise ValueError("need kid_subsets >= 0, kid_subset_size >= 2 and 1 <= prdc_k <= 15")

@@ -17,7 +17,7 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from .config import ada_settings, diff_augment_bits
+from .config import ada_settings, diff_augment_bits, r1_settings
 from .dist import GradSync
 from .model import Adjuster, Discriminator, Generator, ParamStore
 from .utils import save_image, soft
@@ -91,6 +91,13 @@ class EagerTrainer:
         # plain diff_augment step with no state and no launch of its own; else the gated draw, with the controller when a target is set
         self.ada = ada_settings(getattr(args, "diff_augment", ""), getattr(args, "diff_augment_p", None), getattr(args, "ada_target", None),
                                 getattr(args, "ada_interval", 4), getattr(args, "ada_kimg", 500.0))
+        # R1 penalty on D's real-image logit, applied every r1_interval-th step (the reference has none): None = off
+        self.r1 = r1_settings(getattr(args, "r1_gamma", 0.0), getattr(args, "r1_interval", 16))
+        if self.r1 is not None and self.use_gp:
+            raise ValueError("r1_gamma and use_gp exclude each other: two gradient penalties on one disc tape (DESIGN.md §24)")
+        if self.r1 is not None and self.dropout:
+            raise ValueError("r1_gamma and dropout_train exclude each other: the penalty's double backward through a masked norm "
+                             "is not built (DESIGN.md §24)")
         # weight average for sampling (the reference has none): on when ema_decay > 0
         self.ema_decay = validate_ema_decay(getattr(args, "ema_decay", 0.0))
         self.sample_ema = bool(getattr(args, "sample_ema", True))
@@ -104,7 +111,7 @@ class EagerTrainer:
         self.opt_state = {m: torch.tensor([b1, b2], dtype=torch.float32, device=self.device)
                           for m, (_, b1, b2) in self.opt_cfg.items()}
         self.losses = {k: torch.zeros(1, dtype=torch.float32, device=self.device)
-                       for k in ("gen", "disc", "adj") + (("gp",) if self.use_gp else ())}
+                       for k in ("gen", "disc", "adj") + (("gp",) if self.use_gp else ()) + (("r1",) if self.r1 is not None else ())}
         self.sync = GradSync(self.device)
         self.adam_order = ("D", "G", "A")   # = the launch order of the all-reduces (see train_step_from_inputs)
         self.global_epoch = 1
@@ -186,9 +193,12 @@ class EagerTrainer:
         if adaptive and not self._ada_ticked:   # (graph_step has counted this step already, whichever way it runs it)
             self._ada_tick()
         # the Adjuster reuses D's encoder maps of `fake` as its skip inputs: keep the fp32 maps only then
+        x_real = new_image   # what D reads as its real batch: the R1 penalty's input on a penalty step
         if self.diffaug:
             par0 = self._diffaug_draw(aug_key, 0, 2 * B, S)
-            p = D.forward_packed(ops.diffaug_fwd(d_in, par0), ctx_d, keep_maps=False)   # the maps are those of T(fake): not handed over
+            d_aug = ops.diffaug_fwd(d_in, par0)
+            x_real = d_aug[:B]
+            p = D.forward_packed(d_aug, ctx_d, keep_maps=False)   # the maps are those of T(fake): not handed over
             if adaptive and not run_adj:   # after the step's last draw: step n + 1 is the first to see a new p
                 self._ada_control(p, B)
         else:
@@ -207,6 +217,10 @@ class EagerTrainer:
             # gradients are added to the disc tape's before the all-reduce
             D.gradient_penalty(ops.gp_interp(new_image, fake, gp_eps), a.gp_weight, self.losses["disc"], self.losses["gp"],
                                train_range=rng_d)
+        if self.r1_step(batch_no):
+            # disc_loss += (r1_gamma r1_interval / 2) mean_b |d logit(x_b) / d x_b|^2 over the real rows D read (under diff_augment the
+            # augmented rows, kept from above: no new draw); its weight gradients are added to the disc tape's before the all-reduce
+            D.r1_penalty(x_real, self.r1["weight"], self.losses["disc"], self.losses["r1"], train_range=rng_d)
         self.sync.launch("D", self.store, *self.store.model_range("D", *rng_d))
 
         # ---- gen tape (eager_trainer.py:140,149): BCE(.98,fake_pr) + BCE(c2,fake_c) + l1*mean|img2-fake|
@@ -355,11 +369,16 @@ class EagerTrainer:
         return self.ema_weights() if (self.ema_decay > 0.0 and self.sample_ema) else contextlib.nullcontext()
 
     # ------------------------------------------------------------------ the same step as a replayed HIP graph
+    def r1_step(self, batch_no: int) -> bool:
+        """Whether this step carries the R1 penalty: stateless and resumable, like the partition steps."""
+        return self.r1 is not None and batch_no % self.r1["interval"] == 0
+
     def step_kind(self, batch_no: int):
-        """Steps with the same kind enqueue the same kernels on the same shapes: (partition group or -1, Adjuster on)."""
+        """Steps with the same kind enqueue the same kernels on the same shapes: (partition group or -1, Adjuster on, R1 penalty step;
+        the last is constant with r1_gamma == 0)."""
         a = self.args
         part = (batch_no // (a.partition_interval + 1)) % 3 if (a.use_partition and batch_no % (a.partition_interval + 1) == 0) else -1
-        return part, bool(a.train_adj and batch_no > 10)
+        return part, bool(a.train_adj and batch_no > 10), self.r1_step(batch_no)
 
     def graph_step(self, batch_no: int, inp: Dict[str, torch.Tensor]):
         """train_step_from_inputs through a captured HIP graph, one graph per step kind (full step, the three partition
@@ -567,7 +586,8 @@ class EagerTrainer:
                     lg, ld = float(result[3]), float(result[4])
                     la = float(result[5]) if result[5] is not None else float("nan")
                     aug_p = "" if self.ada is None else f" AugP {float(self.ada_p()):.4f}"   # read where the losses are: no sync of its own
-                    print(f"  [{seen}] LossG {lg:.4f} LossD {ld:.4f} LossA {la:.4f}{aug_p}")
+                    r1 = "" if self.r1 is None else f" R1 {float(self.losses['r1']):.4f}"   # the term of the most recent penalty step
+                    print(f"  [{seen}] LossG {lg:.4f} LossD {ld:.4f} LossA {la:.4f}{r1}{aug_p}")
                 if b % a.freq_test == 0 and io and self.test_cond is not None:
                     self.predict(self.test_noise, self.test_cond, self.test_image,
                                  os.path.join(a.result_dir, "test", "gen", "%d-%d.jpg" % (e, b)),

@@ -684,6 +684,35 @@ class Discriminator(_Module):
             self.encoder.gp_second_backward(ctx, g2.view(B, i, i, f), uz2, levels)
         return r
 
+    def r1_penalty(self, image, weight: float, loss=None, r1_loss=None, train_range=None):
+        """R1 penalty of this project (the reference has none): image = what D reads as its real batch [B,H,W,C],
+        l_b = the PRE-sigmoid value of output_pr(image_b), g_b = dl_b/dimage_b, r2_b = |g_b|^2, r1 = (weight / 2) mean_b r2_b.
+        loss (+)= r1, r1_loss = r1 (1-element device tensors, may be None).  The gradients of r1 w.r.t.
+        Discriminator.weights[lo:hi] (train_range, default all 20) are ADDED to the gradient views (the disc tape has written them);
+        dense_cond, dense_pr.bias and norm4.beta get exactly nothing.  The pass of gradient_penalty with the sigmoid taken out: the
+        top seed is w_pr itself, the heads have no second-order term and the second backward starts from a zero top gradient,
+        driven by the injected adjoints alone.  Returns r2 [B]."""
+        lo, hi = train_range if train_range is not None else (0, 20)
+        heads = lo <= 16 and hi >= 20
+        levels = [i for i in range(1, 5) if lo <= 4 * (i - 1) and 4 * i <= hi]
+        ctx: dict = {}
+        self.forward_packed(image, ctx)
+        B = image.shape[0]
+        i, f = self.args.init_dim, self.args.conv_filter[0]
+        g_top = ops.r1_heads_seed(self._w["dense_pr.kernel"], B)
+        g0, rec = self.encoder.backward_recorded(ctx, g_top.view(B, i, i, f))
+        u0, r2 = ops.r1_seed(g0, weight, loss, r1_loss)
+        u4, uz2 = self.encoder.gp_sweep(ctx, rec, u0, levels, min(levels) if levels else 5)
+        if heads:
+            ops.r1_heads_colsum(u4.view(B, -1), self._g["dense_pr.kernel"])
+        if levels:
+            # the zero top gradient: made once per shape (the second backward never writes it), so a step enqueues no fill
+            zero = getattr(self, "_r1_zero", None)
+            if zero is None or tuple(zero.shape) != (B, i, i, f) or zero.device != image.device:
+                zero = self._r1_zero = torch.zeros(B, i, i, f, dtype=torch.float32, device=image.device)
+            self.encoder.gp_second_backward(ctx, zero, uz2, levels)
+        return r2
+
 
 class Adjuster(_Module):
     """model.py:108-136: encoder shared with D, decoder and final conv shared with G; own = dense, norm."""

@@ -1511,3 +1511,41 @@ def gp_heads_2nd(p, wpr, x, u, dwpr=None, dbpr=None):
     check(_lib.load().lg_gp_heads_2nd(_p(p), _p(wpr), _p(x), _p(u), _p(t), _p(g2), _p(dwpr), _p(dbpr), B, K, J - 1, _stream()),
           "lg_gp_heads_2nd")
     return t, g2
+
+
+# ------------------------------------------------------------------ R1 gradient penalty (r1.hip; include/littlegan_hip_reg.h)
+def r1_heads_seed(wpr, B):
+    """g [B, K] = wpr for every row: the gradient of the pre-sigmoid output_pr on the heads input (step 2 of the pass)"""
+    K = wpr.shape[0]
+    _chk(wpr, (K, 1), "wpr")
+    g = torch.empty(int(B), K, dtype=torch.float32, device=wpr.device)
+    check(_lib.load().lgr_r1_heads_seed(_p(wpr), _p(g), int(B), K, _stream()), "lgr_r1_heads_seed")
+    return g
+
+
+def r1_seed(g, weight, loss=None, r1_loss=None):
+    """g = the image gradient of the logit: -> (u0 = (weight / B) g, r2 [B] = |g_b|^2); loss (+)= term, r1_loss = term with
+    term = (weight / 2) mean_b r2 (step 4)"""
+    _chk(g, name="g")
+    B = g.shape[0]
+    L = g.numel() // B
+    for t, nm in ((loss, "loss"), (r1_loss, "r1_loss")):
+        if t is not None:
+            _chk(t, (1,), nm)
+    u0 = torch.empty_like(g)
+    r2 = torch.empty(B, dtype=torch.float32, device=g.device)
+    lib = _lib.load()
+    ws = workspace(int(lib.lgr_r1_workspace_bytes(B, L)), g.device, "r1")
+    check(lib.lgr_r1_seed(_p(g), _p(u0), _p(r2), _p(loss), _p(r1_loss), float(weight), _p(ws), ws.numel(), B, L, _stream()), "lgr_r1_seed")
+    return u0, r2
+
+
+def r1_heads_colsum(u, dwpr):
+    """dwpr [K, 1] += sum_b u[b] (step 6: the logit is bilinear in (w_pr, h4), so this is all the heads receive)"""
+    _chk(u, name="u")
+    B, K = u.shape
+    _chk(dwpr, (K, 1), "dwpr")
+    lib = _lib.load()
+    ws = workspace(int(lib.lgr_r1_colsum_workspace_bytes(B, K)), u.device, "r1")
+    check(lib.lgr_r1_heads_colsum(_p(u), _p(dwpr), _p(ws), ws.numel(), B, K, _stream()), "lgr_r1_heads_colsum")
+    return dwpr
