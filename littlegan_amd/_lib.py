@@ -1,5 +1,5 @@
 """ctypes binding of liblittlegan_hip.so (C ABI: include/littlegan_hip.h, include/littlegan_hip_ext.h for the lgx_ extensions and
-include/littlegan_hip_reg.h for the lgr_ regularisers).
+include/littlegan_hip_reg.h for the lgr_ regularisers, include/littlegan_hip_obj.h for the lgo_ logit-side objectives).
 
 The product path has NO fallback: if the shared library is missing this module raises at
 import of the symbol table, and every op raises `LittleGanHipError` on a non-zero return.
@@ -167,6 +167,14 @@ REG_SIGNATURES = {
 }
 
 
+# logit-side GAN objectives (include/littlegan_hip_obj.h, prefix lgo_): exported by the same library, bound beside them
+OBJ_SIGNATURES = {
+    # gan_loss (objective.hip): the heads forward that keeps the logit of output_pr, and the loss on it
+    "lgo_heads_fwd": (I, [P, P, P, P, P, P, P, P, Z, I, I, I, P]),
+    "lgo_gan_heads_loss_fwd_bwd": (I, [P, P, P, I, I, F, F, P, P, I, I, I, P]),
+}
+
+
 class LittleGanHipError(RuntimeError):
     pass
 
@@ -199,7 +207,7 @@ def load():
     # before torch, the system runtime it links against would come in as a SECOND runtime and its kernels would see no device.
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(REG_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(REG_SIGNATURES.items()) + list(OBJ_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

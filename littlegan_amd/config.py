@@ -11,7 +11,10 @@ row with probability p, fixed or driven on the device towards ada_target; null /
 evaluate_metrics (list out of fid, kid, prdc: what `evaluate` computes; ["fid"] = the reference's run) / evaluate_real_activations (the
 real images' saved activations that kid and prdc need) / kid_subsets / kid_subset_size / prdc_k (metrics.py),
 r1_gamma / r1_interval (R1 gradient penalty on the Discriminator's real-image logit, (r1_gamma r1_interval / 2) mean |dlogit/dx|^2 added
-to the disc loss on every r1_interval-th step; 0 = off; excludes use_gp and dropout_train, allowed with diff_augment)."""
+to the disc loss on every r1_interval-th step; 0 = off; excludes use_gp and dropout_train, allowed with diff_augment),
+gan_loss ("bce" | "logistic" | "hinge" | "lsgan" | "wgan": the real / fake terms of the three losses; "bce" = the reference's sigmoid +
+clipped cross entropy against 0.98 / 0.02, the others are taken on the pre-sigmoid value of output_pr without smoothing; "wgan" needs
+use_gp, which then penalises the logit)."""
 import json
 import os
 from argparse import ArgumentParser
@@ -90,7 +93,25 @@ DEFAULTS = {
     # (batch_no % r1_interval == 0) disc_loss += (r1_gamma r1_interval / 2) mean_b |d logit(x_b) / d x_b|^2 over the real rows D read (under
     # diff_augment: the augmented rows, differentiated with respect to them).  r1_gamma 0 = off.  Excludes use_gp and dropout_train.
     'r1_gamma': 0.0, 'r1_interval': 16,
+    # objective of the real / fake terms: "bce" = the reference's (sigmoid + clipped cross entropy against the smoothed
+    # targets); "logistic" (non-saturating), "hinge", "lsgan", "wgan" are taken on the logit of output_pr, without label smoothing.  The
+    # attribute and L1 terms are the same under every value.  "wgan" needs use_gp; under a logit-side objective use_gp penalises the logit.
+    'gan_loss': 'bce',
 }
+
+GAN_LOSS_KINDS = {"bce": 0, "logistic": 1, "hinge": 2, "lsgan": 3, "wgan": 4}   # the `kind` of lgo_gan_heads_loss_fwd_bwd; 0 = not its
+
+
+def gan_loss_kind(name, use_gp=None) -> int:
+    """The gan_loss key as the `kind` of lgo_gan_heads_loss_fwd_bwd (0 for "bce": the reference's objective, none of that code runs).
+    Raises ValueError for anything but one of the five names as a string and, when use_gp is given (not None), for "wgan" without
+    use_gp: the Wasserstein objective has no bound of its own and needs the penalty on the logit."""
+    if not isinstance(name, str) or name not in GAN_LOSS_KINDS:
+        raise ValueError(f"gan_loss must be one of {', '.join(GAN_LOSS_KINDS)} (a string), got {name!r}")
+    if name == "wgan" and use_gp is not None and not use_gp:
+        raise ValueError("gan_loss 'wgan' needs use_gp: the Wasserstein objective is unbounded without the gradient penalty on the logit "
+                         "(DESIGN.md §25)")
+    return GAN_LOSS_KINDS[name]
 
 DIFF_AUGMENT_BITS = {"color": 1, "translation": 2, "cutout": 4}
 
@@ -204,6 +225,7 @@ class Arg:
         diff_augment_bits(self.diff_augment)   # a misspelt component fails here, not at the first training step
         ada_settings(self.diff_augment, self.diff_augment_p, self.ada_target, self.ada_interval, self.ada_kimg)
         r1_settings(self.r1_gamma, self.r1_interval)
+        gan_loss_kind(self.gan_loss, bool(self.use_gp))   # a misspelt objective fails here, and so does wgan without its penalty
         self.evaluate_metrics = metric_list(self.evaluate_metrics)   # a misspelt metric fails here, not after the sampling run
         if int(self.kid_subsets) < 0 or int(self.kid_subset_size) < 2 or not 1 <= int(self.prdc_k) <= 15:
             raise ValueError("need kid_subsets >= 0, kid_subset_size >= 2 and 1 <= prdc_k <= 15")

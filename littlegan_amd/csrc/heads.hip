@@ -197,13 +197,12 @@ extern "C" size_t lg_heads_fwd_workspace_bytes(int B, int K, int c) {
   return (size_t)lg_cdiv(K, FKC) * (size_t)B * (size_t)(c + 1) * sizeof(float);
 }
 
-extern "C" int lg_heads_fwd(const float* x, const float* wpr, const float* bpr, const float* wc, const float* bc,
-                            float* p, void* workspace, size_t ws_bytes, int B, int K, int c, void* stream) {
-  LG_CHECK_ARG(x && wpr && bpr && wc && bc && p && workspace, "lg_heads_fwd: null pointer");
-  LG_CHECK_ARG(B > 0 && K > 0 && K % 4 == 0 && c >= 1 && c <= HC_MAX, "lg_heads_fwd: bad shape B=%d K=%d c=%d", B, K, c);
-  LG_CHECK_ARG(ws_bytes >= lg_heads_fwd_workspace_bytes(B, K, c), "lg_heads_fwd: workspace too small (%zu bytes)", ws_bytes);
+// The partials stage of the heads forward: route choice (fp32 matrix instruction on aligned shapes, else the VALU kernel), the split of
+// K (*nkc_out slices) and the GEMM launch into part[nkc][B][1 + c].  Shared by lg_heads_fwd and lgo_heads_fwd (objective.hip), which
+// differ in their finaliser alone.  The arguments are the caller's, already checked.
+extern "C" int lg_heads_fwd_partials(const float* x, const float* wpr, const float* wc, float* part, int B, int K, int c, int* nkc_out,
+                                     void* stream) {
   int nkc = lg_cdiv(K, FKC);
-  float* part = (float*)workspace;
   const int rc = lg_heads_fwd_mfma_try(x, wpr, wc, part, B, K, c, &nkc, stream);  // aligned shapes: fp32 matrix instruction
   if (rc != LG_OK && rc != LG_ERR_UNSUPPORTED) return rc;
   if (rc == LG_ERR_UNSUPPORTED) {
@@ -212,6 +211,19 @@ extern "C" int lg_heads_fwd(const float* x, const float* wpr, const float* bpr, 
     LG_CHECK_LAUNCH("lg_heads_fwd");
     lg_note_kernel("heads_fwd_kernel");
   }
+  *nkc_out = nkc;
+  return LG_OK;
+}
+
+extern "C" int lg_heads_fwd(const float* x, const float* wpr, const float* bpr, const float* wc, const float* bc,
+                            float* p, void* workspace, size_t ws_bytes, int B, int K, int c, void* stream) {
+  LG_CHECK_ARG(x && wpr && bpr && wc && bc && p && workspace, "lg_heads_fwd: null pointer");
+  LG_CHECK_ARG(B > 0 && K > 0 && K % 4 == 0 && c >= 1 && c <= HC_MAX, "lg_heads_fwd: bad shape B=%d K=%d c=%d", B, K, c);
+  LG_CHECK_ARG(ws_bytes >= lg_heads_fwd_workspace_bytes(B, K, c), "lg_heads_fwd: workspace too small (%zu bytes)", ws_bytes);
+  int nkc = 0;
+  float* part = (float*)workspace;
+  const int rc = lg_heads_fwd_partials(x, wpr, wc, part, B, K, c, &nkc, stream);
+  if (rc != LG_OK) return rc;
   hipLaunchKernelGGL(heads_final_kernel, dim3(lg_cdiv(B * (c + 1), 256)), dim3(256), 0, (hipStream_t)stream, part, bpr,
                      bc, p, B, c, nkc);
   LG_CHECK_LAUNCH("lg_heads_fwd(final)");  // (the name noted stays that of the GEMM kernel: heads_final_kernel follows both)

@@ -98,6 +98,11 @@ extern "C" int lg_n3_s1t_fwd_rows_try(const void* x16, const float* stats, float
 extern "C" size_t lg_conv_pack_up_offset(int cb, int cs, int dtype);
 extern "C" size_t lg_conv_pack_raw_offset(int cb, int cs, int dtype);   // cb == 3: the verbatim fp32 kernel [5][5][3][cs]
 
+// ---- heads.hip ----  the partials stage of the heads forward (route, split of K, GEMM launch): part[*nkc_out][B][1 + c]; arguments checked
+// by the caller (lg_heads_fwd, lgo_heads_fwd)
+extern "C" int lg_heads_fwd_partials(const float* x, const float* wpr, const float* wc, float* part, int B, int K, int c, int* nkc_out,
+                                     void* stream);
+
 // ---- skinny_mfma.hip ----  the dense / head GEMMs on the exact-f32 MFMA
 extern "C" int lg_heads_fwd_mfma_try(const float* x, const float* wpr, const float* wc, float* part, int B, int K, int c,
                                      int* nkc_out, void* stream);

@@ -17,7 +17,7 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from .config import ada_settings, diff_augment_bits, r1_settings
+from .config import ada_settings, diff_augment_bits, gan_loss_kind, r1_settings
 from .dist import GradSync
 from .model import Adjuster, Discriminator, Generator, ParamStore
 from .utils import save_image, soft
@@ -98,6 +98,10 @@ class EagerTrainer:
         if self.r1 is not None and self.dropout:
             raise ValueError("r1_gamma and dropout_train exclude each other: the penalty's double backward through a masked norm "
                              "is not built (DESIGN.md §24)")
+        # objective of the real / fake terms (the reference's is "bce"): read once.  0 = "bce", the step as it always was,
+        # none of the logit-side code runs; else the `kind` of ops.gan_heads_loss, and use_gp penalises the logit
+        self.gan_loss = getattr(args, "gan_loss", "bce")
+        self.gan_kind = gan_loss_kind(self.gan_loss, self.use_gp)
         # weight average for sampling (the reference has none): on when ema_decay > 0
         self.ema_decay = validate_ema_decay(getattr(args, "ema_decay", 0.0))
         self.sample_ema = bool(getattr(args, "sample_ema", True))
@@ -194,20 +198,28 @@ class EagerTrainer:
             self._ada_tick()
         # the Adjuster reuses D's encoder maps of `fake` as its skip inputs: keep the fp32 maps only then
         x_real = new_image   # what D reads as its real batch: the R1 penalty's input on a penalty step
+        kind = self.gan_kind
+        lk = dict(logits=True) if kind else {}   # a logit-side objective: the heads keep z_pr (same launches, another finaliser)
         if self.diffaug:
             par0 = self._diffaug_draw(aug_key, 0, 2 * B, S)
             d_aug = ops.diffaug_fwd(d_in, par0)
             x_real = d_aug[:B]
-            p = D.forward_packed(d_aug, ctx_d, keep_maps=False)   # the maps are those of T(fake): not handed over
+            p = D.forward_packed(d_aug, ctx_d, keep_maps=False, **lk)   # the maps are those of T(fake): not handed over
             if adaptive and not run_adj:   # after the step's last draw: step n + 1 is the first to see a new p
                 self._ada_control(p, B)
         else:
-            p = D.forward_packed(d_in, ctx_d, keep_maps=run_adj, drop=drop[0])  # [2B, 1+c]: rows [0,B) real, [B,2B) fake
+            p = D.forward_packed(d_in, ctx_d, keep_maps=run_adj, drop=drop[0], **lk)  # [2B, 1+c]: rows [0,B) real, [B,2B) fake
 
         # ---- disc tape (eager_trainer.py:139,145): 2*BCE(c1,real_c) + BCE(.98,real_pr) + BCE(.02,fake_pr)
         dz = torch.empty(2 * B, 1 + c, dtype=torch.float32, device=self.device)
-        ops.bce_heads_loss(p[:B], c1, soft(1.0), 1.0, 2.0, self.losses["disc"], dz[:B], False)
-        ops.bce_heads_loss(p[B:], None, soft(0.0), 1.0, 0.0, self.losses["disc"], dz[B:], True)
+        # (a logit-side gan_loss, DESIGN.md §25: the two BCE(., _pr) become f(z) of the D-real / D-fake rows, no smoothing; the same launches)
+        if kind:
+            z = ctx_d["z_pr"]
+            ops.gan_heads_loss(p[:B], z[:B], c1, kind, ops.GAN_ROLE_D_REAL, 1.0, 2.0, self.losses["disc"], dz[:B], False)
+            ops.gan_heads_loss(p[B:], z[B:], None, kind, ops.GAN_ROLE_D_FAKE, 1.0, 0.0, self.losses["disc"], dz[B:], True)
+        else:
+            ops.bce_heads_loss(p[:B], c1, soft(1.0), 1.0, 2.0, self.losses["disc"], dz[:B], False)
+            ops.bce_heads_loss(p[B:], None, soft(0.0), 1.0, 0.0, self.losses["disc"], dz[B:], True)
         # a partition step differentiates one weight group only (eager_trainer.py:104-113,145): untrained groups get no
         # weight-gradient kernels, no all-reduce, and the backward chain stops where nothing below is asked for
         rng_d = train_weight_range(a, "D", batch_no)
@@ -215,8 +227,9 @@ class EagerTrainer:
         if self.use_gp:
             # disc_loss += gp_weight * mean_b (|d output_pr(x^_b) / d x^_b| - 1)^2 on x^ = eps new_image + (1 - eps) fake; its weight
             # gradients are added to the disc tape's before the all-reduce
+            # (under a logit-side gan_loss the penalised quantity is the logit: DESIGN.md §25)
             D.gradient_penalty(ops.gp_interp(new_image, fake, gp_eps), a.gp_weight, self.losses["disc"], self.losses["gp"],
-                               train_range=rng_d)
+                               train_range=rng_d, **(dict(logit=True) if kind else {}))
         if self.r1_step(batch_no):
             # disc_loss += (r1_gamma r1_interval / 2) mean_b |d logit(x_b) / d x_b|^2 over the real rows D read (under diff_augment the
             # augmented rows, kept from above: no new draw); its weight gradients are added to the disc tape's before the all-reduce
@@ -225,7 +238,10 @@ class EagerTrainer:
 
         # ---- gen tape (eager_trainer.py:140,149): BCE(.98,fake_pr) + BCE(c2,fake_c) + l1*mean|img2-fake|
         dz_g = torch.empty(B, 1 + c, dtype=torch.float32, device=self.device)
-        ops.bce_heads_loss(p[B:], c2, soft(1.0), 1.0, 1.0, self.losses["gen"], dz_g, False)
+        if kind:
+            ops.gan_heads_loss(p[B:], ctx_d["z_pr"][B:], c2, kind, ops.GAN_ROLE_G, 1.0, 1.0, self.losses["gen"], dz_g, False)
+        else:
+            ops.bce_heads_loss(p[B:], c2, soft(1.0), 1.0, 1.0, self.losses["gen"], dz_g, False)
         g_img = D.backward(ctx_d, dz_g, need_wgrad=False, need_input_grad=True, rows=slice(B, 2 * B))
         if self.diffaug:
             g_img = ops.diffaug_bwd(g_img, par0[B:])   # the gen tape is differentiated through T: rows B..2B of slot 0
@@ -254,11 +270,14 @@ class EagerTrainer:
                 par1 = self._diffaug_draw(aug_key, 1, 2 * B, S)
                 if adaptive:   # both draws of the step have read p: the real rows of slot 0 feed the controller
                     self._ada_control(p, B)
-                p_a = D.forward_packed(ops.diffaug_fwd(adj_image, par1), ctx_d2, keep_maps=False, top_only=True)
+                p_a = D.forward_packed(ops.diffaug_fwd(adj_image, par1), ctx_d2, keep_maps=False, top_only=True, **lk)
             else:
-                p_a = D.forward_packed(adj_image, ctx_d2, keep_maps=False, top_only=True, drop=drop[2])
+                p_a = D.forward_packed(adj_image, ctx_d2, keep_maps=False, top_only=True, drop=drop[2], **lk)
             dz_a = torch.empty(2 * B, 1 + c, dtype=torch.float32, device=self.device)
-            ops.bce_heads_loss(p_a, adj_t_cond, soft(1.0), 1.0, 1.0, self.losses["adj"], dz_a, False)
+            if kind:
+                ops.gan_heads_loss(p_a, ctx_d2["z_pr"], adj_t_cond, kind, ops.GAN_ROLE_G, 1.0, 1.0, self.losses["adj"], dz_a, False)
+            else:
+                ops.bce_heads_loss(p_a, adj_t_cond, soft(1.0), 1.0, 1.0, self.losses["adj"], dz_a, False)
             g_adj = D.backward(ctx_d2, dz_a, need_wgrad=False, need_input_grad=True)
             if self.diffaug:
                 g_adj = ops.diffaug_bwd(g_adj, par1)

@@ -628,13 +628,20 @@ class Discriminator(_Module):
         return self.encoder.weights + [self._w[n] for n in self._names]
 
     def forward_packed(self, image, ctx: Optional[dict] = None, keep_maps: bool = True, top_only: bool = False,
-                       drop: Optional[ops.Drop] = None):
+                       drop: Optional[ops.Drop] = None, logits: bool = False):
         """top_only: no weight gradient will be asked of this pass and only the heads read the encoder (see Encoder.__call__).
-        drop: the encoder's drop context of this pass (training step only; backward() finds it in ctx)."""
+        drop: the encoder's drop context of this pass (training step only; backward() finds it in ctx).
+        logits: the heads also keep the pre-sigmoid value of output_pr as ctx["z_pr"] [B] (a logit-side gan_loss); the
+        returned p is the same bits either way."""
         outs = self.encoder(image, ctx, keep_maps=keep_maps, top_only=top_only, drop=drop)
         x = outs[3].view(image.shape[0], -1)
-        p = ops.heads_fwd(x, self._w["dense_pr.kernel"], self._w["dense_pr.bias"], self._w["dense_cond.kernel"],
-                          self._w["dense_cond.bias"])
+        heads = (self._w["dense_pr.kernel"], self._w["dense_pr.bias"], self._w["dense_cond.kernel"], self._w["dense_cond.bias"])
+        if logits:
+            if ctx is None:
+                raise ValueError("forward_packed: logits=True needs a ctx to keep z_pr in")
+            p, ctx["z_pr"] = ops.heads_fwd_logit(x, *heads)
+        else:
+            p = ops.heads_fwd(x, *heads)
         if ctx is not None:
             ctx["heads_x"] = x
         return p
@@ -660,12 +667,16 @@ class Discriminator(_Module):
         i, f = self.args.init_dim, self.args.conv_filter[0]
         return self.encoder.backward(ctx, dx.view(-1, i, i, f), bool(levels), need_input_grad, rows, wgrad_levels=levels)
 
-    def gradient_penalty(self, image, gp_weight: float, loss=None, gp_loss=None, train_range=None):
+    def gradient_penalty(self, image, gp_weight: float, loss=None, gp_loss=None, train_range=None, logit: bool = False):
         """Gradient penalty of this project (the reference raises, eager_trainer.py:141-143): image = x^ [B,H,W,C],
         p_b = output_pr(x^_b), g_b = dp_b/dx^_b, r_b = |g_b|, gp = mean_b (r_b - 1)^2.  loss (+)= gp_weight gp, gp_loss =
         gp_weight gp (1-element device tensors, may be None).  The gradients of gp_weight gp w.r.t. Discriminator.weights[lo:hi]
         (train_range, default all 20) are ADDED to the gradient views (the disc tape has written them); dense_cond gets
-        nothing.  Returns r [B]."""
+        nothing.  Returns r [B].
+        logit: the penalty is taken on l_b, the PRE-sigmoid value of output_pr, instead of p_b (a logit-side gan_loss):
+        r1_penalty's pass with the seed of this penalty on the image gradient; dense_pr.bias and norm4.beta get nothing either."""
+        if logit:
+            return self._logit_penalty(ops.gp_seed, image, gp_weight, loss, gp_loss, train_range)
         lo, hi = train_range if train_range is not None else (0, 20)
         heads = lo <= 16 and hi >= 20
         levels = [i for i in range(1, 5) if lo <= 4 * (i - 1) and 4 * i <= hi]
@@ -692,6 +703,11 @@ class Discriminator(_Module):
         dense_cond, dense_pr.bias and norm4.beta get exactly nothing.  The pass of gradient_penalty with the sigmoid taken out: the
         top seed is w_pr itself, the heads have no second-order term and the second backward starts from a zero top gradient,
         driven by the injected adjoints alone.  Returns r2 [B]."""
+        return self._logit_penalty(ops.r1_seed, image, weight, loss, r1_loss, train_range)
+
+    def _logit_penalty(self, seed, image, weight, loss, term_loss, train_range):
+        """The reverse-over-reverse pass of a penalty on the image gradient of the logit; `seed` (ops.r1_seed: |g|^2, or ops.gp_seed:
+        (|g| - 1)^2) turns that gradient into the term, the adjoint u0 and the per-row value it returns."""
         lo, hi = train_range if train_range is not None else (0, 20)
         heads = lo <= 16 and hi >= 20
         levels = [i for i in range(1, 5) if lo <= 4 * (i - 1) and 4 * i <= hi]
@@ -701,7 +717,7 @@ class Discriminator(_Module):
         i, f = self.args.init_dim, self.args.conv_filter[0]
         g_top = ops.r1_heads_seed(self._w["dense_pr.kernel"], B)
         g0, rec = self.encoder.backward_recorded(ctx, g_top.view(B, i, i, f))
-        u0, r2 = ops.r1_seed(g0, weight, loss, r1_loss)
+        u0, r2 = seed(g0, weight, loss, term_loss)
         u4, uz2 = self.encoder.gp_sweep(ctx, rec, u0, levels, min(levels) if levels else 5)
         if heads:
             ops.r1_heads_colsum(u4.view(B, -1), self._g["dense_pr.kernel"])

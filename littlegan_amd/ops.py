@@ -837,6 +837,46 @@ def bce_heads_loss(p, t_c, t_pr, w_pr, w_c, loss, dz, accumulate):
                                                 B, J - 1, int(accumulate), _stream()), "lg_bce_heads_loss_fwd_bwd")
 
 
+# ------------------------------------------------------------------ logit-side objectives (objective.hip; include/littlegan_hip_obj.h)
+GAN_ROLE_D_REAL, GAN_ROLE_D_FAKE, GAN_ROLE_G = 0, 1, 2
+
+
+def heads_fwd_logit(x, wpr, bpr, wc, bc, out=None, z_out=None):
+    """heads_fwd that also keeps the logit of output_pr: -> (p [B, 1 + c], bit for bit heads_fwd's; z_pr [B], the pre-sigmoid p[:, 0])"""
+    B, K = x.shape
+    c = wc.shape[1]
+    _chk(x, name="x")
+    _chk(wpr, (K, 1), "wpr")
+    _chk(bpr, (1,), "bpr")
+    _chk(wc, (K, c), "wc")
+    _chk(bc, (c,), "bc")
+    if out is None:
+        out = torch.empty(B, 1 + c, dtype=torch.float32, device=x.device)
+    if z_out is None:
+        z_out = torch.empty(B, dtype=torch.float32, device=x.device)
+    _chk(out, (B, 1 + c), "out")
+    _chk(z_out, (B,), "z_out")
+    lib = _lib.load()
+    ws = workspace(int(lib.lg_heads_fwd_workspace_bytes(B, K, c)), x.device, "small")
+    check(lib.lgo_heads_fwd(_p(x), _p(wpr), _p(bpr), _p(wc), _p(bc), _p(out), _p(z_out), _p(ws), ws.numel(), B, K, c, _stream()),
+          "lgo_heads_fwd")
+    return out, z_out
+
+
+def gan_heads_loss(p, z_pr, t_c, kind, role, w_pr, w_c, loss, dz, accumulate):
+    """bce_heads_loss with the real / fake term taken on the logit z_pr [B]: kind 1 logistic, 2 hinge, 3 lsgan, 4 wgan; role 0 D on real
+    rows, 1 D on fake rows, 2 G / Adjuster.  The attribute term (t_c, w_c) is bce_heads_loss's."""
+    B, J = p.shape
+    _chk(p, name="p")
+    _chk(z_pr, (B,), "z_pr")
+    _chk(dz, (B, J), "dz")
+    _chk(loss, (1,), "loss")
+    if t_c is not None:
+        _chk(t_c, (B, J - 1), "t_c")
+    check(_lib.load().lgo_gan_heads_loss_fwd_bwd(_p(p), _p(z_pr), _p(t_c), int(kind), int(role), float(w_pr), float(w_c), _p(loss), _p(dz),
+                                                 B, J - 1, int(accumulate), _stream()), "lgo_gan_heads_loss_fwd_bwd")
+
+
 def l1_tanh_loss(t, img, g_in, dpre, loss, lam, accumulate):
     _chk(t, name="t")
     _chk(img, t.shape, "img")
