@@ -1,5 +1,5 @@
-"""ctypes binding of liblittlegan_hip.so (C ABI: include/littlegan_hip.h, include/littlegan_hip_ext.h for the lgx_ extensions and
-include/littlegan_hip_reg.h for the lgr_ regularisers, include/littlegan_hip_obj.h for the lgo_ logit-side objectives).
+"""ctypes binding of liblittlegan_hip.so.  The C ABI is every function declared in include/littlegan_hip*.h; SIGNATURES below is its one
+table (tests/test_abi.py holds it to the headers and to the symbols the library exports).
 
 The product path has NO fallback: if the shared library is missing this module raises at
 import of the symbol table, and every op raises `LittleGanHipError` on a non-zero return.
@@ -144,31 +144,20 @@ SIGNATURES = {
     "lg_soft_labels": (I, [P, P, P, I, I, I, P, P]),
     "lg_augment_drawn_u8_workspace_bytes": (Z, [I]),
     "lg_augment_drawn_u8": (I, [P, P, P, P, I, I, I, F, F, F, F, F, L, L, L, P, Z, P]),
-}
-
-# training-control extensions (include/littlegan_hip_ext.h, prefix lgx_): exported by the same library, bound beside SIGNATURES
-EXT_SIGNATURES = {
+    # training-control extensions (include/littlegan_hip_ext.h)
     # adaptive augmentation probability (ada.hip): the gated draw and the controller of p; state = 16 device bytes
     "lgx_diffaug_draw_gated": (I, [P, I, I, I, I, I, P, P, P]),
     "lgx_ada_init": (I, [P, F, P]),
     "lgx_ada_accumulate": (I, [P, P, I, I, P]),
     "lgx_ada_adjust": (I, [P, I, F, F, P]),
-}
-
-
-# regularisers beyond the reference's recipe (include/littlegan_hip_reg.h, prefix lgr_): exported by the same library, bound beside them
-REG_SIGNATURES = {
+    # regularisers beyond the reference's recipe (include/littlegan_hip_reg.h)
     # R1 gradient penalty (r1.hip): the top seed, the seed on the image gradient, the heads' column sum
     "lgr_r1_workspace_bytes": (Z, [I, L]),
     "lgr_r1_heads_seed": (I, [P, P, I, I, P]),
     "lgr_r1_seed": (I, [P, P, P, P, P, F, P, Z, I, L, P]),
     "lgr_r1_colsum_workspace_bytes": (Z, [I, I]),
     "lgr_r1_heads_colsum": (I, [P, P, P, Z, I, I, P]),
-}
-
-
-# logit-side GAN objectives (include/littlegan_hip_obj.h, prefix lgo_): exported by the same library, bound beside them
-OBJ_SIGNATURES = {
+    # logit-side GAN objectives (include/littlegan_hip_obj.h)
     # gan_loss (objective.hip): the heads forward that keeps the logit of output_pr, and the loss on it
     "lgo_heads_fwd": (I, [P, P, P, P, P, P, P, P, Z, I, I, I, P]),
     "lgo_gan_heads_loss_fwd_bwd": (I, [P, P, P, I, I, F, F, P, P, I, I, I, P]),
@@ -207,7 +196,7 @@ def load():
     # before torch, the system runtime it links against would come in as a SECOND runtime and its kernels would see no device.
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(REG_SIGNATURES.items()) + list(OBJ_SIGNATURES.items()):
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -41,11 +41,8 @@ def build(force=False, verbose=True, variant=None):
         raise SystemExit("LG_EXTRA_FLAGS needs --variant NAME: ablation builds never replace the product library")
     os.makedirs(objdir, exist_ok=True)
     # every source includes lg_internal.h, and through it lg_common.h and the public header: all headers are every object's dependencies
-    # (littlegan_hip_ext.h, the training-control extensions, is included by ada.hip alone, littlegan_hip_reg.h, the regularisers, by
-    # r1.hip alone, littlegan_hip_obj.h, the logit-side objectives, by objective.hip alone; all three are listed with them)
     inc = os.path.join(os.path.dirname(PKG), "include")
-    headers = sorted(glob.glob(os.path.join(HERE, "*.h"))) + [os.path.join(inc, "littlegan_hip.h"), os.path.join(inc, "littlegan_hip_ext.h"),
-                                                              os.path.join(inc, "littlegan_hip_reg.h"), os.path.join(inc, "littlegan_hip_obj.h")]
+    headers = sorted(glob.glob(os.path.join(HERE, "*.h"))) + sorted(glob.glob(os.path.join(inc, "littlegan_hip*.h")))
 
     # LG_EXTRA_FLAGS carries the ablation macros of scripts/probe/*.sh ("results wrong, timing only"): the flag set an object
     # was built with is recorded beside it, and an object (hence the library) built with OTHER flags is stale — a probe build

@@ -4,13 +4,18 @@ A `Guarded` buffer is one flat uint8 allocation [front red zone | payload | back
 kernel writes outside the tensor it was given lands in one of them and is found by a byte compare (`intact()`), and whatever it reads
 outside the tensor is 0xFF..FF: NaN as fp32 / bf16 / fp64, -1 as an integer, so a stray operand cannot stay invisible behind a zero
 weight or mask.  `exact_workspaces` hands the op wrappers scratch buffers of exactly the size the library's *_workspace_bytes function
-advertised (the pool of ops.workspace never gives less than 1 MiB), each inside guard bands; `called` records which lg_* entry points
-a piece of code fetched from the library.
+advertised (the pool of ops.workspace never gives less than 1 MiB), each inside guard bands; `called` records which entry points of
+the C ABI (`ABI_NAME`) a piece of code fetched from the library.
 
 Nothing here depends on the device: tests/test_guards_cpu.py runs the helper on CPU tensors."""
 import math
+import re
 
 import torch
+
+# What a name of the C ABI looks like, for every check that has to tell one from anything else (tests/test_abi.py, the recorder below):
+# `lg`, an optional lower-case letter, `_`.  The letter groups names for the reader; no check keys off it.
+ABI_NAME = r"lg[a-z]?_\w+"
 
 ZONE_MIN = 64 << 10   # bytes: a red zone is max(payload, 64 KiB), so an overrun by a whole payload (one more tile, row block, sample) stays inside
 ALIGN = 256           # the payload keeps the alignment of a plain torch device allocation (lg_conv_wgrad_m16 routes on dw & 15)
@@ -109,13 +114,13 @@ class _Recorder:
         object.__setattr__(self, "_names", names)
 
     def __getattr__(self, name):
-        if name.startswith("lg_"):
+        if re.fullmatch(ABI_NAME, name):
             self._names.append(name)
         return getattr(self._handle, name)
 
 
 def called(monkeypatch, ops):
-    """Wraps ops._lib.load so that the handle it returns records every lg_* attribute fetched -> the list of names, in order."""
+    """Wraps ops._lib.load so that the handle it returns records every ABI name fetched -> the list of names, in order."""
     names = []
     real = ops._lib.load
     monkeypatch.setattr(ops._lib, "load", lambda *a, **k: _Recorder(real(*a, **k), names))

@@ -1,26 +1,32 @@
-"""CPU-side checks of the drop-in boundary: the C-ABI library builds/loads here (no GPU needed) and
-exports every symbol include/littlegan_hip.h declares, with the parameter lists the ctypes table uses."""
+"""CPU-side checks of the drop-in boundary: the C-ABI library builds/loads here (no GPU needed) and exports every symbol the
+headers include/littlegan_hip*.h declare, with the parameter lists the one ctypes table (_lib.SIGNATURES) uses."""
 import ctypes as C
 import glob
 import os
 import re
 import shutil
 import subprocess
+import sys
 
 import pytest
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from guards import ABI_NAME  # noqa: E402
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "littlegan_hip.h")
+HEADERS = sorted(glob.glob(os.path.join(ROOT, "include", "littlegan_hip*.h")))
 
 
-def _protos():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+def _protos(header=None):
+    """name -> (return type, [parameter declarations]) of the prototypes of one header, or of the whole ABI: every
+    include/littlegan_hip*.h, where no name may be declared twice (in one header or in two)"""
     out = {}
-    for m in re.finditer(r"(?:^|\n)\s*(const char\*|int|size_t)\s+(lg_\w+)\s*\((.*?)\)\s*;", src, flags=re.S):
-        ret, name, args = m.group(1), m.group(2), " ".join(m.group(3).split())
-        plist = [] if args in ("", "void") else [a.strip() for a in args.split(",")]
-        out[name] = (ret, plist)
+    for path in HEADERS if header is None else [header]:
+        src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+        for m in re.finditer(r"(?:^|\n)\s*(const char\*|int|size_t)\s+(" + ABI_NAME + r")\s*\((.*?)\)\s*;", src, flags=re.S):
+            ret, name, args = m.group(1), m.group(2), " ".join(m.group(3).split())
+            assert name not in out, f"{name} is declared twice (the second time in {os.path.basename(path)})"
+            out[name] = (ret, [] if args in ("", "void") else [a.strip() for a in args.split(",")])
     return out
 
 
@@ -54,6 +60,12 @@ def test_header_declares_the_hot_path_entry_points():
         assert n in names
 
 
+def test_no_name_is_declared_in_two_headers():
+    per_header = [_protos(h) for h in HEADERS]
+    assert len(HEADERS) >= 4 and all(per_header)
+    assert len(_protos()) == sum(len(p) for p in per_header)      # (_protos() itself asserts on a second declaration, and names it)
+
+
 def test_library_loads_and_exports_every_declared_symbol(lib):
     handle = lib.load()
     protos = _protos()
@@ -65,7 +77,9 @@ def test_library_loads_and_exports_every_declared_symbol(lib):
         for a, decl in zip(args, plist):
             assert a is _ctype(decl), f"{name}: param '{decl}' bound as {a}"
         exp_ret = {"int": C.c_int, "size_t": C.c_size_t, "const char*": C.c_char_p}[ret]
-        assert res is exp_ret
+        assert res is exp_ret, f"{name}: returns {ret}, bound as {res}"
+        fn = getattr(handle, name)
+        assert fn.argtypes == args and fn.restype is res, f"{name}: load() did not bind it"
     assert handle.lg_abi_version() == 1
 
 
@@ -122,15 +136,15 @@ def test_kernel_files_declare_nothing_themselves():
 
 
 def test_exported_symbols_are_the_declared_ones(lib):
-    """The lg_* symbols the library defines are exactly the names declared in the public header, lg_internal.h and lg_common.h:
-    nothing is exported that no header declares, and no declaration is left without its definition."""
+    """The symbols with an ABI name that the library defines are exactly the names declared in the public headers, lg_internal.h and
+    lg_common.h: nothing is exported that no header declares, and no declaration is left without its definition."""
     nm = os.path.join("/opt/rocm/lib/llvm/bin", "llvm-nm")
     nm = nm if os.path.exists(nm) else (shutil.which("llvm-nm") or shutil.which("nm"))
     if not nm:
         pytest.skip("nm not found")
     out = subprocess.run([nm, "-D", "--defined-only", os.path.join(ROOT, "littlegan_amd", "liblittlegan_hip.so")],
                          stdout=subprocess.PIPE, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if line.split() and line.split()[-1].startswith("lg_")}
+    exported = {line.split()[-1] for line in out.splitlines() if line.split() and re.fullmatch(ABI_NAME, line.split()[-1])}
     internal = _declared(os.path.join(CSRC, "lg_internal.h")) | _declared(os.path.join(CSRC, "lg_common.h"))
     public = set(_protos())
     assert len(internal) >= 40 and not internal & public, internal & public

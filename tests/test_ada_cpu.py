@@ -1,6 +1,6 @@
 """Adaptive augmentation probability (ADA) without a GPU: the restatement of the gate and of the controller (the oracle
-of tests/test_ada_gpu.py), the C ABI of the extension header include/littlegan_hip_ext.h (declared, exported, bound, validating before
-any launch), the ledger of that header's memory-contract rows, and the configuration / trainer behaviour.
+of tests/test_ada_gpu.py), the entry points of include/littlegan_hip_ext.h (the names; validating before any launch: the whole ABI is
+held to its table and its ledger by tests/test_abi.py and tests/test_guards_cpu.py), and the configuration / trainer behaviour.
 
 The gate: row r of call slot q under {seed, key_offset} has the first counter ctr = key_offset + (((q << 24) + r) << 1); its record reads
 the Philox blocks {lo(ctr), hi(ctr), 0, 0} and {lo(ctr + 1), hi(ctr + 1), 0, 0} (tests/test_diffaug_cpu.py), its gates the block
@@ -12,7 +12,6 @@ The controller: state = {fp32 p, int32 sum, int32 rows, int32 steps}.
               p = min(max(p + float32(dir) * (float32(rows) * per_row), 0), 1); sum = rows = steps = 0      (each operation rounded to fp32)"""
 import ctypes as C
 import os
-import re
 import sys
 
 import numpy as np
@@ -20,7 +19,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from oracle import input_oracle as IO  # noqa: E402
-from test_abi import ROOT, _ctype  # noqa: E402
+from test_abi import ROOT, _protos  # noqa: E402
 from test_diffaug_cpu import BITS, IDENTITY, M64, _cpu_trainer, draw_params, key_of, policy_bits  # noqa: E402
 
 EXT_HEADER = os.path.join(ROOT, "include", "littlegan_hip_ext.h")
@@ -154,17 +153,7 @@ def test_controller_restatement():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the ABI of the extension header
-def _ext_protos():
-    """test_abi._protos on include/littlegan_hip_ext.h with the lgx_ prefix"""
-    src = re.sub(r"/\*.*?\*/", "", open(EXT_HEADER).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"(?:^|\n)\s*(const char\*|int|size_t)\s+(lgx_\w+)\s*\((.*?)\)\s*;", src, flags=re.S):
-        ret, name, args = m.group(1), m.group(2), " ".join(m.group(3).split())
-        out[name] = (ret, [] if args in ("", "void") else [a.strip() for a in args.split(",")])
-    return out
-
-
+# the entry points of the extension header
 @pytest.fixture(scope="module")
 def lib():
     from littlegan_amd.csrc.build import build
@@ -173,21 +162,8 @@ def lib():
     return _lib
 
 
-def test_extension_header_declares_exports_and_binds_the_entry_points(lib):
-    protos = _ext_protos()
-    assert set(protos) == set(ENTRY_POINTS) == set(lib.EXT_SIGNATURES), (sorted(protos), sorted(lib.EXT_SIGNATURES))
-    h = lib.load()
-    for name, (ret, plist) in protos.items():
-        assert hasattr(h, name), f"{name} not exported"
-        res, args = lib.EXT_SIGNATURES[name]
-        assert len(args) == len(plist), f"{name}: ctypes table has {len(args)} params, header {len(plist)}"
-        for a, decl in zip(args, plist):
-            assert a is _ctype(decl), (name, decl)
-        assert res is C.c_int and ret == "int"
-        assert getattr(h, name).argtypes == args and getattr(h, name).restype is res     # bound by load()
-    assert not re.search(r"\blgx_", open(os.path.join(ROOT, "include", "littlegan_hip.h")).read())
-    assert not set(lib.SIGNATURES) & set(lib.EXT_SIGNATURES) and not any(n.startswith("lgx_") for n in lib.SIGNATURES)
-    assert h.lg_abi_version() == 1
+def test_extension_header_declares_the_entry_points(lib):
+    assert set(_protos(EXT_HEADER)) == set(ENTRY_POINTS) == {n for n in lib.SIGNATURES if n.startswith("lgx_")}
 
 
 def test_argument_validation_without_gpu(lib):
@@ -237,20 +213,6 @@ def test_argument_validation_without_gpu(lib):
     assert adj(d, 4, 0.6, -1e-3, None) == -1 and b"per_row" in err()
     assert adj(d, 4, 0.6, float("inf"), None) == -1 and b"per_row" in err()
     assert adj(d, 4, 0.6, float("nan"), None) == -1 and b"per_row" in err() and b"lgx_ada_adjust" in err()
-
-
-def test_every_pointer_taking_extension_has_a_contract_row():
-    """The ledger of include/littlegan_hip_ext.h, as tests/test_guards_cpu.py keeps the main header's: every pointer-taking lgx_*
-    function is named in `covers` by a row of tests/test_ada_gpu.py's contract cases.  No exemptions."""
-    import test_ada_gpu as AG
-    protos = _ext_protos()
-    want = {name for name, (ret, plist) in protos.items() if any("*" in p for p in plist)}
-    assert want == set(ENTRY_POINTS)
-    covered = {n for r in AG.CONTRACT_CASES for n in r.covers}
-    assert not covered - set(protos), f"rows name functions the header does not declare: {sorted(covered - set(protos))}"
-    assert not want - covered, f"extension entry points without a contract row in tests/test_ada_gpu.py: {sorted(want - covered)}"
-    ids = [r.id for r in AG.CONTRACT_CASES]
-    assert len(ids) == len(set(ids)) and all(r.covers and callable(r.run) and callable(r.check) for r in AG.CONTRACT_CASES)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -5,9 +5,9 @@ ranges, p at both ends of the threshold); lgx_ada_accumulate (integers: exact) b
 lgx_ada_adjust bit for bit from hand-built states.  Whole steps at the geometry and with the references of tests/test_diffaug_gpu.py: a
 fixed p = 0.5 against the float64 oracles under the gated records at that module's tolerances; the controller's trajectory eager against
 graph replay and against the restated controller fed with the float64 oracle's signs, in both directions and into both clamps; a fixed p
-leaves the counters alone; checkpoint resume; p = 1 without a target is the plain diff_augment step bit for bit; the memory contract of
-the four entry points with the row harness of tests/test_memory_contract_gpu.py; the data-parallel all-reduce of the counters at world
-size 1."""
+leaves the counters alone; checkpoint resume; p = 1 without a target is the plain diff_augment step bit for bit; the data-parallel
+all-reduce of the counters at world size 1.  (The memory contract of the four entry points: the ada-* rows of
+tests/test_memory_contract_gpu.py, on this module's data.)"""
 import os
 import sys
 
@@ -19,8 +19,7 @@ import torch.multiprocessing as mp
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))   # the spawned child imports this module by name too
 from oracle import np_oracle as O  # noqa: E402
 from oracle import torch_oracle as TO  # noqa: E402
-import test_memory_contract_gpu as MC  # noqa: E402
-from test_ada_cpu import (ENTRY_POINTS, F32, P_HI, P_LO, ada_accumulate_np, ada_adjust_np, draw_params_gated)  # noqa: E402
+from test_ada_cpu import (F32, P_HI, P_LO, ada_accumulate_np, ada_adjust_np, draw_params_gated)  # noqa: E402
 from test_diffaug_cpu import BITS, IDENTITY, draw_params, key_of  # noqa: E402
 from test_diffaug_gpu import FULL, SMALL, AugNet, _same_state, aug_np_oracle, build_aug, dev_key, step_reference  # noqa: E402
 from test_dp_gpu import CFG as DP_CFG, _free_port, _inputs, _join_all  # noqa: E402
@@ -373,101 +372,6 @@ def test_p_one_without_a_target_is_the_plain_step(ops):
         assert all((u is None) == (v is None) and (u is None or torch.equal(u, v)) for u, v in zip(ra, rb)), b
         assert _same_state(tr_a, tr_b), b
     assert "ada_state" not in tr_a.checkpoint_state()
-
-
-# ---------------------------------------------------------------------------------------------------------------------- memory contract
-CONTRACT_CASES = []
-
-
-def contract_row(*a, **k):
-    CONTRACT_CASES.append(MC.Row(*a, **k))
-
-
-def _draw_row(rows, S):
-    seed, koff = 0x7654321, (9 << 40) + 3
-
-    def run(ops, alloc):
-        key = alloc.inp("key", torch.tensor([seed, koff], dtype=torch.int64))
-        state = alloc.inp("state", torch.from_numpy(words(0.5, 7, 9, 1))).view(torch.float32)
-        return dict(drawn=ops.diffaug_draw_gated(key, 1, 2, rows, S, FULL, state, out=alloc.out("params", (rows, 8))))
-
-    def check(res):
-        assert np.array_equal(u32(res["drawn"].cpu().numpy()), u32(draw_params_gated(seed, koff, 1, 2, rows, S, FULL, 0.5)))
-
-    contract_row(f"ada-draw-{rows}x{S}", ("lgx_diffaug_draw_gated",), run, check)
-
-
-def _accumulate_row(B, ld):
-    st = (0.375, -3, 11, 1)
-
-    def run(ops, alloc):
-        state = alloc.state("state", torch.from_numpy(words(*st)))
-        ops.ada_accumulate(state.view(torch.float32), alloc.inp("heads", heads_mix(B, ld, 3)), B)
-        return dict(state=state)
-
-    def check(res):
-        want = ada_accumulate_np((F32(st[0]),) + st[1:], heads_mix(B, ld, 3), B)
-        assert res["state"].cpu().numpy().tolist() == words(*want).tolist()
-
-    contract_row(f"ada-accumulate-{B}x{ld}", ("lgx_ada_accumulate",), run, check)
-
-
-def _adjust_row(tag, st):
-    def run(ops, alloc):
-        state = alloc.state("state", torch.from_numpy(words(*st)))
-        ops.ada_adjust(state.view(torch.float32), 2, 0.6, PER_ROW)
-        return dict(state=state)
-
-    def check(res):
-        want = ada_adjust_np((F32(st[0]),) + st[1:], 2, 0.6, PER_ROW)
-        assert res["state"].cpu().numpy().tolist() == words(*want).tolist()
-        assert (want[1:] == (0, 0, 0)) == (tag == "due")
-
-    contract_row(f"ada-adjust-{tag}", ("lgx_ada_adjust",), run, check)
-
-
-def _init_row():
-    def run(ops, alloc):
-        return dict(state=ops.ada_init(0.625, out=alloc.out("state", (4,))).view(torch.int32))
-
-    def check(res):
-        assert res["state"].cpu().numpy().tolist() == words(0.625).tolist()
-
-    contract_row("ada-init", ("lgx_ada_init",), run, check)
-
-
-_draw_row(3, 8)
-_accumulate_row(65, 6)
-_adjust_row("due", (0.5, 5, 6, 2))
-_adjust_row("not-due", (0.5, 5, 6, 1))
-_init_row()
-assert {n for r in CONTRACT_CASES for n in r.covers} == set(ENTRY_POINTS)
-
-
-class _Fetched:
-    """records the lgx_* entry points fetched from the library handle (tests/guards.py's recorder keeps the lg_* ones)"""
-
-    def __init__(self, handle, names):
-        object.__setattr__(self, "_handle", handle)
-        object.__setattr__(self, "_names", names)
-
-    def __getattr__(self, name):
-        if name.startswith("lgx_"):
-            self._names.append(name)
-        return getattr(self._handle, name)
-
-
-@pytest.mark.parametrize("case", CONTRACT_CASES, ids=lambda r: r.id)
-def test_memory_contract_of_the_extensions(case, ops, monkeypatch):
-    """The body of tests/test_memory_contract_gpu.py::test_memory_contract on this module's rows: plain twice, then red zones and
-    outputs filled with 0xFF, 0x00 and 0x3F.  That body counts lg_* fetches, so the row goes in without its lgx_* names and they are
-    counted here."""
-    fetched = []
-    real = ops._lib.load
-    monkeypatch.setattr(ops._lib, "load", lambda *a, **k: _Fetched(real(*a, **k), fetched))
-    MC.test_memory_contract(MC.Row(case.id, (), case.run, case.check), ops, monkeypatch)
-    missing = set(case.covers) - set(fetched)
-    assert not missing, f"the row claims entry points it never fetched: {sorted(missing)} (fetched {sorted(set(fetched))})"
 
 
 # ---------------------------------------------------------------------------------------------------------------------- data parallel

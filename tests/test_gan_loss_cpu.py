@@ -1,5 +1,6 @@
-"""Logit-side GAN objectives (gan_loss) without a GPU: the C ABI of include/littlegan_hip_obj.h (declared, exported, bound,
-validating before any launch); the configuration key and the trainer's refusals; the float64 step reference of tests/test_gan_loss_gpu.py
+"""Logit-side GAN objectives (gan_loss) without a GPU: the entry points of include/littlegan_hip_obj.h (the names, the kind
+numbers, validating before any launch: the whole ABI is held to its table and its ledger by tests/test_abi.py and
+tests/test_guards_cpu.py); the configuration key and the trainer's refusals; the float64 step reference of tests/test_gan_loss_gpu.py
 (oracle.np_oracle.step_gradients plus the autograd gradient of "new real / fake terms minus the BCE ones", per tape) anchored against a
 direct torch restatement of the whole step under each objective; the logit-side gradient penalty by torch double backward; and the data
 of the exact-arithmetic kernel cases with the conditions under which "bit for bit" is a fair demand.
@@ -24,10 +25,10 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from oracle import np_oracle as O  # noqa: E402
 from oracle import torch_oracle as TO  # noqa: E402
-from test_abi import ROOT, _ctype, _protos  # noqa: E402
+from test_abi import ROOT, _protos  # noqa: E402
 from test_diffaug_cpu import _cpu_trainer, diffaug_torch  # noqa: E402
 from test_gp_cpu import TINY, _tiny_case  # noqa: E402
-from test_r1_cpu import ZERO_GRADS, _exported  # noqa: E402
+from test_r1_cpu import ZERO_GRADS  # noqa: E402
 
 OBJ_HEADER = os.path.join(ROOT, "include", "littlegan_hip_obj.h")
 ENTRY_POINTS = ("lgo_heads_fwd", "lgo_gan_heads_loss_fwd_bwd")
@@ -225,16 +226,7 @@ def test_logit_penalty_by_double_backward():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the ABI of include/littlegan_hip_obj.h
-def _obj_protos():
-    src = re.sub(r"/\*.*?\*/", "", open(OBJ_HEADER).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"(?:^|\n)\s*(const char\*|int|size_t)\s+(lgo_\w+)\s*\((.*?)\)\s*;", src, flags=re.S):
-        ret, name, args = m.group(1), m.group(2), " ".join(m.group(3).split())
-        out[name] = (ret, [] if args in ("", "void") else [a.strip() for a in args.split(",")])
-    return out
-
-
+# the entry points of include/littlegan_hip_obj.h
 @pytest.fixture(scope="module")
 def lib():
     from littlegan_amd.csrc.build import build
@@ -243,40 +235,14 @@ def lib():
     return _lib
 
 
-def test_obj_header_declares_exports_and_binds_the_entry_points(lib):
-    protos = _obj_protos()
-    assert set(protos) == set(ENTRY_POINTS) == set(lib.OBJ_SIGNATURES), (sorted(protos), sorted(lib.OBJ_SIGNATURES))
-    h = lib.load()
-    for name, (ret, plist) in protos.items():
-        assert hasattr(h, name), f"{name} not exported"
-        res, args = lib.OBJ_SIGNATURES[name]
-        assert len(args) == len(plist), f"{name}: ctypes table has {len(args)} params, header {len(plist)}"
-        for a, decl in zip(args, plist):
-            assert a is _ctype(decl), (name, decl)
-        assert res is C.c_int and ret == "int"
-        assert getattr(h, name).argtypes == args and getattr(h, name).restype is res     # bound by load()
-    exported = _exported(lib, "lgo_")
-    assert exported is None or exported == set(ENTRY_POINTS), exported
-    for other in ("littlegan_hip.h", "littlegan_hip_ext.h", "littlegan_hip_reg.h"):
-        assert not re.search(r"\blgo_", open(os.path.join(ROOT, "include", other)).read()), other
-    assert not any(n.startswith("lgo_") for n in list(lib.SIGNATURES) + list(lib.EXT_SIGNATURES) + list(lib.REG_SIGNATURES))
-    assert not any(n.startswith("lgo_") for n in _protos())
-    assert all(n.startswith("lgo_") for n in lib.OBJ_SIGNATURES)
-    assert h.lg_abi_version() == 1
+def test_obj_header_declares_the_entry_points_and_the_kinds(lib):
+    assert set(_protos(OBJ_HEADER)) == set(ENTRY_POINTS) == {n for n in lib.SIGNATURES if n.startswith("lgo_")}
     # the two kind tables agree: config's names are the header's numbers
     from littlegan_amd import config
     assert config.GAN_LOSS_KINDS == dict(KIND_NO, bce=0)
     hdr = open(OBJ_HEADER).read()
     for name, no in KIND_NO.items():
         assert re.search(rf"#define LGO_KIND_{name.upper()} {no}\b", hdr), name
-
-
-def test_every_pointer_taking_obj_function_has_a_contract_row():
-    import test_gan_loss_gpu as GG
-    covered = {n for r in GG.CONTRACT_CASES for n in r.covers}
-    assert covered == set(ENTRY_POINTS), covered ^ set(ENTRY_POINTS)
-    ids = [r.id for r in GG.CONTRACT_CASES]
-    assert len(ids) == len(set(ids)) and all(callable(r.run) and callable(r.check) for r in GG.CONTRACT_CASES)
 
 
 def test_argument_validation_without_gpu(lib):

@@ -2,8 +2,8 @@
 
 Kernels: the loss kernel bit for bit in exact arithmetic (hinge, lsgan, wgan in each role; tests/test_gan_loss_cpu.py::
 test_conditions_of_the_exact_cases), its attribute part bit for bit against ops.bce_heads_loss, every kind on random data against fp64 at
-the bounds of tests/test_tail_ops_gpu.py::test_bce_heads_loss_sizes; the heads forward that keeps the logit on both GEMM routes; the
-memory contract of both entry points with tests/guards.py.
+the bounds of tests/test_tail_ops_gpu.py::test_bce_heads_loss_sizes; the heads forward that keeps the logit on both GEMM routes.  (The
+memory contract of both entry points: the heads-fwd-logit-* and gan-loss-* rows of tests/test_memory_contract_gpu.py, on this module's data.)
 Steps: whole steps against np_oracle.step_gradients + the autograd gradient of the objectives' difference (tests/test_gan_loss_cpu.py::
 step_reference) at the whole-step tolerances of tests/test_step_gpu.py, the Wasserstein objective with the penalty on the logit, the
 neighbours (r1_gamma, diff_augment at p = 0.5), the defaults, bit-determinism, graph replay, two gloo ranks and the CLI."""
@@ -20,7 +20,7 @@ import torch.multiprocessing as mp
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))  # the spawned ranks import this module by name too
 from oracle import np_oracle as O  # noqa: E402
-import test_memory_contract_gpu as MC  # noqa: E402
+from guards import called  # noqa: E402
 from test_gan_loss_cpu import (ENTRY_POINTS, EXACT_KINDS, EXACT_LOSS0, EXACT_SHAPES, EXACT_W_PR, KIND_NO, KINDS, ROLE_D_FAKE, ROLE_D_REAL,  # noqa: E402
                                ROLE_G, exact_case, np_term, objective_delta, step_reference, torch_gp_logit, with_objective)
 from test_r1_cpu import ZERO_GRADS, np_r1  # noqa: E402
@@ -66,26 +66,6 @@ def rel(got, exp):
     """the measure of tests/test_tail_ops_gpu.py: max-abs error relative to the max-abs of the fp64 result"""
     got = f64(got) if torch.is_tensor(got) else np.asarray(got)
     return float(np.abs(got - exp).max() / (np.abs(exp).max() + 1e-30))
-
-
-class _Fetched:
-    """records the lgo_* entry points fetched from the library handle (tests/test_r1_gpu.py's recorder keeps the lgr_* ones)"""
-
-    def __init__(self, handle, names):
-        object.__setattr__(self, "_handle", handle)
-        object.__setattr__(self, "_names", names)
-
-    def __getattr__(self, name):
-        if name.startswith("lgo_"):
-            self._names.append(name)
-        return getattr(self._handle, name)
-
-
-def fetched_lgo(monkeypatch, ops):
-    names = []
-    real = ops._lib.load
-    monkeypatch.setattr(ops._lib, "load", lambda *a, **k: _Fetched(real(*a, **k), names))
-    return names
 
 
 def _heads_data(B, c, seed):
@@ -249,65 +229,6 @@ def test_heads_fwd_logit(ops, case, mode):
         assert rel(z, z_e) < 1e-5
     # z is exactly the value whose sigmoid went into column 0
     assert rel(p[:, 0], O.sigmoid(f64(z))) < 1e-6
-
-
-# ---------------------------------------------------------------------------------------------------------------- memory contract
-CONTRACT_CASES = []
-
-
-def _heads_row(case):
-    B, K, c, route = case
-
-    def run(ops, alloc):
-        x, wpr, bpr, wc, bc = _heads_operands(case, "int")
-        ins = [alloc.inp(n, a.astype(F32)) for n, a in (("x", x), ("wpr", wpr), ("bpr", bpr), ("wc", wc), ("bc", bc))]
-        p, z = ops.heads_fwd_logit(*ins, out=alloc.out("p", (B, 1 + c)), z_out=alloc.out("z_pr", (B,)))   # the workspace comes exactly sized
-        return dict(p=p, z_pr=z)
-
-    def check(res):
-        x, wpr, bpr, wc, bc = _heads_operands(case, "int")
-        assert np.array_equal(_bits(res["z_pr"]), _np_bits((x @ wpr + bpr)[:, 0]))
-        assert rel(res["p"], np.concatenate([O.sigmoid(x @ wpr + bpr), O.sigmoid(x @ wc + bc)], 1)) < 1e-5
-
-    CONTRACT_CASES.append(MC.Row(f"heads-fwd-logit-{B}x{K}x{c}", ("lgo_heads_fwd",), run, check, route=HEADS_FWD[route]))
-
-
-def _loss_row(kind, role, B, c):
-    def run(ops, alloc):
-        p, t_c = _heads_data(B, c, 23 * B + c)
-        z = exact_case(kind, role, B)[0]
-        loss, dz = alloc.state("loss", np.array([EXACT_LOSS0], F32)), alloc.out("dz", (B, 1 + c))
-        ops.gan_heads_loss(alloc.inp("p", p.astype(F32)), alloc.inp("z_pr", z), alloc.inp("t_c", t_c.astype(F32)), KIND_NO[kind], role,
-                           EXACT_W_PR, 1.0, loss, dz, True)
-        return dict(loss=loss, dz=dz)
-
-    def check(res):
-        p, t_c = _heads_data(B, c, 23 * B + c)
-        _, dz_w, term_w, _ = exact_case(kind, role, B)
-        assert np.array_equal(_bits(res["dz"][:, 0]), _np_bits(dz_w))
-        exp = EXACT_LOSS0 + float(term_w) + O.bce_mean(t_c, p[:, 1:])
-        assert abs(float(res["loss"]) - exp) < 2e-6 * abs(exp) + 1e-6
-        assert rel(res["dz"][:, 1:], O.bce_mean_bwd(t_c, p[:, 1:]) * p[:, 1:] * (1 - p[:, 1:])) < 1e-5
-
-    CONTRACT_CASES.append(MC.Row(f"gan-loss-{kind}-{role}-{B}x{c}", ("lgo_gan_heads_loss_fwd_bwd",), run, check, route="gan_heads_kernel"))
-
-
-_heads_row(HEADS_CASES[4])
-_heads_row(HEADS_CASES[0])
-_loss_row("hinge", ROLE_D_REAL, 1, 1)
-_loss_row("lsgan", ROLE_D_FAKE, 4, 3)
-_loss_row("wgan", ROLE_G, 1024, 40)
-
-
-@pytest.mark.parametrize("case", CONTRACT_CASES, ids=lambda r: r.id)
-def test_memory_contract_of_the_objectives(case, ops, monkeypatch):
-    """The body of tests/test_memory_contract_gpu.py::test_memory_contract on this module's rows (plain twice, then red zones, outputs
-    and exactly-sized workspaces filled with 0xFF, 0x00 and 0x3F).  That body counts lg_* fetches, so the row goes in without its
-    lgo_* names and they are counted here."""
-    fetched = fetched_lgo(monkeypatch, ops)
-    MC.test_memory_contract(MC.Row(case.id, (), case.run, case.check, route=case.route), ops, monkeypatch)
-    missing = set(case.covers) - set(fetched)
-    assert not missing and set(case.covers) <= set(ENTRY_POINTS), (sorted(missing), sorted(set(fetched)))
 
 
 # ---------------------------------------------------------------------------------------------------------------- whole steps
@@ -488,20 +409,21 @@ def test_defaults_fetch_nothing_and_agree(ops, monkeypatch):
     W = perturbed(cfg, 2)
     absent, bce, hinge = _build(cfg, W, "f32", None), _build(cfg, W, "f32", "bce"), _build(cfg, W, "f32", "hinge")
     assert not hasattr(absent.args, "gan_loss") and absent.gan_kind == 0 and bce.gan_kind == 0 and hinge.gan_kind == 2
-    names = fetched_lgo(monkeypatch, ops)
+    fetched = called(monkeypatch, ops)
+    names = lambda: [n for n in fetched if n.startswith("lgo_")]   # noqa: E731
     for b in (1, 5, 11):
         inp = dev_inputs(_step_inputs(cfg, b))
         inp.pop("gp_eps")
         absent.train_step_from_inputs(b, inp)
         bce.train_step_from_inputs(b, inp)
     torch.cuda.synchronize()
-    assert names == []
+    assert fetched and names() == []
     assert torch.equal(absent.store.flat, bce.store.flat) and torch.equal(absent.store.grad, bce.store.grad)
     inp = dev_inputs(_step_inputs(cfg, 11))
     inp.pop("gp_eps")
     hinge.train_step_from_inputs(11, inp)
     torch.cuda.synchronize()
-    assert set(names) == set(ENTRY_POINTS) and names.count("lgo_gan_heads_loss_fwd_bwd") == 4 and names.count("lgo_heads_fwd") == 2
+    assert set(names()) == set(ENTRY_POINTS) and names().count("lgo_gan_heads_loss_fwd_bwd") == 4 and names().count("lgo_heads_fwd") == 2
     assert not torch.equal(hinge.store.grad, bce.store.grad)
 
 

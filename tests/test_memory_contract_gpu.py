@@ -17,8 +17,8 @@ intact, every input bit-identical to what went in;  5. everything written: no ou
 plain result is finite;  6. oracle: plain against oracle/np_oracle.py (or the op's bit-exact restatement) at the tolerances the op
 has in its own test module — imported from there, none is introduced here.
 
-Each row names the lg_* entry points it covers; tests/test_guards_cpu.py checks that every pointer-taking function of the public
-header is named by a row or listed in EXEMPT with its reason, so a new entry point fails there until it gets a row."""
+Each row names the entry points it covers; tests/test_guards_cpu.py checks that every pointer-taking function of the C ABI (every
+include/littlegan_hip*.h) is named by a row or listed in EXEMPT with its reason, so a new entry point fails there until it gets a row."""
 import ctypes
 import functools
 import os
@@ -44,6 +44,13 @@ from test_ema_cpu import ema_update  # noqa: E402
 from test_ema_gpu import ADAM, BOUND, DECAY  # noqa: E402
 from test_metrics_cpu import CASES as PAIR_CASES, MARGIN, ball_margin, dot_eps, make_sets, oracle_d2, oracle_poly  # noqa: E402
 from test_fid_stream import check_stats, eigh_reference, fixture  # noqa: E402
+from test_r1_cpu import EXACT_LOSS0 as R1_LOSS0, EXACT_WEIGHT, exact_colsum_case, exact_seed_case, heads_seed_wpr  # noqa: E402
+from test_r1_gpu import _bits as i32, _np_bits as np_i32  # noqa: E402
+from test_ada_cpu import ada_accumulate_np, ada_adjust_np, draw_params_gated  # noqa: E402
+from test_ada_gpu import FULL, PER_ROW, heads_mix, u32, words  # noqa: E402
+from test_gan_loss_cpu import (EXACT_LOSS0 as GAN_LOSS0, EXACT_W_PR, KIND_NO, ROLE_D_FAKE, ROLE_D_REAL, ROLE_G,  # noqa: E402
+                               exact_case)
+from test_gan_loss_gpu import HEADS_CASES as LOGIT_HEADS_CASES, _heads_data, _heads_operands  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -146,9 +153,9 @@ class Trace:
 
 
 class Row:
-    """id; covers: the lg_* entry points the row runs; run(ops, alloc) -> dict of results (tensors, or plain Python values; "_route":
+    """id; covers: the entry points the row runs; run(ops, alloc) -> dict of results (tensors, or plain Python values; "_route":
     the Trace); check(res): the oracle comparison of the plain results; route: substrings the plain route must contain; sizing:
-    [(lg_*_workspace_bytes name, args)] of the workspaces the row uses; wgrad: (B, Hs, Ws, cb, cs, dtype) of a conv weight gradient."""
+    [(*_workspace_bytes name, args)] of the workspaces the row uses; wgrad: (B, Hs, Ws, cb, cs, dtype) of a conv weight gradient."""
 
     def __init__(self, id, covers, run, check=None, route=(), sizing=(), wgrad=None):
         self.id, self.covers, self.run, self.check = id, tuple(covers), run, check
@@ -1747,3 +1754,167 @@ def legacy_row():
 
 
 legacy_row()
+
+
+# ------------------------------------------------------------------------------------------------------------------ adaptive augmentation probability
+def ada_draw_row(rows, S):
+    """the gated draw against its restatement bit for bit: tests/test_ada_gpu.py"""
+    seed, koff = 0x7654321, (9 << 40) + 3
+
+    def run(ops, alloc):
+        key = alloc.inp("key", torch.tensor([seed, koff], dtype=torch.int64))
+        state = alloc.inp("state", torch.from_numpy(words(0.5, 7, 9, 1))).view(torch.float32)
+        return dict(drawn=ops.diffaug_draw_gated(key, 1, 2, rows, S, FULL, state, out=alloc.out("params", (rows, 8))))
+
+    def check(res):
+        assert np.array_equal(u32(res["drawn"].cpu().numpy()), u32(draw_params_gated(seed, koff, 1, 2, rows, S, FULL, 0.5)))
+
+    row(f"ada-draw-{rows}x{S}", ("lgx_diffaug_draw_gated",), run, check)
+
+
+def ada_accumulate_row(B, ld):
+    st = (0.375, -3, 11, 1)
+
+    def run(ops, alloc):
+        state = alloc.state("state", torch.from_numpy(words(*st)))
+        ops.ada_accumulate(state.view(torch.float32), alloc.inp("heads", heads_mix(B, ld, 3)), B)
+        return dict(state=state)
+
+    def check(res):
+        want = ada_accumulate_np((np.float32(st[0]),) + st[1:], heads_mix(B, ld, 3), B)
+        assert res["state"].cpu().numpy().tolist() == words(*want).tolist()
+
+    row(f"ada-accumulate-{B}x{ld}", ("lgx_ada_accumulate",), run, check)
+
+
+def ada_adjust_row(tag, st):
+    def run(ops, alloc):
+        state = alloc.state("state", torch.from_numpy(words(*st)))
+        ops.ada_adjust(state.view(torch.float32), 2, 0.6, PER_ROW)
+        return dict(state=state)
+
+    def check(res):
+        want = ada_adjust_np((np.float32(st[0]),) + st[1:], 2, 0.6, PER_ROW)
+        assert res["state"].cpu().numpy().tolist() == words(*want).tolist()
+        assert (want[1:] == (0, 0, 0)) == (tag == "due")
+
+    row(f"ada-adjust-{tag}", ("lgx_ada_adjust",), run, check)
+
+
+def ada_init_row():
+    def run(ops, alloc):
+        return dict(state=ops.ada_init(0.625, out=alloc.out("state", (4,))).view(torch.int32))
+
+    def check(res):
+        assert res["state"].cpu().numpy().tolist() == words(0.625).tolist()
+
+    row("ada-init", ("lgx_ada_init",), run, check)
+
+
+ada_draw_row(3, 8)
+ada_accumulate_row(65, 6)
+ada_adjust_row("due", (0.5, 5, 6, 2))
+ada_adjust_row("not-due", (0.5, 5, 6, 1))
+ada_init_row()
+
+
+# ------------------------------------------------------------------------------------------------------------------ R1 gradient penalty
+def r1_seed_row(B, L):
+    """the three R1 kernels bit for bit in exact arithmetic: tests/test_r1_gpu.py (data: tests/test_r1_cpu.py)"""
+    def run(ops, alloc):
+        g = alloc.inp("g", exact_seed_case(B, L)[0])
+        loss, r1l = alloc.state("loss", np.array([R1_LOSS0], np.float32)), alloc.out("r1_loss", (1,))
+        u0, r2 = alloc.out("u0", (B, L)), alloc.out("r2", (B,))
+        lib = ops._lib.load()
+        ws = ops.workspace(int(lib.lgr_r1_workspace_bytes(B, L)), g.device, "r1")   # (the wrapper allocates its outputs: guarded ones here)
+        ops._lib.check(lib.lgr_r1_seed(g.data_ptr(), u0.data_ptr(), r2.data_ptr(), loss.data_ptr(), r1l.data_ptr(), EXACT_WEIGHT,
+                                       ws.data_ptr(), ws.numel(), B, L, torch.cuda.current_stream().cuda_stream), "lgr_r1_seed")
+        return dict(u0=u0, r2=r2, loss=loss, r1_loss=r1l)
+
+    def check(res):
+        _, u0, r2, term, loss = exact_seed_case(B, L)
+        assert np.array_equal(i32(res["u0"]), np_i32(u0)) and np.array_equal(i32(res["r2"]), np_i32(r2))
+        assert np.array_equal(i32(res["r1_loss"]), np_i32([term])) and np.array_equal(i32(res["loss"]), np_i32([loss]))
+
+    row(f"r1-seed-{B}x{L}", ("lgr_r1_seed",), run, check, sizing=[("lgr_r1_workspace_bytes", (B, L))])
+
+
+def r1_colsum_row(B, K):
+    def run(ops, alloc):
+        u, d0, _ = exact_colsum_case(B, K)
+        dw = alloc.state("dwpr", d0)
+        ops.r1_heads_colsum(alloc.inp("u", u), dw)
+        return dict(dwpr=dw)
+
+    def check(res):
+        assert np.array_equal(i32(res["dwpr"]), np_i32(exact_colsum_case(B, K)[2]))
+
+    row(f"r1-colsum-{B}x{K}", ("lgr_r1_heads_colsum",), run, check, sizing=[("lgr_r1_colsum_workspace_bytes", (B, K))])
+
+
+def r1_heads_seed_row(B, K):
+    def run(ops, alloc):
+        wpr = alloc.inp("wpr", heads_seed_wpr(K).reshape(K, 1))
+        g = alloc.out("g", (B, K))
+        ops._lib.check(ops._lib.load().lgr_r1_heads_seed(wpr.data_ptr(), g.data_ptr(), B, K, torch.cuda.current_stream().cuda_stream),
+                       "lgr_r1_heads_seed")
+        return dict(g=g.view(torch.int32))   # compared as words: a NaN is equal to itself
+
+    def check(res):
+        assert np.array_equal(res["g"].cpu().numpy(), np.broadcast_to(heads_seed_wpr(K).view(np.int32), (B, K)))
+
+    row(f"r1-heads-seed-{B}x{K}", ("lgr_r1_heads_seed",), run, check)
+
+
+r1_seed_row(1, 4)
+r1_seed_row(4, 4100)
+r1_colsum_row(1, 4)
+r1_colsum_row(33, 5)
+r1_heads_seed_row(1, 1)
+r1_heads_seed_row(3, 8)
+
+
+# ------------------------------------------------------------------------------------------------------------------ logit-side objectives
+def heads_logit_row(case):
+    """the heads forward that keeps the logit, on both GEMM routes, and the loss on it: tests/test_gan_loss_gpu.py"""
+    B, K, c, route = case
+
+    def run(ops, alloc):
+        x, wpr, bpr, wc, bc = _heads_operands(case, "int")
+        ins = [alloc.inp(n, a.astype(np.float32)) for n, a in (("x", x), ("wpr", wpr), ("bpr", bpr), ("wc", wc), ("bc", bc))]
+        p, z = ops.heads_fwd_logit(*ins, out=alloc.out("p", (B, 1 + c)), z_out=alloc.out("z_pr", (B,)))   # the workspace comes exactly sized
+        return dict(p=p, z_pr=z)
+
+    def check(res):
+        x, wpr, bpr, wc, bc = _heads_operands(case, "int")
+        assert np.array_equal(i32(res["z_pr"]), np_i32((x @ wpr + bpr)[:, 0]))
+        assert rel(res["p"], np.concatenate([O.sigmoid(x @ wpr + bpr), O.sigmoid(x @ wc + bc)], 1)) < 1e-5
+
+    row(f"heads-fwd-logit-{B}x{K}x{c}", ("lgo_heads_fwd",), run, check, route=HEADS_FWD[route])
+
+
+def gan_loss_row(kind, role, B, c):
+    def run(ops, alloc):
+        p, t_c = _heads_data(B, c, 23 * B + c)
+        z = exact_case(kind, role, B)[0]
+        loss, dz = alloc.state("loss", np.array([GAN_LOSS0], np.float32)), alloc.out("dz", (B, 1 + c))
+        ops.gan_heads_loss(alloc.inp("p", p.astype(np.float32)), alloc.inp("z_pr", z), alloc.inp("t_c", t_c.astype(np.float32)), KIND_NO[kind], role,
+                           EXACT_W_PR, 1.0, loss, dz, True)
+        return dict(loss=loss, dz=dz)
+
+    def check(res):
+        p, t_c = _heads_data(B, c, 23 * B + c)
+        _, dz_w, term_w, _ = exact_case(kind, role, B)
+        assert np.array_equal(i32(res["dz"][:, 0]), np_i32(dz_w))
+        exp = GAN_LOSS0 + float(term_w) + O.bce_mean(t_c, p[:, 1:])
+        assert abs(float(res["loss"]) - exp) < 2e-6 * abs(exp) + 1e-6
+        assert rel(res["dz"][:, 1:], O.bce_mean_bwd(t_c, p[:, 1:]) * p[:, 1:] * (1 - p[:, 1:])) < 1e-5
+
+    row(f"gan-loss-{kind}-{role}-{B}x{c}", ("lgo_gan_heads_loss_fwd_bwd",), run, check, route="gan_heads_kernel")
+
+
+heads_logit_row(LOGIT_HEADS_CASES[4])
+heads_logit_row(LOGIT_HEADS_CASES[0])
+gan_loss_row("hinge", ROLE_D_REAL, 1, 1)
+gan_loss_row("lsgan", ROLE_D_FAKE, 4, 3)
+gan_loss_row("wgan", ROLE_G, 1024, 40)

@@ -2,7 +2,8 @@
 
 Kernels: the three lgr_* entry points bit for bit in exact arithmetic (integers in [-4, 4] times a power of two, weight and B powers of
 two: tests/test_r1_cpu.py::test_conditions_of_the_exact_cases) at every chunk / slab edge, as launched, repeated and under a one-CU
-budget; on random fp32 data against fp64 (the bounds of tests/test_gp_gpu.py); their memory contract with tests/guards.py.
+budget; on random fp32 data against fp64 (the bounds of tests/test_gp_gpu.py).  (Their memory contract: the r1-* rows of
+tests/test_memory_contract_gpu.py, on this module's data.)
 Penalty: its value and D weight gradients alone against the torch float64 double-backward oracle (tests/test_r1_cpu.py::torch_r1),
 then whole steps against np_oracle.step_gradients + np_r1 (full step, each partition group, the Adjuster branch, under diff_augment
 and a fixed augmentation probability), the lazy interval, bit-determinism, graph replay, the defaults, two gloo ranks and the CLI.
@@ -20,7 +21,7 @@ import torch.multiprocessing as mp
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))  # the spawned ranks import this module by name too
 from oracle import np_oracle as O  # noqa: E402
-import test_memory_contract_gpu as MC  # noqa: E402
+from guards import called  # noqa: E402
 from test_r1_cpu import (COLSUM_SHAPES, EXACT_LOSS0, EXACT_WEIGHT, HEADS_SEED_SHAPES, SEED_SHAPES, ZERO_GRADS, exact_colsum_case,  # noqa: E402
                          exact_seed_case, heads_seed_wpr, np_r1, torch_r1)
 from test_step_gpu import TOLS, check_grads, dev_inputs, f32_round, grads_of, load_weights, make_args, perturbed  # noqa: E402
@@ -67,26 +68,6 @@ class one_cu:
 
     def __exit__(self, *exc):
         assert self.lib.lg_set_reserved_cus(self.was) == 0
-
-
-class _Fetched:
-    """records the lgr_* entry points fetched from the library handle (tests/guards.py's recorder keeps the lg_* ones)"""
-
-    def __init__(self, handle, names):
-        object.__setattr__(self, "_handle", handle)
-        object.__setattr__(self, "_names", names)
-
-    def __getattr__(self, name):
-        if name.startswith("lgr_"):
-            self._names.append(name)
-        return getattr(self._handle, name)
-
-
-def fetched_lgr(monkeypatch, ops):
-    names = []
-    real = ops._lib.load
-    monkeypatch.setattr(ops._lib, "load", lambda *a, **k: _Fetched(real(*a, **k), names))
-    return names
 
 
 # ---------------------------------------------------------------------------------------------------------------- kernels, exact
@@ -199,79 +180,6 @@ def test_wrappers_refuse_wrong_shapes(ops):
         ops.r1_seed(torch.zeros(2, 6, device="cuda"), 1.0)            # L % 4 != 0: refused by the library, before any launch
     with pytest.raises(ops._lib.LittleGanHipError, match="lgr_r1_seed"):
         ops.r1_seed(g, float("nan"))
-
-
-# ---------------------------------------------------------------------------------------------------------------- memory contract
-CONTRACT_CASES = []
-
-
-def contract_row(*a, **k):
-    CONTRACT_CASES.append(MC.Row(*a, **k))
-
-
-def _seed_row(B, L):
-    def run(ops, alloc):
-        g = alloc.inp("g", exact_seed_case(B, L)[0])
-        loss, r1l = alloc.state("loss", np.array([EXACT_LOSS0], np.float32)), alloc.out("r1_loss", (1,))
-        u0, r2 = alloc.out("u0", (B, L)), alloc.out("r2", (B,))
-        lib = ops._lib.load()
-        ws = ops.workspace(int(lib.lgr_r1_workspace_bytes(B, L)), g.device, "r1")   # (the wrapper allocates its outputs: guarded ones here)
-        ops._lib.check(lib.lgr_r1_seed(g.data_ptr(), u0.data_ptr(), r2.data_ptr(), loss.data_ptr(), r1l.data_ptr(), EXACT_WEIGHT,
-                                       ws.data_ptr(), ws.numel(), B, L, torch.cuda.current_stream().cuda_stream), "lgr_r1_seed")
-        return dict(u0=u0, r2=r2, loss=loss, r1_loss=r1l)
-
-    def check(res):
-        _, u0, r2, term, loss = exact_seed_case(B, L)
-        assert np.array_equal(_bits(res["u0"]), _np_bits(u0)) and np.array_equal(_bits(res["r2"]), _np_bits(r2))
-        assert np.array_equal(_bits(res["r1_loss"]), _np_bits([term])) and np.array_equal(_bits(res["loss"]), _np_bits([loss]))
-
-    contract_row(f"r1-seed-{B}x{L}", ("lgr_r1_seed",), run, check)
-
-
-def _colsum_row(B, K):
-    def run(ops, alloc):
-        u, d0, _ = exact_colsum_case(B, K)
-        dw = alloc.state("dwpr", d0)
-        ops.r1_heads_colsum(alloc.inp("u", u), dw)
-        return dict(dwpr=dw)
-
-    def check(res):
-        assert np.array_equal(_bits(res["dwpr"]), _np_bits(exact_colsum_case(B, K)[2]))
-
-    contract_row(f"r1-colsum-{B}x{K}", ("lgr_r1_heads_colsum",), run, check)
-
-
-def _heads_seed_row(B, K):
-    def run(ops, alloc):
-        wpr = alloc.inp("wpr", heads_seed_wpr(K).reshape(K, 1))
-        g = alloc.out("g", (B, K))
-        ops._lib.check(ops._lib.load().lgr_r1_heads_seed(wpr.data_ptr(), g.data_ptr(), B, K, torch.cuda.current_stream().cuda_stream),
-                       "lgr_r1_heads_seed")
-        return dict(g=g.view(torch.int32))   # compared as words: a NaN is equal to itself
-
-    def check(res):
-        assert np.array_equal(res["g"].cpu().numpy(), np.broadcast_to(heads_seed_wpr(K).view(np.int32), (B, K)))
-
-    contract_row(f"r1-heads-seed-{B}x{K}", ("lgr_r1_heads_seed",), run, check)
-
-
-_seed_row(1, 4)
-_seed_row(4, 4100)
-_colsum_row(1, 4)
-_colsum_row(33, 5)
-_heads_seed_row(1, 1)
-_heads_seed_row(3, 8)
-
-
-@pytest.mark.parametrize("case", CONTRACT_CASES, ids=lambda r: r.id)
-def test_memory_contract_of_the_regularisers(case, ops, monkeypatch):
-    """The body of tests/test_memory_contract_gpu.py::test_memory_contract on this module's rows: plain twice, then red zones, outputs
-    and exactly-sized workspaces filled with 0xFF, 0x00 and 0x3F.  That body counts lg_* fetches, so the row goes in without its
-    lgr_* names and they are counted here."""
-    fetched = fetched_lgr(monkeypatch, ops)
-    MC.test_memory_contract(MC.Row(case.id, (), case.run, case.check), ops, monkeypatch)
-    missing = set(case.covers) - set(fetched)
-    assert not missing, f"the row claims entry points it never fetched: {sorted(missing)} (fetched {sorted(set(fetched))})"
 
 
 # ---------------------------------------------------------------------------------------------------------------- penalty
@@ -387,17 +295,17 @@ def test_lazy_interval(ops, monkeypatch, mfma):
     tr.losses["r1"].fill_(7.0)
     inp = dev_inputs(_step_inputs(cfg, 3))
     with monkeypatch.context() as mp_:
-        names = fetched_lgr(mp_, ops)
+        names = called(mp_, ops)
         tr.train_step_from_inputs(3, inp)
         off.train_step_from_inputs(3, inp)
         torch.cuda.synchronize()
-    assert names == [] and float(tr.losses["r1"]) == 7.0
+    assert not [n for n in names if n.startswith("lgr_")] and float(tr.losses["r1"]) == 7.0
     assert torch.equal(tr.store.grad, off.store.grad) and torch.equal(tr.store.flat, off.store.flat)
     assert torch.equal(tr.losses["disc"], off.losses["disc"])
     host = _step_inputs(cfg, 4)
     load_weights(tr, W)
     with monkeypatch.context() as mp_:
-        names = fetched_lgr(mp_, ops)
+        names = called(mp_, ops)
         _, _, _, ld, _ = tr.train_step_from_inputs(4, dev_inputs(host))
         torch.cuda.synchronize()
     assert {"lgr_r1_heads_seed", "lgr_r1_seed", "lgr_r1_heads_colsum"} <= set(names)
@@ -478,13 +386,13 @@ def test_defaults_fetch_nothing_and_agree(ops, monkeypatch):
     absent, zero = _build_r1(cfg, W, "f32", r1_gamma=None), _build_r1(cfg, W, "f32", r1_gamma=0, r1_interval=1)
     assert not hasattr(absent.args, "r1_gamma") and absent.r1 is None and zero.r1 is None
     assert "r1" not in absent.losses and "r1" not in zero.losses
-    names = fetched_lgr(monkeypatch, ops)
+    names = called(monkeypatch, ops)
     for b in (1, 2, 16):
         inp = dev_inputs(_step_inputs(cfg, b))
         absent.train_step_from_inputs(b, inp)
         zero.train_step_from_inputs(b, inp)
     torch.cuda.synchronize()
-    assert names == []
+    assert names and not [n for n in names if n.startswith("lgr_")]
     assert torch.equal(absent.store.flat, zero.store.flat) and torch.equal(absent.store.grad, zero.store.grad)
 
 
