@@ -164,6 +164,15 @@ SIGNATURES = {
 }
 
 
+# include/littlegan_geom.h: geometric augmentation of D's inputs (geom.hip).  A table of its own: SIGNATURES is the ABI of
+# include/littlegan_hip*.h, this one that of the `lgeo_` header; load() binds both (tests/test_geom_cpu.py holds it to its header)
+GEOM_SIGNATURES = {
+    "lgeo_draw": (I, [P, I, I, I, I, I, P, P, P]),
+    "lgeo_fwd": (I, [P, P, P, I, I, P]),
+    "lgeo_bwd": (I, [P, P, P, I, I, P]),
+}
+
+
 class LittleGanHipError(RuntimeError):
     pass
 
@@ -196,7 +205,7 @@ def load():
     # before torch, the system runtime it links against would come in as a SECOND runtime and its kernels would see no device.
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(GEOM_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -8,6 +8,9 @@ diff_augment (comma list out of color,translation,cutout: differentiable augment
 training step, the generator-side tapes differentiated through it; "" = off, the reference's step),
 diff_augment_p / ada_target / ada_interval / ada_kimg (adaptive augmentation probability: each diff_augment component is applied per
 row with probability p, fixed or driven on the device towards ada_target; null / null = every component always),
+geom_augment (comma list out of xflip,rot90,scale,rotate: geometric augmentation of the same images — a per-sample affine resampling,
+bilinear with zero fill, applied before diff_augment's map and differentiated through on the gen / adj tapes; gated by the same p;
+"" = off),
 evaluate_metrics (list out of fid, kid, prdc: what `evaluate` computes; ["fid"] = the reference's run) / evaluate_real_activations (the
 real images' saved activations that kid and prdc need) / kid_subsets / kid_subset_size / prdc_k (metrics.py),
 r1_gamma / r1_interval (R1 gradient penalty on the Discriminator's real-image logit, (r1_gamma r1_interval / 2) mean |dlogit/dx|^2 added
@@ -85,6 +88,11 @@ DEFAULTS = {
     # (the paper uses 0.6), adjusted every ada_interval steps at a rate that takes p from 0 to 1 while D sees ada_kimg thousand real
     # images.  Both need diff_augment to name a component.
     'diff_augment_p': None, 'ada_target': None, 'ada_interval': 4, 'ada_kimg': 500,
+    # geometric augmentation of D's inputs (the blitting / geometric group of Karras et al. 2020): a comma list out of
+    # xflip, rot90, scale, rotate.  Every image D reads is resampled under a per-sample map M = R(theta) Q^k F / s (bilinear, zero fill)
+    # before diff_augment's T, and the gen / adj tapes are differentiated through it; diff_augment_p / ada_target gate its components
+    # with the same p.  "" = off.  Excludes use_gp and dropout_train.
+    'geom_augment': '',
     # sample-based metrics beside FID: which metrics `evaluate` runs (a list out of fid, kid, prdc); the saved
     # activations of the real images that kid / prdc compare against (the stats file holds only mu and sigma; a path, relative ones
     # under test_data_dir); subsets and rows per subset of KID (0 subsets = one estimate over the full sets); k of the k-NN manifolds
@@ -131,11 +139,29 @@ def diff_augment_bits(policy) -> int:
     return bits
 
 
-def ada_settings(diff_augment, diff_augment_p=None, ada_target=None, ada_interval=4, ada_kimg=500.0):
-    """The four keys of the adaptive augmentation probability, validated: None when the step is the plain diff_augment
+GEOM_AUGMENT_BITS = {"xflip": 1, "rot90": 2, "scale": 4, "rotate": 8}
+
+
+def geom_augment_bits(policy) -> int:
+    """The geom_augment key as the policy bits of lgeo_draw (1 xflip, 2 rot90, 4 scale, 8 rotate); "" or None = 0 (off).
+    Raises ValueError for anything but a comma list of the four names."""
+    if policy is None:
+        return 0
+    if not isinstance(policy, str):
+        raise ValueError(f"geom_augment must be a string (a comma list out of {', '.join(GEOM_AUGMENT_BITS)}), got {policy!r}")
+    bits = 0
+    for name in (n.strip() for n in policy.split(",")) if policy.strip() else ():
+        if name not in GEOM_AUGMENT_BITS:
+            raise ValueError(f"geom_augment: unknown component {name!r} in {policy!r} (a comma list out of {', '.join(GEOM_AUGMENT_BITS)})")
+        bits |= GEOM_AUGMENT_BITS[name]
+    return bits
+
+
+def ada_settings(diff_augment, diff_augment_p=None, ada_target=None, ada_interval=4, ada_kimg=500.0, geom_augment=""):
+    """The four keys of the adaptive augmentation probability, validated: None when the step is the plain augmenting
     one (diff_augment_p null or 1.0 and ada_target null: every component applied to every row), else a dict {p0, target (None = a fixed
     p), interval, per_row} of the gated path.  Raises ValueError for a value out of range, and for diff_augment_p or ada_target set
-    while diff_augment names no component."""
+    while neither diff_augment nor geom_augment (gated by the same p) names a component."""
     def number(name, v):
         if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
             raise ValueError(f"{name} must be a number, got {v!r}")
@@ -153,9 +179,10 @@ def ada_settings(diff_augment, diff_augment_p=None, ada_target=None, ada_interva
         per_row = float(np.float32(1.0 / (float(ada_kimg) * 1000.0)))
     if not 0.0 < per_row < float("inf"):
         raise ValueError(f"ada_kimg {ada_kimg!r}: 1 / (ada_kimg * 1000) must be a positive finite fp32 number")
-    if (diff_augment_p is not None or ada_target is not None) and not diff_augment_bits(diff_augment):
-        raise ValueError("diff_augment_p / ada_target need diff_augment to name a component: there is nothing to gate "
-                         f"(diff_augment = {diff_augment!r})")
+    if (diff_augment_p is not None or ada_target is not None) and not diff_augment_bits(diff_augment) \
+            and not geom_augment_bits(geom_augment):
+        raise ValueError("diff_augment_p / ada_target need diff_augment to name a component (or geom_augment): there is nothing to gate "
+                         f"(diff_augment = {diff_augment!r}, geom_augment = {geom_augment!r})")
     if ada_target is None and (diff_augment_p is None or float(diff_augment_p) == 1.0):
         return None
     return {"p0": float(np.float32(0.0 if diff_augment_p is None else diff_augment_p)),
@@ -223,7 +250,8 @@ class Arg:
         for k, v in vars(args).items():
             setattr(self, k, v)
         diff_augment_bits(self.diff_augment)   # a misspelt component fails here, not at the first training step
-        ada_settings(self.diff_augment, self.diff_augment_p, self.ada_target, self.ada_interval, self.ada_kimg)
+        geom_augment_bits(self.geom_augment)
+        ada_settings(self.diff_augment, self.diff_augment_p, self.ada_target, self.ada_interval, self.ada_kimg, self.geom_augment)
         r1_settings(self.r1_gamma, self.r1_interval)
         gan_loss_kind(self.gan_loss, bool(self.use_gp))   # a misspelt objective fails here, and so does wgan without its penalty
         self.evaluate_metrics = metric_list(self.evaluate_metrics)   # a misspelt metric fails here, not after the sampling run

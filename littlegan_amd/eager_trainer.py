@@ -17,7 +17,7 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from .config import ada_settings, diff_augment_bits, gan_loss_kind, r1_settings
+from .config import ada_settings, diff_augment_bits, gan_loss_kind, geom_augment_bits, r1_settings
 from .dist import GradSync
 from .model import Adjuster, Discriminator, Generator, ParamStore
 from .utils import save_image, soft
@@ -89,8 +89,20 @@ class EagerTrainer:
             raise ValueError("diff_augment needs 3-channel images")
         # adaptive augmentation probability (the reference has none): None = every named component on every row, the
         # plain diff_augment step with no state and no launch of its own; else the gated draw, with the controller when a target is set
+        # geometric augmentation of D's inputs (the reference has none): on when geom_augment names a component.  D then
+        # reads T(Geo(image)); the step is "augmenting" (self.augmenting) when either key is on
+        self.geom = geom_augment_bits(getattr(args, "geom_augment", ""))
+        if self.geom and self.use_gp:
+            raise ValueError("geom_augment and use_gp exclude each other: the penalty's double backward through the resampling "
+                             "is not built (DESIGN.md §26)")
+        if self.geom and self.dropout:
+            raise ValueError("geom_augment and dropout_train exclude each other: under geom_augment the Adjuster encodes `fake` itself "
+                             "and the masks of the rows D used to hand over are not built for that pass (DESIGN.md §26)")
+        if self.geom and int(getattr(args, "image_channel", 3)) != 3:
+            raise ValueError("geom_augment needs 3-channel images")
+        self.augmenting = bool(self.diffaug or self.geom)
         self.ada = ada_settings(getattr(args, "diff_augment", ""), getattr(args, "diff_augment_p", None), getattr(args, "ada_target", None),
-                                getattr(args, "ada_interval", 4), getattr(args, "ada_kimg", 500.0))
+                                getattr(args, "ada_interval", 4), getattr(args, "ada_kimg", 500.0), getattr(args, "geom_augment", ""))
         # R1 penalty on D's real-image logit, applied every r1_interval-th step (the reference has none): None = off
         self.r1 = r1_settings(getattr(args, "r1_gamma", 0.0), getattr(args, "r1_interval", 16))
         if self.r1 is not None and self.use_gp:
@@ -144,7 +156,8 @@ class EagerTrainer:
     def train_step_from_inputs(self, batch_no: int, inp: Dict[str, torch.Tensor]):
         """inp: real_image_1, real_cond_1, real_image_2, real_cond_2, noise, new_image (device fp32, NHWC); with use_gp also
         gp_eps [B] (the penalty's interpolation weights, U[0,1)); with dropout_train also dropout_key (int64 [2] = {seed, key_offset} of
-        the step's mask stream, draw_dropout_key); with diff_augment also diffaug_key (the same kind of pair, draw_diffaug_key).
+        the step's mask stream, draw_dropout_key); with diff_augment or geom_augment also diffaug_key (the same kind of pair, draw_diffaug_key:
+        both read it, on Philox blocks of their own).
         Returns (fake_image, adj_image|None, gen_loss, disc_loss, adj_loss|None) — losses are 1-element device tensors
         (no host sync on the hot path)."""
         a = self.args
@@ -170,11 +183,11 @@ class EagerTrainer:
         # differentiable augmentation call slots: 0 = D on [new_image ; fake], 1 = D on the Adjuster's output.  D reads
         # T(image); `fake` itself (the L1 term, the Adjuster's input, the returned image) stays un-augmented.
         aug_key, S = None, img1.shape[1]
-        if self.diffaug:
+        if self.augmenting:
             aug_key = inp.get("diffaug_key")
             if aug_key is None:
-                raise ValueError("train_step_from_inputs: diff_augment is on and inp has no 'diffaug_key' (int64 [2] device tensor "
-                                 "{seed, key_offset}: draw_diffaug_key)")
+                raise ValueError(f"train_step_from_inputs: {'diff_augment' if self.diffaug else 'geom_augment'} is on and inp has no "
+                                 "'diffaug_key' (int64 [2] device tensor {seed, key_offset}: draw_diffaug_key)")
 
         # ---- forward: fake = G(noise, c2); D on the [new_image ; fake] batch (eager_trainer.py:134-137)
         ctx_g: dict = {}
@@ -200,9 +213,9 @@ class EagerTrainer:
         x_real = new_image   # what D reads as its real batch: the R1 penalty's input on a penalty step
         kind = self.gan_kind
         lk = dict(logits=True) if kind else {}   # a logit-side objective: the heads keep z_pr (same launches, another finaliser)
-        if self.diffaug:
-            par0 = self._diffaug_draw(aug_key, 0, 2 * B, S)
-            d_aug = ops.diffaug_fwd(d_in, par0)
+        if self.augmenting:
+            par0, geo0 = self._augment_draw(aug_key, 0, 2 * B, S)
+            d_aug = self._augment_fwd(d_in, par0, geo0)   # T(Geo(d_in)), either alone when the other key is off
             x_real = d_aug[:B]
             p = D.forward_packed(d_aug, ctx_d, keep_maps=False, **lk)   # the maps are those of T(fake): not handed over
             if adaptive and not run_adj:   # after the step's last draw: step n + 1 is the first to see a new p
@@ -243,8 +256,8 @@ class EagerTrainer:
         else:
             ops.bce_heads_loss(p[B:], c2, soft(1.0), 1.0, 1.0, self.losses["gen"], dz_g, False)
         g_img = D.backward(ctx_d, dz_g, need_wgrad=False, need_input_grad=True, rows=slice(B, 2 * B))
-        if self.diffaug:
-            g_img = ops.diffaug_bwd(g_img, par0[B:])   # the gen tape is differentiated through T: rows B..2B of slot 0
+        if self.augmenting:   # the gen tape is differentiated through the augmentation, Geo^T(T^T g): rows B..2B of slot 0
+            g_img = self._augment_bwd(g_img, None if par0 is None else par0[B:], None if geo0 is None else geo0[B:])
         dpre = torch.empty_like(g_img)
         ops.l1_tanh_loss(img2, fake, g_img, dpre, self.losses["gen"], a.l1_lambda, True)
         rng_g = train_weight_range(a, "G", batch_no)
@@ -258,7 +271,7 @@ class EagerTrainer:
             ctx_a: dict = {}
             # encoder(fake) was computed by D above with the same weights: hand its 4 maps to the Adjuster.  Under diff_augment D
             # encoded T(fake), so `fake` is encoded here, by one more B-row pass whose maps take the same place
-            if self.diffaug:
+            if self.augmenting:
                 tails = A.encoder(fake)
             else:
                 tails = [m[B:] for m in ctx_d["enc_maps"]]  # fp32 maps (f32 path) / bf16 mirrors + the fp32 top map (bf16 path)
@@ -266,11 +279,11 @@ class EagerTrainer:
             # handed-over maps keep the masks call 0 drew for them — no tape differentiates through the skips)
             adj_image = A([img1, adj_in_cond], ctx_a, enc_tails=tails, drop=drop[1])
             ctx_d2: dict = {}
-            if self.diffaug:
-                par1 = self._diffaug_draw(aug_key, 1, 2 * B, S)
+            if self.augmenting:
+                par1, geo1 = self._augment_draw(aug_key, 1, 2 * B, S)
                 if adaptive:   # both draws of the step have read p: the real rows of slot 0 feed the controller
                     self._ada_control(p, B)
-                p_a = D.forward_packed(ops.diffaug_fwd(adj_image, par1), ctx_d2, keep_maps=False, top_only=True, **lk)
+                p_a = D.forward_packed(self._augment_fwd(adj_image, par1, geo1), ctx_d2, keep_maps=False, top_only=True, **lk)
             else:
                 p_a = D.forward_packed(adj_image, ctx_d2, keep_maps=False, top_only=True, drop=drop[2], **lk)
             dz_a = torch.empty(2 * B, 1 + c, dtype=torch.float32, device=self.device)
@@ -279,8 +292,8 @@ class EagerTrainer:
             else:
                 ops.bce_heads_loss(p_a, adj_t_cond, soft(1.0), 1.0, 1.0, self.losses["adj"], dz_a, False)
             g_adj = D.backward(ctx_d2, dz_a, need_wgrad=False, need_input_grad=True)
-            if self.diffaug:
-                g_adj = ops.diffaug_bwd(g_adj, par1)
+            if self.augmenting:
+                g_adj = self._augment_bwd(g_adj, par1, geo1)
             dpre_a = torch.empty_like(g_adj)
             # target = [img2 ; img1]: one call per half instead of a 2B-image concatenation (lambda / 2 over half the elements is
             # the same scale, exactly: the element count is a multiple of a power of two)
@@ -305,6 +318,29 @@ class EagerTrainer:
         if self.ada is None:
             return ops.diffaug_draw(key, call, 0, rows, S, self.diffaug)
         return ops.diffaug_draw_gated(key, call, 0, rows, S, self.diffaug, self.ada_state)
+
+    def _augment_draw(self, key, call, rows, S):
+        """The records of call slot `call`: (diff_augment's | None, the geometric ones | None), each under the present p on the gated path"""
+        par = self._diffaug_draw(key, call, rows, S) if self.diffaug else None
+        geo = ops.geom_draw(key, call, 0, rows, S, self.geom, None if self.ada is None else self.ada_state) if self.geom else None
+        return par, geo
+
+    def _augment_fwd(self, images, par, geo):
+        """What D reads of `images`: T(Geo(images)), Geo alone when diff_augment is off, T alone when geom_augment
+        is — then exactly the launches of the diff_augment step"""
+        if geo is not None:
+            images = ops.geom_fwd(images, geo)
+        if par is not None:
+            images = ops.diffaug_fwd(images, par)
+        return images
+
+    def _augment_bwd(self, g, par, geo):
+        """The adjoint of _augment_fwd on an image gradient: Geo^T(T^T g)"""
+        if par is not None:
+            g = ops.diffaug_bwd(g, par)
+        if geo is not None:
+            g = ops.geom_bwd(g, geo)
+        return g
 
     def _ada_tick(self):
         """Advances the host mirror of the state's step counter, once per training step: at the top of train_step_from_inputs, or at
@@ -472,7 +508,7 @@ class EagerTrainer:
             inp["gp_eps"] = self.draw_gp_eps(real_image_1.shape[0])
         if self.dropout:
             inp["dropout_key"] = self.draw_dropout_key()
-        if self.diffaug:
+        if self.augmenting:
             inp["diffaug_key"] = self.draw_diffaug_key()
         fake, adj, lg, ld, la = self.train_step_from_inputs(batch_no, inp)
         return True, fake, adj, lg, ld, la
@@ -501,7 +537,7 @@ class EagerTrainer:
             inp["gp_eps"] = self.draw_gp_eps(B)
         if self.dropout:
             inp["dropout_key"] = self.draw_dropout_key()
-        if self.diffaug:
+        if self.augmenting:
             inp["diffaug_key"] = self.draw_diffaug_key()
         fake, adj, lg, ld, la = self.train_step_from_inputs(batch_no, inp)
         return True, fake, adj, lg, ld, la

@@ -1222,6 +1222,47 @@ def ada_read(state):
     return float(host[0]), w[1], w[2], w[3]
 
 
+# ------------------------------------------------------------------ geometric augmentation of D's inputs (geom.hip)
+def geom_draw(key, call, r0, rows, S, policy, state=None, out=None):
+    """geo [rows, 4] fp32 = the records {a, b, c, d} (M = R(theta) Q^k F / s, destination -> source about the centre) of rows
+    r0 .. r0+rows-1 of call slot `call` under the step's diff_augment key; policy: the geom_augment string or its bits; state: None =
+    every named component on every row, else the ADA state whose p gates each component per row.  See include/littlegan_geom.h"""
+    from .config import geom_augment_bits
+    bits = int(policy) if isinstance(policy, int) else geom_augment_bits(policy)
+    _chk_key(key, "geom_draw")
+    if state is not None:
+        _chk_ada(state, "geom_draw")
+    if out is None:
+        out = torch.empty(int(rows), 4, dtype=torch.float32, device=key.device)
+    _chk(out, (int(rows), 4), "out")
+    check(_lib.load().lgeo_draw(_p(key), int(call), int(r0), int(rows), int(S), bits, None if state is None else _p(state), _p(out),
+                                _stream()), "lgeo_draw")
+    return out
+
+
+def _geom_map(fn_name, v, geo, out):
+    _chk(v, name="image")
+    rows, S, W, c = v.shape
+    if W != S or c != 3:
+        raise ValueError(f"{fn_name}: square 3-channel NHWC images only, got {tuple(v.shape)}")
+    _chk(geo, (rows, 4), "geo")
+    if out is None:
+        out = torch.empty_like(v)
+    _chk(out, v.shape, "out")
+    check(getattr(_lib.load(), fn_name)(_p(v), _p(geo), _p(out), rows, S, _stream()), fn_name)
+    return out
+
+
+def geom_fwd(x, geo, out=None):
+    """Geo(x): x [rows, S, S, 3] fp32 resampled bilinearly (zero fill) under geo [rows, 4] (geom_draw, or hand-built records)"""
+    return _geom_map("lgeo_fwd", x, geo, out)
+
+
+def geom_bwd(g, geo, out=None):
+    """The exact adjoint of geom_fwd: the gradient w.r.t. x of <Geo(x), g>, gathered in a fixed order"""
+    return _geom_map("lgeo_bwd", g, geo, out)
+
+
 
 # ------------------------------------------------------------------ packed uint8 data set (input_u8.hip, DESIGN.md §13)
 def _chk_rows(src, idx, name):
