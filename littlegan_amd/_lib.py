@@ -172,6 +172,14 @@ GEOM_SIGNATURES = {
     "lgeo_bwd": (I, [P, P, P, I, I, P]),
 }
 
+# include/littlegan_rel.h: the relativistic pairing objective and the R1 + R2 seed (objective.hip, r1.hip).  A table of its
+# own for the same reason; load() binds it too (tests/test_rel_cpu.py holds it to its header)
+REL_SIGNATURES = {
+    "lgrel_pair_heads_loss_fwd_bwd": (I, [P, P, P, P, I, I, F, F, P, P, I, I, I, I, P]),
+    "lgrel_r12_workspace_bytes": (Z, [I, L]),
+    "lgrel_r12_seed": (I, [P, P, P, P, P, P, F, F, P, Z, I, L, P]),
+}
+
 
 class LittleGanHipError(RuntimeError):
     pass
@@ -205,7 +213,7 @@ def load():
     # before torch, the system runtime it links against would come in as a SECOND runtime and its kernels would see no device.
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name, (res, args) in list(SIGNATURES.items()) + list(GEOM_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(GEOM_SIGNATURES.items()) + list(REL_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

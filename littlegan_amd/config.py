@@ -17,7 +17,11 @@ r1_gamma / r1_interval (R1 gradient penalty on the Discriminator's real-image lo
 to the disc loss on every r1_interval-th step; 0 = off; excludes use_gp and dropout_train, allowed with diff_augment),
 gan_loss ("bce" | "logistic" | "hinge" | "lsgan" | "wgan": the real / fake terms of the three losses; "bce" = the reference's sigmoid +
 clipped cross entropy against 0.98 / 0.02, the others are taken on the pre-sigmoid value of output_pr without smoothing; "wgan" needs
-use_gp, which then penalises the logit)."""
+use_gp, which then penalises the logit),
+relativistic (bool: the real / fake terms become f0(D(real) - D(fake)) per pair of rows, f0 the D-real function of gan_loss, which must be
+logistic, hinge or lsgan) / r2_gamma (the R1 penalty's twin on the fake rows D read, on R1's schedule: r1_interval, weight
+r2_gamma r1_interval; 0 = off; excludes use_gp and dropout_train; with r1_gamma also on, one pass over the 2B-row batch carries both;
+DESIGN.md §27)."""
 import json
 import os
 from argparse import ArgumentParser
@@ -105,6 +109,14 @@ DEFAULTS = {
     # targets); "logistic" (non-saturating), "hinge", "lsgan", "wgan" are taken on the logit of output_pr, without label smoothing.  The
     # attribute and L1 terms are the same under every value.  "wgan" needs use_gp; under a logit-side objective use_gp penalises the logit.
     'gan_loss': 'bce',
+    # relativistic pairing (Jolicoeur-Martineau 2018): with gan_loss logistic | hinge | lsgan, the real / fake terms of the
+    # three losses become f0(z_r[b] - z_f[b]) (disc), f0(z_f[b] - z_r[b]) (gen) and f0(z_a[i] - z_r[i mod B]) (adj), f0 the kind's D-real
+    # function, row b of the real half paired with row b of the fake half.  false = the terms of §25.
+    'relativistic': False,
+    # R2 gradient penalty (Huang et al. 2024): R1's term on the FAKE rows D read, on R1's schedule — on every
+    # r1_interval-th step disc_loss += (r2_gamma r1_interval / 2) mean_b |d logit(x_b) / d x_b|^2.  0 = off.  With r1_gamma also on, both
+    # penalties are one reverse-over-reverse pass over the 2B-row batch.  Excludes use_gp and dropout_train.
+    'r2_gamma': 0.0,
 }
 
 GAN_LOSS_KINDS = {"bce": 0, "logistic": 1, "hinge": 2, "lsgan": 3, "wgan": 4}   # the `kind` of lgo_gan_heads_loss_fwd_bwd; 0 = not its
@@ -207,6 +219,38 @@ def r1_settings(r1_gamma=0.0, r1_interval=16):
     return {"gamma": float(r1_gamma), "interval": int(r1_interval), "weight": weight}
 
 
+def r2_settings(r2_gamma=0.0, r1_interval=16):
+    """The R2 penalty's key on R1's schedule, validated as r1_settings validates its own: None when it is off
+    (r2_gamma == 0), else {gamma, interval, weight} with weight = r2_gamma * r1_interval.  Raises ValueError for an r2_gamma that is no
+    finite number >= 0 (bools and strings refused) and for a bad r1_interval."""
+    import math
+    if isinstance(r2_gamma, bool) or not isinstance(r2_gamma, (int, float)) or not math.isfinite(r2_gamma) or r2_gamma < 0:
+        raise ValueError(f"r2_gamma must be a finite number >= 0 (0 = off), got {r2_gamma!r}")
+    if isinstance(r1_interval, bool) or not isinstance(r1_interval, int) or r1_interval < 1:
+        raise ValueError(f"r1_interval must be an integer >= 1, got {r1_interval!r}")
+    weight = float(r2_gamma) * r1_interval
+    if not weight <= 3.0e38:
+        raise ValueError(f"r2_gamma * r1_interval = {weight!r} does not fit fp32 (r2_gamma {r2_gamma!r}, r1_interval {r1_interval!r})")
+    if r2_gamma == 0:
+        return None
+    return {"gamma": float(r2_gamma), "interval": int(r1_interval), "weight": weight}
+
+
+def relativistic_setting(relativistic=False, gan_loss="bce"):
+    """The relativistic key, validated against gan_loss: a bool; True needs gan_loss logistic, hinge or lsgan — "bce" has
+    no logit to pair, and the pairing of "wgan" is wgan itself.  Returns the bool."""
+    if not isinstance(relativistic, bool):
+        raise ValueError(f"relativistic must be true or false, got {relativistic!r}")
+    if relativistic and gan_loss == "bce":
+        raise ValueError("relativistic needs a logit-side gan_loss (logistic, hinge or lsgan): 'bce' is taken behind the sigmoid and has "
+                         "no logit to pair (DESIGN.md §27)")
+    if relativistic and gan_loss == "wgan":
+        raise ValueError("relativistic excludes gan_loss 'wgan': f0(z_r - z_f) = -z_r + z_f is the wgan objective itself (DESIGN.md §27)")
+    if relativistic and gan_loss not in ("logistic", "hinge", "lsgan"):
+        raise ValueError(f"relativistic needs gan_loss logistic, hinge or lsgan, got {gan_loss!r}")
+    return relativistic
+
+
 METRIC_NAMES = ("fid", "kid", "prdc")
 
 
@@ -254,6 +298,8 @@ class Arg:
         ada_settings(self.diff_augment, self.diff_augment_p, self.ada_target, self.ada_interval, self.ada_kimg, self.geom_augment)
         r1_settings(self.r1_gamma, self.r1_interval)
         gan_loss_kind(self.gan_loss, bool(self.use_gp))   # a misspelt objective fails here, and so does wgan without its penalty
+        relativistic_setting(self.relativistic, self.gan_loss)
+        r2_settings(self.r2_gamma, self.r1_interval)
         self.evaluate_metrics = metric_list(self.evaluate_metrics)   # a misspelt metric fails here, not after the sampling run
         if int(self.kid_subsets) < 0 or int(self.kid_subset_size) < 2 or not 1 <= int(self.prdc_k) <= 15:
             raise ValueError("need kid_subsets >= 0, kid_subset_size >= 2 and 1 <= prdc_k <= 15")

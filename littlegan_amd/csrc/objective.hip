@@ -4,8 +4,11 @@
 //   heads_final_logit_kernel : heads_final_kernel (heads.hip) that also stores z of column 0 — the GEMM partials are lg_heads_fwd's
 //   gan_heads_kernel         : bce_heads_kernel with column 0 replaced by f(z) / f'(z); the attribute columns keep its expressions and
 //                              its thread mapping, so with w_pr == 0 the two kernels write the same bits
+//   pair_heads_kernel        : gan_heads_kernel with column 0 taken on the difference of two logits (relativistic pairing, DESIGN.md §27,
+//                              include/littlegan_rel.h): the same gan_term at role 0, the same attribute columns
 #include "lg_internal.h"
 #include "../../include/littlegan_hip_obj.h"
+#include "../../include/littlegan_rel.h"
 
 #define LG_BCE_EPS 1e-7f   // = loss_optim.hip's
 
@@ -58,6 +61,15 @@ __device__ __forceinline__ void gan_term(int kind, int role, float z, float s, f
   }
 }
 
+// an attribute column (the expressions of bce_heads_kernel): returns its summand of the loss, g = its gradient (0 outside the clip)
+__device__ __forceinline__ float attr_term(float t, float pv, float sc, float& g) {
+  const float pc = fminf(fmaxf(pv, LG_BCE_EPS), 1.f - LG_BCE_EPS);
+  const float f = -sc * (t * logf(pc + LG_BCE_EPS) + (1.f - t) * logf(1.f - pc + LG_BCE_EPS));
+  const bool inside = pv >= LG_BCE_EPS && pv <= 1.f - LG_BCE_EPS;
+  if (inside) g = -sc * (t / (pc + LG_BCE_EPS) - (1.f - t) / (1.f - pc + LG_BCE_EPS)) * pv * (1.f - pv);
+  return f;
+}
+
 __global__ __launch_bounds__(1024) void gan_heads_kernel(const float* __restrict__ p, const float* __restrict__ zpr,
                                                         const float* __restrict__ t_c, int kind, int role, float w_pr, float w_c,
                                                         float* __restrict__ loss, float* __restrict__ dz, int B, int c, int accumulate) {
@@ -74,12 +86,45 @@ __global__ __launch_bounds__(1024) void gan_heads_kernel(const float* __restrict
         gan_term(kind, role, zpr[b], sc, f, g);
         acc += f;
       } else {
-        const float t = t_c[b * c + j - 1];
-        const float pv = p[i];
-        const float pc = fminf(fmaxf(pv, LG_BCE_EPS), 1.f - LG_BCE_EPS);
-        acc += -sc * (t * logf(pc + LG_BCE_EPS) + (1.f - t) * logf(1.f - pc + LG_BCE_EPS));
-        const bool inside = pv >= LG_BCE_EPS && pv <= 1.f - LG_BCE_EPS;
-        if (inside) g = -sc * (t / (pc + LG_BCE_EPS) - (1.f - t) / (1.f - pc + LG_BCE_EPS)) * pv * (1.f - pv);
+        acc += attr_term(t_c[b * c + j - 1], p[i], sc, g);
+      }
+    }
+    dz[i] = g;
+  }
+  __shared__ float sred[16];
+  float red[1] = {acc};
+  lg_block_sum<1>(red, sred);
+  if (threadIdx.x == 0) loss[0] = (accumulate ? loss[0] : 0.f) + red[0];
+}
+
+// gan_heads_kernel with column 0 taken on a PAIR of logits (relativistic pairing): f0 = gan_term's role-0 function of the
+// kind, t = z[b] - z_ref[b mod m] (SELF: the loss and its gradient with respect to z) or z_ref[b mod m] - z[b] (OTHER: the gradient
+// with respect to z of the pair's term, which the SELF call of the other half has added to the loss).  The attribute columns, the loop
+// and the block sum are gan_heads_kernel's.
+__global__ __launch_bounds__(1024) void pair_heads_kernel(const float* __restrict__ p, const float* __restrict__ z,
+                                                         const float* __restrict__ z_ref, const float* __restrict__ t_c, int kind, int side,
+                                                         float w_pr, float w_c, float* __restrict__ loss, float* __restrict__ dz, int n,
+                                                         int m, int c, int accumulate) {
+  const int J = c + 1, tot = n * J;
+  const float s_pr = w_pr / (float)n, s_c = w_c / (float)(n * c);
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < tot; i += blockDim.x) {
+    const int b = i / J, j = i - b * J;
+    const float sc = j == 0 ? s_pr : s_c;
+    float g = 0.f;
+    if (sc != 0.f) {
+      if (j == 0) {
+        const float zr = z_ref[b % m];
+        float f;
+        if (side == LGREL_SIDE_SELF) {
+          gan_term(kind, LGO_ROLE_D_REAL, z[b] - zr, sc, f, g);
+          acc += f;
+        } else {
+          gan_term(kind, LGO_ROLE_D_REAL, zr - z[b], sc, f, g);
+          g = -g;
+        }
+      } else {
+        acc += attr_term(t_c[b * c + j - 1], p[i], sc, g);
       }
     }
     dz[i] = g;
@@ -123,5 +168,26 @@ extern "C" int lgo_gan_heads_loss_fwd_bwd(const float* p, const float* z_pr, con
                      accumulate);
   LG_CHECK_LAUNCH("lgo_gan_heads_loss_fwd_bwd");
   lg_note_kernel("gan_heads_kernel");
+  return LG_OK;
+}
+
+extern "C" int lgrel_pair_heads_loss_fwd_bwd(const float* p, const float* z, const float* z_ref, const float* t_c, int kind, int side,
+                                             float w_pr, float w_c, float* loss, float* dz, int n, int m, int c, int accumulate,
+                                             void* stream) {
+  LG_CHECK_ARG(p && z && z_ref && loss && dz, "lgrel_pair_heads_loss_fwd_bwd: null pointer");
+  LG_CHECK_ARG((((uintptr_t)p | (uintptr_t)z | (uintptr_t)z_ref | (uintptr_t)t_c | (uintptr_t)loss | (uintptr_t)dz) & 3) == 0,
+               "lgrel_pair_heads_loss_fwd_bwd: every pointer must be 4-byte aligned");
+  LG_CHECK_ARG(kind >= LGO_KIND_LOGISTIC && kind <= LGO_KIND_LSGAN,
+               "lgrel_pair_heads_loss_fwd_bwd: bad kind %d (1 logistic, 2 hinge, 3 lsgan; wgan of a difference is wgan itself)", kind);
+  LG_CHECK_ARG(side == LGREL_SIDE_SELF || side == LGREL_SIDE_OTHER, "lgrel_pair_heads_loss_fwd_bwd: bad side %d (0 self, 1 other)", side);
+  LG_CHECK_ARG(n > 0 && c >= 1 && (long long)n * (c + 1) < (1LL << 31), "lgrel_pair_heads_loss_fwd_bwd: bad shape n=%d c=%d", n, c);
+  LG_CHECK_ARG(m > 0 && n % m == 0, "lgrel_pair_heads_loss_fwd_bwd: n=%d must be a multiple of m=%d > 0", n, m);
+  LG_CHECK_ARG(finite_f(w_pr) && finite_f(w_c), "lgrel_pair_heads_loss_fwd_bwd: weights w_pr=%g w_c=%g must be finite", (double)w_pr,
+               (double)w_c);
+  LG_CHECK_ARG(t_c || w_c == 0.f, "lgrel_pair_heads_loss_fwd_bwd: t_c is null but w_c != 0");
+  hipLaunchKernelGGL(pair_heads_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, p, z, z_ref, t_c, kind, side, w_pr, w_c, loss, dz, n,
+                     m, c, accumulate);
+  LG_CHECK_LAUNCH("lgrel_pair_heads_loss_fwd_bwd");
+  lg_note_kernel("pair_heads_kernel");
   return LG_OK;
 }

@@ -10,8 +10,11 @@
 // Every reduction has ONE order that the shape alone decides: fp64 partials over chunks / slabs whose boundaries depend on (B, L) or
 // (B, K), merged in index order.  The grids come from the CU budget (lg_grid_cus), the partial layout does not: blocks walk the items
 // with a stride, and an item's partial is the same whichever block computes it.  No atomics.
+// lgrel_r12_seed (R1 + R2 in one pass over a 2B-row batch, DESIGN.md §27, include/littlegan_rel.h) is the seed with a weight per half:
+// the same pass kernel with the scale selected per row, the same final sums once per half.
 #include "lg_internal.h"
 #include "../../include/littlegan_hip_reg.h"
+#include "../../include/littlegan_rel.h"
 
 namespace {
 
@@ -44,12 +47,15 @@ __global__ __launch_bounds__(256) void r1_heads_seed_kernel(const unsigned* __re
   }
 }
 
-// item = (row b, chunk j): u0 = scale g over the chunk, part[b][j] = sum of g^2 over it (products and sum in fp64: exact products)
+// item = (row b, chunk j): u0 = scale g over the chunk, part[b][j] = sum of g^2 over it (products and sum in fp64: exact products).
+// Rows from `split` on take scale_hi (lgrel_r12_seed: the fake half of a 2B-row batch); lgr_r1_seed passes split = its row count.
 __global__ __launch_bounds__(256) void r1_seed_kernel(const float* __restrict__ g, float* __restrict__ u0, double* __restrict__ part,
-                                                      float scale, long long L, int nch, long long items) {
+                                                      float scale_lo, float scale_hi, long long split, long long L, int nch,
+                                                      long long items) {
   __shared__ double sred[16];
   for (long long it = blockIdx.x; it < items; it += gridDim.x) {
     const long long b = it / nch;
+    const float scale = b < split ? scale_lo : scale_hi;
     const long long c0 = (it - b * nch) * CHUNK;
     const float* gs = g + b * L;
     float* us = u0 + b * L;
@@ -69,11 +75,9 @@ __global__ __launch_bounds__(256) void r1_seed_kernel(const float* __restrict__ 
   }
 }
 
-// r2[b] = the row's partials in chunk order; term = (w / 2) mean_b r2; loss (+)= term, r1_loss = term
-__global__ __launch_bounds__(256) void r1_seed_final_kernel(const double* __restrict__ part, int nch, int B, float w,
-                                                            float* __restrict__ r2, float* __restrict__ loss,
-                                                            float* __restrict__ r1_loss) {
-  __shared__ double sh[256];
+// r2[b] = the row's partials in chunk order over B rows; returns term = (w / 2) mean_b r2, valid in thread 0
+__device__ __forceinline__ float seed_final_term(const double* __restrict__ part, int nch, int B, float w, float* __restrict__ r2,
+                                                 double* sh) {
   double acc = 0.0;
   for (int n = threadIdx.x; n < B; n += 256) {
     double s = 0.0;
@@ -82,10 +86,33 @@ __global__ __launch_bounds__(256) void r1_seed_final_kernel(const double* __rest
     acc += s;
   }
   const double tot = block_tree_sum(acc, sh);
+  return (float)(0.5 * (double)w * tot / (double)B);
+}
+
+// loss (+)= term, r1_loss = term
+__global__ __launch_bounds__(256) void r1_seed_final_kernel(const double* __restrict__ part, int nch, int B, float w,
+                                                            float* __restrict__ r2, float* __restrict__ loss,
+                                                            float* __restrict__ r1_loss) {
+  __shared__ double sh[256];
+  const float term = seed_final_term(part, nch, B, w, r2, sh);
   if (threadIdx.x == 0) {
-    const float term = (float)(0.5 * (double)w * tot / (double)B);
     if (loss) loss[0] = loss[0] + term;
     if (r1_loss) r1_loss[0] = term;
+  }
+}
+
+// the two halves of a 2B-row batch, each as r1_seed_final_kernel takes its B rows: loss = (loss + term_real) + term_fake
+__global__ __launch_bounds__(256) void r12_seed_final_kernel(const double* __restrict__ part, int nch, int B, float w_real, float w_fake,
+                                                             float* __restrict__ r2, float* __restrict__ loss,
+                                                             float* __restrict__ r1_loss, float* __restrict__ r2_loss) {
+  __shared__ double sh[256];
+  const float t_real = seed_final_term(part, nch, B, w_real, r2, sh);
+  __syncthreads();   // thread 0 has read sh[0] before the second tree writes it
+  const float t_fake = seed_final_term(part + (long long)B * nch, nch, B, w_fake, r2 + B, sh);
+  if (threadIdx.x == 0) {
+    if (loss) loss[0] = (loss[0] + t_real) + t_fake;
+    if (r1_loss) r1_loss[0] = t_real;
+    if (r2_loss) r2_loss[0] = t_fake;
   }
 }
 
@@ -179,10 +206,43 @@ extern "C" int lgr_r1_seed(const float* g, float* u0, float* r2, float* loss, fl
   const long long items = (long long)B * nch;
   lg_note_kernel("r1_seed_kernel");
   hipLaunchKernelGGL(r1_seed_kernel, dim3(grid_of(items, R1_RESIDENT(r1_seed_kernel))), dim3(256), 0, st, g, u0, part,
-                     weight / (float)B, L, nch, items);
+                     weight / (float)B, 0.f, (long long)B, L, nch, items);
   LG_CHECK_LAUNCH("lgr_r1_seed(pass)");
   hipLaunchKernelGGL(r1_seed_final_kernel, dim3(1), dim3(256), 0, st, (const double*)part, nch, B, weight, r2, loss, r1_loss);
   LG_CHECK_LAUNCH("lgr_r1_seed(final)");
+  return LG_OK;
+}
+
+extern "C" size_t lgrel_r12_workspace_bytes(int B, long long L) {
+  if (B <= 0 || L <= 0) return 0;
+  return al(2 * (size_t)B * (size_t)nchunks(L) * sizeof(double));
+}
+
+// lgr_r1_seed over g[2B][L] with a weight per half: the same pass kernel (the scale selected per row) and the same per-half final sums,
+// so the bits are those of two lgr_r1_seed calls on the halves
+extern "C" int lgrel_r12_seed(const float* g, float* u0, float* r2, float* loss, float* r1_loss, float* r2_loss, float w_real, float w_fake,
+                              void* workspace, size_t ws_bytes, int B, long long L, void* stream) {
+  LG_CHECK_ARG(g && u0 && r2 && workspace, "lgrel_r12_seed: null pointer");
+  LG_CHECK_ARG(aligned16(g, u0) && ((uintptr_t)workspace & 7) == 0, "lgrel_r12_seed: g and u0 must be 16-byte, workspace 8-byte aligned");
+  LG_CHECK_ARG((((uintptr_t)r2 | (uintptr_t)loss | (uintptr_t)r1_loss | (uintptr_t)r2_loss) & 3) == 0,
+               "lgrel_r12_seed: r2, loss, r1_loss and r2_loss must be 4-byte aligned");
+  LG_CHECK_ARG(B > 0 && L > 0 && L % 4 == 0 && L / 4 < (1LL << 31) && 2 * (long long)B * (L / 4) < (1LL << 31),
+               "lgrel_r12_seed: bad shape B=%d L=%lld (g is [2B][L]; L %% 4 == 0, 2 B * L / 4 < 2^31)", B, L);
+  LG_CHECK_ARG(w_real >= 0.f && w_real <= 3.402823466e38f && w_fake >= 0.f && w_fake <= 3.402823466e38f,
+               "lgrel_r12_seed: weights w_real=%g w_fake=%g must be finite and >= 0", (double)w_real, (double)w_fake);
+  LG_CHECK_ARG(ws_bytes >= lgrel_r12_workspace_bytes(B, L), "lgrel_r12_seed: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  double* part = (double*)workspace;
+  const int nch = (int)nchunks(L);
+  const long long items = 2 * (long long)B * nch;
+  lg_note_kernel("r1_seed_kernel");
+  hipLaunchKernelGGL(r1_seed_kernel, dim3(grid_of(items, R1_RESIDENT(r1_seed_kernel))), dim3(256), 0, st, g, u0, part,
+                     w_real / (float)B, w_fake / (float)B, (long long)B, L, nch, items);
+  LG_CHECK_LAUNCH("lgrel_r12_seed(pass)");
+  lg_note_kernel("r12_seed_final_kernel");
+  hipLaunchKernelGGL(r12_seed_final_kernel, dim3(1), dim3(256), 0, st, (const double*)part, nch, B, w_real, w_fake, r2, loss, r1_loss,
+                     r2_loss);
+  LG_CHECK_LAUNCH("lgrel_r12_seed(final)");
   return LG_OK;
 }
 

@@ -17,7 +17,7 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from .config import ada_settings, diff_augment_bits, gan_loss_kind, geom_augment_bits, r1_settings
+from .config import ada_settings, diff_augment_bits, gan_loss_kind, geom_augment_bits, r1_settings, r2_settings, relativistic_setting
 from .dist import GradSync
 from .model import Adjuster, Discriminator, Generator, ParamStore
 from .utils import save_image, soft
@@ -114,6 +114,19 @@ class EagerTrainer:
         # none of the logit-side code runs; else the `kind` of ops.gan_heads_loss, and use_gp penalises the logit
         self.gan_loss = getattr(args, "gan_loss", "bce")
         self.gan_kind = gan_loss_kind(self.gan_loss, self.use_gp)
+        # relativistic pairing of the real / fake terms (the reference has none): f0(z_r - z_f) per pair of rows, through
+        # ops.pair_heads_loss where ops.gan_heads_loss stands otherwise; refused for "bce" (no logit) and "wgan" (its pairing is itself)
+        self.relativistic = relativistic_setting(getattr(args, "relativistic", False), self.gan_loss)
+        # R2 penalty: R1's term on the fake rows D read, on R1's schedule (the reference has none): None = off
+        self.r2 = r2_settings(getattr(args, "r2_gamma", 0.0), getattr(args, "r1_interval", 16))
+        # with both penalties on: one joint 2B-row pass (the product path), or two B-row passes.  No configuration key: an attribute
+        # that scripts/bench_rel.py clears on one of its trainers to time the alternative
+        self.r12_joint = True
+        if self.r2 is not None and self.use_gp:
+            raise ValueError("r2_gamma and use_gp exclude each other: two gradient penalties on one disc tape (DESIGN.md §27)")
+        if self.r2 is not None and self.dropout:
+            raise ValueError("r2_gamma and dropout_train exclude each other: the penalty's double backward through a masked norm "
+                             "is not built (DESIGN.md §27)")
         # weight average for sampling (the reference has none): on when ema_decay > 0
         self.ema_decay = validate_ema_decay(getattr(args, "ema_decay", 0.0))
         self.sample_ema = bool(getattr(args, "sample_ema", True))
@@ -127,7 +140,8 @@ class EagerTrainer:
         self.opt_state = {m: torch.tensor([b1, b2], dtype=torch.float32, device=self.device)
                           for m, (_, b1, b2) in self.opt_cfg.items()}
         self.losses = {k: torch.zeros(1, dtype=torch.float32, device=self.device)
-                       for k in ("gen", "disc", "adj") + (("gp",) if self.use_gp else ()) + (("r1",) if self.r1 is not None else ())}
+                       for k in ("gen", "disc", "adj") + (("gp",) if self.use_gp else ()) + (("r1",) if self.r1 is not None else ())
+                       + (("r2",) if self.r2 is not None else ())}
         self.sync = GradSync(self.device)
         self.adam_order = ("D", "G", "A")   # = the launch order of the all-reduces (see train_step_from_inputs)
         self.global_epoch = 1
@@ -211,12 +225,13 @@ class EagerTrainer:
             self._ada_tick()
         # the Adjuster reuses D's encoder maps of `fake` as its skip inputs: keep the fp32 maps only then
         x_real = new_image   # what D reads as its real batch: the R1 penalty's input on a penalty step
+        x_all = d_in         # ... and the whole batch D reads, [real ; fake]: the fake half is the R2 penalty's input
         kind = self.gan_kind
         lk = dict(logits=True) if kind else {}   # a logit-side objective: the heads keep z_pr (same launches, another finaliser)
         if self.augmenting:
             par0, geo0 = self._augment_draw(aug_key, 0, 2 * B, S)
             d_aug = self._augment_fwd(d_in, par0, geo0)   # T(Geo(d_in)), either alone when the other key is off
-            x_real = d_aug[:B]
+            x_real, x_all = d_aug[:B], d_aug
             p = D.forward_packed(d_aug, ctx_d, keep_maps=False, **lk)   # the maps are those of T(fake): not handed over
             if adaptive and not run_adj:   # after the step's last draw: step n + 1 is the first to see a new p
                 self._ada_control(p, B)
@@ -226,7 +241,14 @@ class EagerTrainer:
         # ---- disc tape (eager_trainer.py:139,145): 2*BCE(c1,real_c) + BCE(.98,real_pr) + BCE(.02,fake_pr)
         dz = torch.empty(2 * B, 1 + c, dtype=torch.float32, device=self.device)
         # (a logit-side gan_loss, DESIGN.md §25: the two BCE(., _pr) become f(z) of the D-real / D-fake rows, no smoothing; the same launches)
-        if kind:
+        rel = self.relativistic
+        if rel:
+            # (relativistic pairing, DESIGN.md §27: ONE term f0(z_r - z_f) per pair, written by the real rows' call; the fake rows' call
+            # adds its gradient with respect to z_f alone.  The same launches, one for one)
+            z = ctx_d["z_pr"]
+            ops.pair_heads_loss(p[:B], z[:B], z[B:], c1, kind, ops.REL_SIDE_SELF, 1.0, 2.0, self.losses["disc"], dz[:B], False)
+            ops.pair_heads_loss(p[B:], z[B:], z[:B], None, kind, ops.REL_SIDE_OTHER, 1.0, 0.0, self.losses["disc"], dz[B:], True)
+        elif kind:
             z = ctx_d["z_pr"]
             ops.gan_heads_loss(p[:B], z[:B], c1, kind, ops.GAN_ROLE_D_REAL, 1.0, 2.0, self.losses["disc"], dz[:B], False)
             ops.gan_heads_loss(p[B:], z[B:], None, kind, ops.GAN_ROLE_D_FAKE, 1.0, 0.0, self.losses["disc"], dz[B:], True)
@@ -246,12 +268,25 @@ class EagerTrainer:
         if self.r1_step(batch_no):
             # disc_loss += (r1_gamma r1_interval / 2) mean_b |d logit(x_b) / d x_b|^2 over the real rows D read (under diff_augment the
             # augmented rows, kept from above: no new draw); its weight gradients are added to the disc tape's before the all-reduce
-            D.r1_penalty(x_real, self.r1["weight"], self.losses["disc"], self.losses["r1"], train_range=rng_d)
+            if self.r2 is None:
+                D.r1_penalty(x_real, self.r1["weight"], self.losses["disc"], self.losses["r1"], train_range=rng_d)
+            elif self.r12_joint:   # R1 + R2: one pass over the 2B rows D read, a weight per half
+                D.r12_penalty(x_all, self.r1["weight"], self.r2["weight"], self.losses["disc"], self.losses["r1"], self.losses["r2"],
+                              train_range=rng_d)
+            else:   # the same as two B-row passes: what scripts/bench_rel.py measures the joint pass against
+                D.r1_penalty(x_real, self.r1["weight"], self.losses["disc"], self.losses["r1"], train_range=rng_d)
+                D.r1_penalty(x_all[B:], self.r2["weight"], self.losses["disc"], self.losses["r2"], train_range=rng_d)
+        elif self.r2_step(batch_no):
+            # R2 alone: R1's pass on the fake rows D read, a constant on this tape
+            D.r1_penalty(x_all[B:], self.r2["weight"], self.losses["disc"], self.losses["r2"], train_range=rng_d)
         self.sync.launch("D", self.store, *self.store.model_range("D", *rng_d))
 
         # ---- gen tape (eager_trainer.py:140,149): BCE(.98,fake_pr) + BCE(c2,fake_c) + l1*mean|img2-fake|
         dz_g = torch.empty(B, 1 + c, dtype=torch.float32, device=self.device)
-        if kind:
+        if rel:   # f0(z_f - z_r), differentiated with respect to z_f alone: z_r is a constant of this tape
+            ops.pair_heads_loss(p[B:], ctx_d["z_pr"][B:], ctx_d["z_pr"][:B], c2, kind, ops.REL_SIDE_SELF, 1.0, 1.0, self.losses["gen"],
+                                dz_g, False)
+        elif kind:
             ops.gan_heads_loss(p[B:], ctx_d["z_pr"][B:], c2, kind, ops.GAN_ROLE_G, 1.0, 1.0, self.losses["gen"], dz_g, False)
         else:
             ops.bce_heads_loss(p[B:], c2, soft(1.0), 1.0, 1.0, self.losses["gen"], dz_g, False)
@@ -287,7 +322,10 @@ class EagerTrainer:
             else:
                 p_a = D.forward_packed(adj_image, ctx_d2, keep_maps=False, top_only=True, drop=drop[2], **lk)
             dz_a = torch.empty(2 * B, 1 + c, dtype=torch.float32, device=self.device)
-            if kind:
+            if rel:   # f0(z_a[i] - z_r[i mod B]) over the Adjuster's 2B rows against the real logits of slot 0
+                ops.pair_heads_loss(p_a, ctx_d2["z_pr"], ctx_d["z_pr"][:B], adj_t_cond, kind, ops.REL_SIDE_SELF, 1.0, 1.0,
+                                    self.losses["adj"], dz_a, False)
+            elif kind:
                 ops.gan_heads_loss(p_a, ctx_d2["z_pr"], adj_t_cond, kind, ops.GAN_ROLE_G, 1.0, 1.0, self.losses["adj"], dz_a, False)
             else:
                 ops.bce_heads_loss(p_a, adj_t_cond, soft(1.0), 1.0, 1.0, self.losses["adj"], dz_a, False)
@@ -428,12 +466,16 @@ class EagerTrainer:
         """Whether this step carries the R1 penalty: stateless and resumable, like the partition steps."""
         return self.r1 is not None and batch_no % self.r1["interval"] == 0
 
+    def r2_step(self, batch_no: int) -> bool:
+        """Whether this step carries the R2 penalty: R1's schedule."""
+        return self.r2 is not None and batch_no % self.r2["interval"] == 0
+
     def step_kind(self, batch_no: int):
-        """Steps with the same kind enqueue the same kernels on the same shapes: (partition group or -1, Adjuster on, R1 penalty step;
-        the last is constant with r1_gamma == 0)."""
+        """Steps with the same kind enqueue the same kernels on the same shapes: (partition group or -1, Adjuster on, a penalty step
+        — R1, R2 or both, which share a schedule; the last is constant with r1_gamma == 0 and r2_gamma == 0)."""
         a = self.args
         part = (batch_no // (a.partition_interval + 1)) % 3 if (a.use_partition and batch_no % (a.partition_interval + 1) == 0) else -1
-        return part, bool(a.train_adj and batch_no > 10), self.r1_step(batch_no)
+        return part, bool(a.train_adj and batch_no > 10), self.r1_step(batch_no) or self.r2_step(batch_no)
 
     def graph_step(self, batch_no: int, inp: Dict[str, torch.Tensor]):
         """train_step_from_inputs through a captured HIP graph, one graph per step kind (full step, the three partition
@@ -642,6 +684,8 @@ class EagerTrainer:
                     la = float(result[5]) if result[5] is not None else float("nan")
                     aug_p = "" if self.ada is None else f" AugP {float(self.ada_p()):.4f}"   # read where the losses are: no sync of its own
                     r1 = "" if self.r1 is None else f" R1 {float(self.losses['r1']):.4f}"   # the term of the most recent penalty step
+                    if self.r2 is not None:
+                        r1 += f" R2 {float(self.losses['r2']):.4f}"
                     print(f"  [{seen}] LossG {lg:.4f} LossD {ld:.4f} LossA {la:.4f}{r1}{aug_p}")
                 if b % a.freq_test == 0 and io and self.test_cond is not None:
                     self.predict(self.test_noise, self.test_cond, self.test_image,

@@ -705,6 +705,15 @@ class Discriminator(_Module):
         driven by the injected adjoints alone.  Returns r2 [B]."""
         return self._logit_penalty(ops.r1_seed, image, weight, loss, r1_loss, train_range)
 
+    def r12_penalty(self, image, w_real: float, w_fake: float, loss=None, r1_loss=None, r2_loss=None, train_range=None):
+        """R1 + R2 of this project in ONE pass: image = the whole [2B,H,W,C] batch D read, rows [0,B) its real half
+        (weight w_real), rows [B,2B) its fake half (w_fake), a constant on this tape.  r1_penalty's pass at 2B rows with a seed that
+        weighs the halves apart: loss = (loss + r1) + r2, r1_loss = r1, r2_loss = r2, term_h = (w_h / 2) mean over the half's rows of
+        |d logit / d image_b|^2.  The weight gradients of both terms are ADDED to the gradient views, as r1_penalty's.  Returns r2 [2B]."""
+        def seed(g, _weight, loss_, _term):
+            return ops.r12_seed(g, w_real, w_fake, loss_, r1_loss, r2_loss)
+        return self._logit_penalty(seed, image, None, loss, None, train_range)
+
     def _logit_penalty(self, seed, image, weight, loss, term_loss, train_range):
         """The reverse-over-reverse pass of a penalty on the image gradient of the logit; `seed` (ops.r1_seed: |g|^2, or ops.gp_seed:
         (|g| - 1)^2) turns that gradient into the term, the adjoint u0 and the per-row value it returns."""

@@ -1630,3 +1630,44 @@ def r1_heads_colsum(u, dwpr):
     ws = workspace(int(lib.lgr_r1_colsum_workspace_bytes(B, K)), u.device, "r1")
     check(lib.lgr_r1_heads_colsum(_p(u), _p(dwpr), _p(ws), ws.numel(), B, K, _stream()), "lgr_r1_heads_colsum")
     return dwpr
+
+
+# ------------------------------------------------------------------ relativistic pairing + R2 (objective.hip, r1.hip; include/littlegan_rel.h)
+REL_SIDE_SELF, REL_SIDE_OTHER = 0, 1
+
+
+def pair_heads_loss(p, z, z_ref, t_c, kind, side, w_pr, w_c, loss, dz, accumulate):
+    """gan_heads_loss with the real / fake term taken on a pair of logits: t = z - z_ref (side 0, SELF: loss and gradient) or z_ref - z
+    (side 1, OTHER: the gradient with respect to z alone, nothing added to the loss); z [n], z_ref [m] with n % m == 0, row i pairs with
+    z_ref[i mod m]; kind 1 logistic, 2 hinge, 3 lsgan, each its role-0 function.  The attribute term (t_c, w_c) is bce_heads_loss's."""
+    n, J = p.shape
+    _chk(p, name="p")
+    _chk(z, (n,), "z")
+    _chk(z_ref, name="z_ref")
+    _chk(dz, (n, J), "dz")
+    _chk(loss, (1,), "loss")
+    if t_c is not None:
+        _chk(t_c, (n, J - 1), "t_c")
+    check(_lib.load().lgrel_pair_heads_loss_fwd_bwd(_p(p), _p(z), _p(z_ref), _p(t_c), int(kind), int(side), float(w_pr), float(w_c),
+                                                    _p(loss), _p(dz), n, int(z_ref.numel()), J - 1, int(accumulate), _stream()),
+          "lgrel_pair_heads_loss_fwd_bwd")
+
+
+def r12_seed(g, w_real, w_fake, loss=None, r1_loss=None, r2_loss=None):
+    """r1_seed over g [2B, ...] with a weight per half: -> (u0 = (w_half / B) g, r2 [2B] = |g_b|^2); r1_loss = the real half's term,
+    r2_loss = the fake half's, loss = (loss + r1 term) + r2 term.  The bits of two r1_seed calls on the halves."""
+    _chk(g, name="g")
+    if g.shape[0] % 2:
+        raise ValueError(f"r12_seed: g must hold the two halves of a batch, got {g.shape[0]} rows")
+    B = g.shape[0] // 2
+    L = g.numel() // (2 * B)
+    for t, nm in ((loss, "loss"), (r1_loss, "r1_loss"), (r2_loss, "r2_loss")):
+        if t is not None:
+            _chk(t, (1,), nm)
+    u0 = torch.empty_like(g)
+    r2 = torch.empty(2 * B, dtype=torch.float32, device=g.device)
+    lib = _lib.load()
+    ws = workspace(int(lib.lgrel_r12_workspace_bytes(B, L)), g.device, "r1")
+    check(lib.lgrel_r12_seed(_p(g), _p(u0), _p(r2), _p(loss), _p(r1_loss), _p(r2_loss), float(w_real), float(w_fake), _p(ws), ws.numel(),
+                             B, L, _stream()), "lgrel_r12_seed")
+    return u0, r2
