@@ -180,6 +180,16 @@ REL_SIGNATURES = {
     "lgrel_r12_seed": (I, [P, P, P, P, P, P, F, F, P, Z, I, L, P]),
 }
 
+# include/littlegan_sched.h: the learning-rate schedule on the device and the Adam passes that read their rate from its state (sched.hip,
+# loss_optim.hip).  A table of its own for the same reason; load() binds it too (tests/test_lr_schedule_cpu.py holds it to
+# its header)
+SCHED_SIGNATURES = {
+    "lgsch_init": (I, [P, I, P]),
+    "lgsch_step": (I, [P, I, I, I, F, F, F, F, P]),
+    "lgsch_clip_adam_update": (I, [P, P, P, P, L, P, P, F, F, F, F, F, P]),
+    "lgsch_clip_adam_ema_update": (I, [P, P, P, P, P, L, L, L, P, P, P, F, F, F, F, F, F, P]),
+}
+
 
 class LittleGanHipError(RuntimeError):
     pass
@@ -213,7 +223,8 @@ def load():
     # before torch, the system runtime it links against would come in as a SECOND runtime and its kernels would see no device.
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name, (res, args) in list(SIGNATURES.items()) + list(GEOM_SIGNATURES.items()) + list(REL_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(GEOM_SIGNATURES.items()) + list(REL_SIGNATURES.items()) \
+            + list(SCHED_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -21,7 +21,12 @@ use_gp, which then penalises the logit),
 relativistic (bool: the real / fake terms become f0(D(real) - D(fake)) per pair of rows, f0 the D-real function of gan_loss, which must be
 logistic, hinge or lsgan) / r2_gamma (the R1 penalty's twin on the fake rows D read, on R1's schedule: r1_interval, weight
 r2_gamma r1_interval; 0 = off; excludes use_gp and dropout_train; with r1_gamma also on, one pass over the 2B-row batch carries both;
-DESIGN.md §27)."""
+DESIGN.md §27),
+lr_g / lr_d / lr_adj (base learning rate of the Generator's, the Discriminator's and the Adjuster's optimizer; null = lr) / lr_schedule
+("constant" | "linear" | "cosine") / lr_warmup_steps / lr_decay_steps / lr_final_ratio (a factor s(k) on all three rates, k the number of
+training steps taken over the whole run: (k + 1) / lr_warmup_steps during warm-up, then a linear or cosine decay over lr_decay_steps from 1
+to lr_final_ratio, where it stays; it is computed on the device from a counter on the device, so replayed graphs follow it, and the
+counter is part of the checkpoint; constant without warm-up = the step as it was)."""
 import json
 import os
 from argparse import ArgumentParser
@@ -117,6 +122,13 @@ DEFAULTS = {
     # r1_interval-th step disc_loss += (r2_gamma r1_interval / 2) mean_b |d logit(x_b) / d x_b|^2.  0 = off.  With r1_gamma also on, both
     # penalties are one reverse-over-reverse pass over the 2B-row batch.  Excludes use_gp and dropout_train.
     'r2_gamma': 0.0,
+    # learning rates per network and their schedule (the reference has one constant lr).  lr_g / lr_d / lr_adj: the base
+    # rate of that optimizer, null = lr.  lr_schedule: "constant", "linear" or "cosine"; with k the number of training steps taken so far
+    # (over the whole run, kept in the checkpoint) every rate is its base times s(k) = up(k) d(k): up = (k + 1) / lr_warmup_steps while
+    # k < lr_warmup_steps, else 1; d falls from 1 to lr_final_ratio over the lr_decay_steps steps after warm-up (a straight line, or half
+    # a cosine) and stays there.  lr_decay_steps is required by linear / cosine and refused with constant.  s is computed on the device.
+    'lr_g': None, 'lr_d': None, 'lr_adj': None, 'lr_schedule': 'constant', 'lr_warmup_steps': 0, 'lr_decay_steps': None,
+    'lr_final_ratio': 0.0,
 }
 
 GAN_LOSS_KINDS = {"bce": 0, "logistic": 1, "hinge": 2, "lsgan": 3, "wgan": 4}   # the `kind` of lgo_gan_heads_loss_fwd_bwd; 0 = not its
@@ -251,6 +263,86 @@ def relativistic_setting(relativistic=False, gan_loss="bce"):
     return relativistic
 
 
+LR_SCHEDULE_KINDS = {"constant": 0, "linear": 1, "cosine": 2}   # the `kind` of lgsch_step
+
+
+def lr_schedule_settings(lr, lr_g=None, lr_d=None, lr_adj=None, lr_schedule="constant", lr_warmup_steps=0, lr_decay_steps=None,
+                         lr_final_ratio=0.0):
+    """The keys of the learning rates and their schedule, validated: a dict {lr_g, lr_d, lr_adj (the base rates as the
+    fp32 values they are used at; a null key takes lr), schedule, kind (of lgsch_step), warmup, decay (None under constant), final_ratio
+    (its fp32 value), device}.  device: the rates are computed on the device from its step counter — true exactly when lr_schedule is not
+    "constant" or lr_warmup_steps > 0; false = the rates are the launch scalars they always were.  Raises ValueError for a rate that is no
+    finite number > 0 fitting fp32 (bools and strings refused; lr itself may be 0, which freezes the weights, as long as nothing is
+    scheduled), a schedule that is not one of the three names, lr_warmup_steps no integer >= 0, lr_decay_steps no integer >= 1, missing
+    under linear / cosine or given under constant, and lr_final_ratio outside [0, 1]."""
+    import math
+    import numpy as np
+
+    def number(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+        return float(v)
+
+    def rate(name, v):
+        with np.errstate(over="ignore"):
+            r = float(np.float32(number(name, v)))
+        if not 0.0 < r < float("inf"):
+            raise ValueError(f"{name} must be a finite number > 0 that fits fp32, got {v!r}")
+        return r
+
+    if not isinstance(lr_schedule, str) or lr_schedule not in LR_SCHEDULE_KINDS:
+        raise ValueError(f"lr_schedule must be one of {', '.join(LR_SCHEDULE_KINDS)} (a string), got {lr_schedule!r}")
+    if isinstance(lr_warmup_steps, bool) or not isinstance(lr_warmup_steps, int) or not 0 <= lr_warmup_steps < 2 ** 31:
+        raise ValueError(f"lr_warmup_steps must be an integer >= 0 (below 2^31), got {lr_warmup_steps!r}")
+    if lr_decay_steps is not None and (isinstance(lr_decay_steps, bool) or not isinstance(lr_decay_steps, int)
+                                       or not 1 <= lr_decay_steps < 2 ** 31):
+        raise ValueError(f"lr_decay_steps must be null or an integer >= 1 (below 2^31), got {lr_decay_steps!r}")
+    if lr_schedule == "constant" and lr_decay_steps is not None:
+        raise ValueError(f"lr_decay_steps = {lr_decay_steps!r} needs lr_schedule linear or cosine: a constant schedule decays nothing")
+    if lr_schedule != "constant" and lr_decay_steps is None:
+        raise ValueError(f"lr_schedule {lr_schedule!r} needs lr_decay_steps (an integer >= 1)")
+    if not 0.0 <= number("lr_final_ratio", lr_final_ratio) <= 1.0:
+        raise ValueError(f"lr_final_ratio must satisfy 0 <= lr_final_ratio <= 1, got {lr_final_ratio!r}")
+    device = lr_schedule != "constant" or lr_warmup_steps > 0
+    base = number("lr", lr)
+    with np.errstate(over="ignore"):
+        base = float(np.float32(base))
+    if not 0.0 <= base < float("inf"):
+        raise ValueError(f"lr must be a finite number >= 0 that fits fp32, got {lr!r}")
+    rates = {}
+    for name, v in (("lr_g", lr_g), ("lr_d", lr_d), ("lr_adj", lr_adj)):
+        rates[name] = base if v is None else rate(name, v)
+        if device and not rates[name] > 0.0:
+            raise ValueError(f"lr must be > 0 under a schedule or warm-up ({name} is null and takes lr = {lr!r})")
+    return dict(rates, schedule=lr_schedule, kind=LR_SCHEDULE_KINDS[lr_schedule], warmup=int(lr_warmup_steps),
+                decay=None if lr_decay_steps is None else int(lr_decay_steps), final_ratio=float(np.float32(lr_final_ratio)), device=device)
+
+
+def lr_factor(k, settings):
+    """s(k) of DESIGN.md §28 as the device computes it (lgsch_step), restated in numpy: fp64 throughout, one conversion to fp32.
+    k: training steps taken so far; settings: what lr_schedule_settings returned.  -> numpy.float32.  For the log and the tests."""
+    import numpy as np
+    f64 = np.float64
+    k, W, N = int(k), settings["warmup"], settings["decay"]
+    r = f64(np.float32(settings["final_ratio"]))
+    up = f64(k + 1) / f64(W) if k < W else f64(1.0)
+    d = f64(1.0)
+    if settings["schedule"] != "constant":
+        t = f64(0.0) if k < W else min(f64(k - W) / f64(N), f64(1.0))
+        if settings["schedule"] == "linear":
+            d = f64(1.0) - (f64(1.0) - r) * t
+        else:
+            d = r + (f64(1.0) - r) * f64(0.5) * (f64(1.0) + np.cos(f64(np.pi) * t))
+    return np.float32(up * d)
+
+
+def lr_rates(k, settings):
+    """The three rates (G, D, A) of step k: float32(base) * s(k), one fp32 multiply each, as numpy.float32."""
+    import numpy as np
+    s = lr_factor(k, settings)
+    return tuple(np.float32(settings[m]) * s for m in ("lr_g", "lr_d", "lr_adj"))
+
+
 METRIC_NAMES = ("fid", "kid", "prdc")
 
 
@@ -300,6 +392,8 @@ class Arg:
         gan_loss_kind(self.gan_loss, bool(self.use_gp))   # a misspelt objective fails here, and so does wgan without its penalty
         relativistic_setting(self.relativistic, self.gan_loss)
         r2_settings(self.r2_gamma, self.r1_interval)
+        lr_schedule_settings(self.lr, self.lr_g, self.lr_d, self.lr_adj, self.lr_schedule, self.lr_warmup_steps, self.lr_decay_steps,
+                             self.lr_final_ratio)   # a misspelt schedule fails here, not at the first step
         self.evaluate_metrics = metric_list(self.evaluate_metrics)   # a misspelt metric fails here, not after the sampling run
         if int(self.kid_subsets) < 0 or int(self.kid_subset_size) < 2 or not 1 <= int(self.prdc_k) <= 15:
             raise ValueError("need kid_subsets >= 0, kid_subset_size >= 2 and 1 <= prdc_k <= 15")

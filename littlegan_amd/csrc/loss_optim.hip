@@ -10,6 +10,7 @@
 //               (eager_trainer.py:28-30,164-168): lr_t = lr*sqrt(1-b2^t)/(1-b1^t), eps outside sqrt,
 //               one beta-power pair per optimizer kept on the device so the step replays as a graph.
 #include "lg_internal.h"
+#include "../../include/littlegan_sched.h"
 
 #define LG_BCE_EPS 1e-7f
 
@@ -93,6 +94,20 @@ __device__ __forceinline__ float clip_adam_element(float w, float g, float& m, f
   return w - lr_t * mv / (sqrtf(vv) + eps);
 }
 
+// The grid-stride pass of clip + Adam over n elements at the bias-corrected rate lr_t: the body of clip_adam_kernel and of its twin that
+// reads the rate from device memory (littlegan_sched.h), so that both are the same instructions after the one line that forms lr_t.
+// (i0 and stride come from the kernel: with blockDim read in here the compiler fetches it another way than it did for clip_adam_kernel
+// before the pass was taken out, and that kernel's instructions are to stay what they were.)
+__device__ __forceinline__ void clip_adam_pass(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
+                                               float* __restrict__ v, long long n, long long i0, long long stride, float lr_t,
+                                               float b1, float b2, float eps, float clip, float gscale) {
+  for (long long i = i0; i < n; i += stride) {
+    float mv = m[i], vv = v[i];
+    w[i] = clip_adam_element(w[i], g[i], mv, vv, lr_t, b1, b2, eps, clip, gscale);
+    m[i] = mv; v[i] = vv;
+  }
+}
+
 // state = {beta1_power, beta2_power}
 __global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ w, const float* __restrict__ g,
                                                         float* __restrict__ m, float* __restrict__ v, long long n,
@@ -100,11 +115,23 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ w, c
                                                         float eps, float clip, float gscale) {
   const float lr_t = lr * sqrtf(1.f - state[1]) / (1.f - state[0]);
   const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float mv = m[i], vv = v[i];
-    w[i] = clip_adam_element(w[i], g[i], mv, vv, lr_t, b1, b2, eps, clip, gscale);
-    m[i] = mv; v[i] = vv;
-  }
+  clip_adam_pass(w, g, m, v, n, (long long)blockIdx.x * blockDim.x + threadIdx.x, stride, lr_t, b1, b2, eps, clip, gscale);
+}
+
+// ... with the rate of the present step read from the schedule's state: lr[0] where the launch scalar stands above
+__global__ __launch_bounds__(256) void clip_adam_lrp_kernel(float* __restrict__ w, const float* __restrict__ g,
+                                                            float* __restrict__ m, float* __restrict__ v, long long n,
+                                                            const float* __restrict__ state, const float* __restrict__ lr, float b1,
+                                                            float b2, float eps, float clip, float gscale) {
+  const float lr_t = lr[0] * sqrtf(1.f - state[1]) / (1.f - state[0]);
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  clip_adam_pass(w, g, m, v, n, (long long)blockIdx.x * blockDim.x + threadIdx.x, stride, lr_t, b1, b2, eps, clip, gscale);
+}
+
+// 1 - d_t of the weight average below, from the device counter of averages taken
+__device__ __forceinline__ float ema_one_minus_decay(const int* __restrict__ ema_state, float decay) {
+  const float kf = (float)ema_state[0];
+  return 1.f - fminf(decay, (1.f + kf) / (10.f + kf));
 }
 
 // clip + Adam on the 4-float groups [lo4, hi4) of one model's weights, and the weight average on ALL of its n4 groups:
@@ -112,17 +139,12 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ w, c
 // (tf.train.ExponentialMovingAverage(decay, num_updates)).  d_t is computed here, from the device counter: a captured graph bakes
 // launch scalars in, a replayed step still walks the ramp.  Outside [lo4, hi4) nothing but w and ema is touched: on a partition
 // step the gradients there are stale and were not all-reduced.  16-byte accesses; the caller guarantees the alignment.
-__global__ __launch_bounds__(256) void clip_adam_ema_kernel(float* __restrict__ w, const float* __restrict__ g,
-                                                            float* __restrict__ m, float* __restrict__ v,
-                                                            float* __restrict__ ema, long long n4, long long lo4, long long hi4,
-                                                            const float* __restrict__ state, const int* __restrict__ ema_state,
-                                                            float lr, float b1, float b2, float eps, float clip, float gscale,
-                                                            float decay) {
-  const float lr_t = lr * sqrtf(1.f - state[1]) / (1.f - state[0]);
-  const float kf = (float)ema_state[0];
-  const float omd = 1.f - fminf(decay, (1.f + kf) / (10.f + kf));
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+// (The pass of clip_adam_ema_kernel and of its twin that reads the rate from device memory; i0, stride as for clip_adam_pass.)
+__device__ __forceinline__ void clip_adam_ema_pass(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, float* __restrict__ ema, long long n4, long long lo4,
+                                                   long long hi4, long long i0, long long stride, float omd, float lr_t, float b1,
+                                                   float b2, float eps, float clip, float gscale) {
+  for (long long i = i0; i < n4; i += stride) {
     f32x4 wv = *reinterpret_cast<const f32x4*>(w + i * 4);
     if (i >= lo4 && i < hi4) {
       const f32x4 gv = *reinterpret_cast<const f32x4*>(g + i * 4);
@@ -143,6 +165,33 @@ __global__ __launch_bounds__(256) void clip_adam_ema_kernel(float* __restrict__ 
     for (int k = 0; k < 4; ++k) ev[k] -= omd * (ev[k] - wv[k]);
     *reinterpret_cast<f32x4*>(ema + i * 4) = ev;
   }
+}
+
+__global__ __launch_bounds__(256) void clip_adam_ema_kernel(float* __restrict__ w, const float* __restrict__ g,
+                                                            float* __restrict__ m, float* __restrict__ v,
+                                                            float* __restrict__ ema, long long n4, long long lo4, long long hi4,
+                                                            const float* __restrict__ state, const int* __restrict__ ema_state,
+                                                            float lr, float b1, float b2, float eps, float clip, float gscale,
+                                                            float decay) {
+  const float lr_t = lr * sqrtf(1.f - state[1]) / (1.f - state[0]);
+  const float omd = ema_one_minus_decay(ema_state, decay);
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  clip_adam_ema_pass(w, g, m, v, ema, n4, lo4, hi4, (long long)blockIdx.x * blockDim.x + threadIdx.x, stride, omd, lr_t, b1, b2, eps,
+                     clip, gscale);
+}
+
+// ... with the rate of the present step read from the schedule's state
+__global__ __launch_bounds__(256) void clip_adam_ema_lrp_kernel(float* __restrict__ w, const float* __restrict__ g,
+                                                                float* __restrict__ m, float* __restrict__ v,
+                                                                float* __restrict__ ema, long long n4, long long lo4, long long hi4,
+                                                                const float* __restrict__ state, const int* __restrict__ ema_state,
+                                                                const float* __restrict__ lr, float b1, float b2, float eps, float clip,
+                                                                float gscale, float decay) {
+  const float lr_t = lr[0] * sqrtf(1.f - state[1]) / (1.f - state[0]);
+  const float omd = ema_one_minus_decay(ema_state, decay);
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  clip_adam_ema_pass(w, g, m, v, ema, n4, lo4, hi4, (long long)blockIdx.x * blockDim.x + threadIdx.x, stride, omd, lr_t, b1, b2, eps,
+                     clip, gscale);
 }
 
 __global__ void adam_advance_kernel(float* state, float b1, float b2) {
@@ -242,6 +291,42 @@ extern "C" int lg_clip_adam_ema_update(float* w, const float* g, float* m, float
   hipLaunchKernelGGL(clip_adam_ema_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, w, g, m, v, ema, n4, lo / 4, hi / 4,
                      adam_state, ema_state, lr, b1, b2, eps, clip, gscale, decay);
   LG_CHECK_LAUNCH("lg_clip_adam_ema_update");
+  return LG_OK;
+}
+
+// lg_clip_adam_update with the rate in device memory (include/littlegan_sched.h): the same grid, the same pass
+extern "C" int lgsch_clip_adam_update(float* w, const float* g, float* m, float* v, long long n, const float* state, const float* lr,
+                                      float b1, float b2, float eps, float clip, float gscale, void* stream) {
+  LG_CHECK_ARG(w && g && m && v && state && lr, "lgsch_clip_adam_update: null pointer");
+  LG_CHECK_ARG(((uintptr_t)lr & 3) == 0, "lgsch_clip_adam_update: lr must be 4-byte aligned");
+  LG_CHECK_ARG(n > 0, "lgsch_clip_adam_update: n=%lld", n);
+  long long nb = (n + 255) / 256;
+  if (nb > 4096) nb = 4096;
+  hipLaunchKernelGGL(clip_adam_lrp_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, w, g, m, v, n, state, lr, b1, b2, eps,
+                     clip, gscale);
+  LG_CHECK_LAUNCH("lgsch_clip_adam_update");
+  lg_note_kernel("clip_adam_lrp_kernel");
+  return LG_OK;
+}
+
+// lg_clip_adam_ema_update with the rate in device memory
+extern "C" int lgsch_clip_adam_ema_update(float* w, const float* g, float* m, float* v, float* ema, long long n, long long lo,
+                                          long long hi, const float* adam_state, const int* ema_state, const float* lr, float b1,
+                                          float b2, float eps, float clip, float gscale, float decay, void* stream) {
+  LG_CHECK_ARG(w && g && m && v && ema && adam_state && ema_state && lr, "lgsch_clip_adam_ema_update: null pointer");
+  LG_CHECK_ARG(n > 0 && n % 4 == 0, "lgsch_clip_adam_ema_update: n=%lld must be a positive multiple of 4", n);
+  LG_CHECK_ARG(lo >= 0 && lo <= hi && hi <= n && lo % 4 == 0 && hi % 4 == 0,
+               "lgsch_clip_adam_ema_update: need 0 <= lo <= hi <= n, both multiples of 4 (lo=%lld hi=%lld n=%lld)", lo, hi, n);
+  LG_CHECK_ARG(((uintptr_t)w | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) % 16 == 0 && ((uintptr_t)lr & 3) == 0,
+               "lgsch_clip_adam_ema_update: w, g, m, v, ema must be 16-byte, lr 4-byte aligned");
+  LG_CHECK_ARG(decay >= 0.f && decay < 1.f, "lgsch_clip_adam_ema_update: decay=%g outside [0, 1)", (double)decay);
+  const long long n4 = n / 4;
+  long long nb = (n4 + 255) / 256;
+  if (nb > 4096) nb = 4096;
+  hipLaunchKernelGGL(clip_adam_ema_lrp_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, w, g, m, v, ema, n4, lo / 4, hi / 4,
+                     adam_state, ema_state, lr, b1, b2, eps, clip, gscale, decay);
+  LG_CHECK_LAUNCH("lgsch_clip_adam_ema_update");
+  lg_note_kernel("clip_adam_ema_lrp_kernel");
   return LG_OK;
 }
 

@@ -17,7 +17,8 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from .config import ada_settings, diff_augment_bits, gan_loss_kind, geom_augment_bits, r1_settings, r2_settings, relativistic_setting
+from .config import (ada_settings, diff_augment_bits, gan_loss_kind, geom_augment_bits, lr_schedule_settings, r1_settings, r2_settings,
+                     relativistic_setting)
 from .dist import GradSync
 from .model import Adjuster, Discriminator, Generator, ParamStore
 from .utils import save_image, soft
@@ -135,8 +136,13 @@ class EagerTrainer:
         if self.ema_decay > 0.0:
             self.store.enable_ema()
         # tf.compat.v1.train.AdamOptimizer x3 (eager_trainer.py:28-30): {beta1_power, beta2_power} per optimizer
-        self.opt_cfg = {"G": (args.lr, args.beta_1, args.beta_2), "D": (args.lr, args.beta_1, args.beta_2),
-                        "A": (args.lr, 0.9, 0.999)}
+        # learning rates per network and their schedule (the reference has one constant lr): the base rates go where lr
+        # went; lr_sched["device"] false = they are the launch scalars of the Adam passes, nothing else changes
+        self.lr_sched = lr_schedule_settings(args.lr, *(getattr(args, k, d) for k, d in (
+            ("lr_g", None), ("lr_d", None), ("lr_adj", None), ("lr_schedule", "constant"), ("lr_warmup_steps", 0), ("lr_decay_steps", None),
+            ("lr_final_ratio", 0.0))))
+        self.opt_cfg = {"G": (self.lr_sched["lr_g"], args.beta_1, args.beta_2), "D": (self.lr_sched["lr_d"], args.beta_1, args.beta_2),
+                        "A": (self.lr_sched["lr_adj"], 0.9, 0.999)}
         self.opt_state = {m: torch.tensor([b1, b2], dtype=torch.float32, device=self.device)
                           for m, (_, b1, b2) in self.opt_cfg.items()}
         self.losses = {k: torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -152,6 +158,9 @@ class EagerTrainer:
             # word on the host, which only needs it to place the data-parallel all-reduce of the counters (_ada_control)
             self.ada_state = ops.ada_init(self.ada["p0"], device=self.device)
             self._ada_steps, self._ada_due, self._ada_ticked = 0, False, False
+        # {k, s, rate of G, D, A, 0, 0, 0} on the device (lgsch_init: written from a launch scalar), advanced by the first launch of every
+        # step; None = the rates are constants.  No host mirror: nothing on the host depends on k
+        self.lr_state = ops.sched_init(0, device=self.device) if self.lr_sched["device"] else None
         self._init_dir()
         # eager_trainer.py:36-43: restore the newest checkpoint (weights, the three optimizers' slots and beta powers)
         # and the epoch from status.json when args.restore is set
@@ -217,6 +226,9 @@ class EagerTrainer:
                   and tuple(new_image.shape) == tuple(img1.shape) and new_image.is_contiguous()):
             raise ValueError("train_step_from_inputs: inp['disc_input'] must be a contiguous fp32 [2B, H, W, C] buffer whose first B "
                              "images ARE inp['new_image'] (a view of it)")
+        if self.lr_state is not None:   # the step's first launch: s(k) and the three rates of this step, then k += 1
+            ls = self.lr_sched
+            ops.sched_step(self.lr_state, ls["kind"], ls["warmup"], ls["decay"], ls["final_ratio"], *(self.opt_cfg[m][0] for m in "GDA"))
         fake = G([noise, c2], ctx_g, out=d_in[B:])
         ctx_d: dict = {}
         run_adj = bool(a.train_adj and batch_no > 10)
@@ -402,9 +414,16 @@ class EagerTrainer:
         synchronisation; float() of it waits like float() of a loss), None when every component is always applied."""
         return None if self.ada is None else self.ada_state[:1]
 
+    def lr_now(self):
+        """The rates of G, D, A of the most recent step under a schedule or warm-up: the 3-element device view of the state's words 2..4
+        (no synchronisation; float() of an element waits like float() of a loss), None when the rates are constants (opt_cfg)."""
+        return None if self.lr_state is None else self.lr_state[2:5]
+
     def _apply_optimizers(self, batch_no: int, run_adj: bool):
         a, st = self.args, self.store
         gscale = 1.0 / self.sync.world_size
+        # under a schedule the Adam passes read their rate from the state the step's first launch wrote (1-element views of it)
+        lr_view = None if self.lr_state is None else {m: self.lr_state[i:i + 1] for m, i in (("G", 2), ("D", 3), ("A", 4))}
         for m in self.adam_order:
             trained = m != "A" or run_adj
             if not trained and st.ema is None:
@@ -415,7 +434,10 @@ class EagerTrainer:
             s, e = st.model_range(m, lo, hi)
             if trained:
                 self.sync.wait(m)
-            if st.ema is None:
+            if st.ema is None and lr_view is not None:
+                ops.sched_clip_adam_update(st.flat[s:e], st.grad[s:e], st.m[s:e], st.v[s:e], self.opt_state[m], lr_view[m], b1, b2,
+                                           ADAM_EPS, clip, gscale)
+            elif st.ema is None:
                 ops.clip_adam_update(st.flat[s:e], st.grad[s:e], st.m[s:e], st.v[s:e], self.opt_state[m], lr, b1, b2,
                                      ADAM_EPS, clip, gscale)
             else:
@@ -423,8 +445,13 @@ class EagerTrainer:
                 # trained group only w and ema are read; an Adjuster that does not train this step gets the average alone (lo == hi)
                 s0, e0 = st.model_range(m)
                 t_lo, t_hi = (s - s0, e - s0) if trained else (0, 0)
-                ops.clip_adam_ema_update(st.flat[s0:e0], st.grad[s0:e0], st.m[s0:e0], st.v[s0:e0], st.ema[s0:e0], t_lo, t_hi,
-                                         self.opt_state[m], st.ema_updates, lr, b1, b2, ADAM_EPS, clip, gscale, self.ema_decay)
+                if lr_view is not None:
+                    ops.sched_clip_adam_ema_update(st.flat[s0:e0], st.grad[s0:e0], st.m[s0:e0], st.v[s0:e0], st.ema[s0:e0], t_lo, t_hi,
+                                                   self.opt_state[m], st.ema_updates, lr_view[m], b1, b2, ADAM_EPS, clip, gscale,
+                                                   self.ema_decay)
+                else:
+                    ops.clip_adam_ema_update(st.flat[s0:e0], st.grad[s0:e0], st.m[s0:e0], st.v[s0:e0], st.ema[s0:e0], t_lo, t_hi,
+                                             self.opt_state[m], st.ema_updates, lr, b1, b2, ADAM_EPS, clip, gscale, self.ema_decay)
             if trained:
                 ops.adam_advance(self.opt_state[m], b1, b2)
         if st.ema is not None:
@@ -686,7 +713,8 @@ class EagerTrainer:
                     r1 = "" if self.r1 is None else f" R1 {float(self.losses['r1']):.4f}"   # the term of the most recent penalty step
                     if self.r2 is not None:
                         r1 += f" R2 {float(self.losses['r2']):.4f}"
-                    print(f"  [{seen}] LossG {lg:.4f} LossD {ld:.4f} LossA {la:.4f}{r1}{aug_p}")
+                    lrs = "" if self.lr_state is None else " LR g/d/a " + "/".join(f"{x:.3e}" for x in self.lr_now().tolist())
+                    print(f"  [{seen}] LossG {lg:.4f} LossD {ld:.4f} LossA {la:.4f}{r1}{aug_p}{lrs}")
                 if b % a.freq_test == 0 and io and self.test_cond is not None:
                     self.predict(self.test_noise, self.test_cond, self.test_image,
                                  os.path.join(a.result_dir, "test", "gen", "%d-%d.jpg" % (e, b)),
@@ -825,6 +853,8 @@ class EagerTrainer:
             ck["ema"], ck["ema_updates"] = st.ema.detach().cpu(), int(st.ema_updates.item())
         if self.ada is not None:   # {p, sum, rows, steps} as its four 32-bit words (absent on the plain diff_augment path)
             ck["ada_state"] = self.ada_state.detach().cpu().view(torch.int32)
+        if self.lr_state is not None:   # the schedule's step counter (absent when the rates are constants)
+            ck["lr_sched_state"] = ops.sched_read(self.lr_state)[0]
         return ck
 
     def save_checkpoint(self, tag: str) -> str:
@@ -867,6 +897,11 @@ class EagerTrainer:
             if not (0.0 <= p <= 1.0 and int(ada_words[2]) >= 0 and int(ada_words[3]) >= 0):
                 raise ValueError(f"{path}: ada_state {ada_words.tolist()} is not a controller state (four words with 0 <= p <= 1, "
                                  f"rows >= 0, steps >= 0; p read as {p})")
+        lr_k = None
+        if self.lr_state is not None and "lr_sched_state" in ck:   # checked before anything is loaded, like the words above
+            lr_k = ck["lr_sched_state"]
+            if isinstance(lr_k, bool) or not isinstance(lr_k, int) or not 0 <= lr_k < 2 ** 31:
+                raise ValueError(f"{path}: lr_sched_state {lr_k!r} is not a step counter (one integer, 0 <= k < 2^31)")
         st.flat.copy_(ck["flat"])
         st.m.copy_(ck["adam_m"])
         st.v.copy_(ck["adam_v"])
@@ -886,6 +921,10 @@ class EagerTrainer:
                 self._ada_steps = int(ada_words[3])
             else:
                 print(f"{path}: no augmentation probability in this checkpoint; it starts from the configured {self.ada['p0']}")
+        if self.lr_state is not None:   # (a checkpoint's counter is ignored when this run schedules nothing)
+            if lr_k is None:
+                print(f"{path}: no learning-rate step counter in this checkpoint; the schedule starts at k = 0")
+            ops.sched_init(lr_k or 0, out=self.lr_state)
         st.bump()
 
     def export_model_checkpoint(self):

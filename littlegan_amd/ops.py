@@ -1671,3 +1671,70 @@ def r12_seed(g, w_real, w_fake, loss=None, r1_loss=None, r2_loss=None):
     check(lib.lgrel_r12_seed(_p(g), _p(u0), _p(r2), _p(loss), _p(r1_loss), _p(r2_loss), float(w_real), float(w_fake), _p(ws), ws.numel(),
                              B, L, _stream()), "lgrel_r12_seed")
     return u0, r2
+
+
+# ------------------------------------------------------------------ learning-rate schedule on the device (sched.hip, loss_optim.hip; include/littlegan_sched.h)
+SCHED_CONSTANT, SCHED_LINEAR, SCHED_COSINE = 0, 1, 2
+
+
+def _chk_sched(t, who):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (8,)):
+        raise ValueError(f"{who}: the schedule's state is a contiguous fp32 [8] CUDA tensor, got {t.dtype} {t.device} {tuple(t.shape)}")
+    return t
+
+
+def sched_init(k0=0, device="cuda", out=None):
+    """The schedule's state {k0, 0, 0, 0, 0, 0, 0, 0} (fp32 [8]: the int32 step counter, fp32 s, the rates of G, D, A, three reserved
+    words), written by a one-block kernel from a launch scalar: no host-to-device copy."""
+    if out is None:
+        out = torch.empty(8, dtype=torch.float32, device=device)
+    _chk_sched(out, "sched_init")
+    check(_lib.load().lgsch_init(_p(out), int(k0), _stream()), "lgsch_init")
+    return out
+
+
+def sched_step(state, kind, warmup, decay_steps, final_ratio, lr_g, lr_d, lr_a):
+    """One step of the schedule: state[1] = s(k), state[2:5] = the three base rates times s(k), then k += 1 (saturating).  kind 0
+    constant, 1 linear, 2 cosine; decay_steps None under constant."""
+    _chk_sched(state, "sched_step")
+    check(_lib.load().lgsch_step(_p(state), int(kind), int(warmup), 0 if decay_steps is None else int(decay_steps), float(final_ratio),
+                                 float(lr_g), float(lr_d), float(lr_a), _stream()), "lgsch_step")
+    return state
+
+
+def sched_read(state):
+    """(k, s, lr_g, lr_d, lr_a) on the host.  Synchronises: for logs, checkpoints and tests, not for the step."""
+    _chk_sched(state, "sched_read")
+    host = state.detach().cpu()
+    return (int(host.view(torch.int32)[0]),) + tuple(float(x) for x in host[1:5])
+
+
+def _chk_rate(lr):
+    if not (lr.is_cuda and lr.dtype == torch.float32 and lr.numel() == 1):
+        raise ValueError(f"lr: need a 1-element fp32 CUDA tensor, got {lr.dtype} {lr.device} numel={lr.numel()}")
+    return lr
+
+
+def sched_clip_adam_update(w, g, m, v, state, lr, b1, b2, eps, clip, gscale=1.0):
+    """clip_adam_update with the rate read on the device: lr is a 1-element fp32 tensor (a view of the schedule's state)."""
+    n = w.numel()
+    for t, nm in ((w, "w"), (g, "g"), (m, "m"), (v, "v")):
+        _chk(t, name=nm)
+        if t.numel() != n:
+            raise ValueError("sched_clip_adam_update: size mismatch")
+    check(_lib.load().lgsch_clip_adam_update(_p(w), _p(g), _p(m), _p(v), n, _p(state), _p(_chk_rate(lr)), float(b1), float(b2),
+                                             float(eps), float(clip), float(gscale), _stream()), "lgsch_clip_adam_update")
+
+
+def sched_clip_adam_ema_update(w, g, m, v, ema, lo, hi, state, ema_state, lr, b1, b2, eps, clip, gscale, decay):
+    """clip_adam_ema_update with the rate read on the device: lr is a 1-element fp32 tensor (a view of the schedule's state)."""
+    n = w.numel()
+    for t, nm in ((w, "w"), (g, "g"), (m, "m"), (v, "v"), (ema, "ema")):
+        _chk(t, name=nm)
+        if t.numel() != n:
+            raise ValueError("sched_clip_adam_ema_update: size mismatch")
+    _chk(state, (2,), "state")
+    _chk_counter(ema_state, "ema_state")
+    check(_lib.load().lgsch_clip_adam_ema_update(_p(w), _p(g), _p(m), _p(v), _p(ema), n, int(lo), int(hi), _p(state), _p(ema_state),
+                                                 _p(_chk_rate(lr)), float(b1), float(b2), float(eps), float(clip), float(gscale),
+                                                 float(decay), _stream()), "lgsch_clip_adam_ema_update")
