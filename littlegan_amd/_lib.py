@@ -190,6 +190,15 @@ SCHED_SIGNATURES = {
     "lgsch_clip_adam_ema_update": (I, [P, P, P, P, P, L, L, L, P, P, P, F, F, F, F, F, F, P]),
 }
 
+# include/littlegan_adj.h: the Adjuster's forward without its single-reader normalised maps (norm_rs.hip, conv_up3.hip).  A
+# table of its own for the same reason; load() binds it too (tests/test_adj_fused_cpu.py holds it to its header)
+ADJ_SIGNATURES = {
+    "lgadj_instnorm_apply_rs": (I, [P, P, P, P, P, P, I, L, I, F, P]),
+    "lgadj_instnorm_apply_p_rs": (I, [P, P, I, P, P, P, P, P, P, P, I, L, I, F, P]),
+    "lgadj_convT_s2_fwd_ns_supported": (I, [I, I, I, I, I, I]),
+    "lgadj_convT_s2_fwd_stats_ns": (I, [P, P, F, P, P, P, P, I, P, P, P, I, I, I, I, I, I, P, Z, P, P]),
+}
+
 
 class LittleGanHipError(RuntimeError):
     pass
@@ -224,7 +233,7 @@ def load():
     import torch  # noqa: F401
     lib = C.CDLL(path)
     for name, (res, args) in list(SIGNATURES.items()) + list(GEOM_SIGNATURES.items()) + list(REL_SIGNATURES.items()) \
-            + list(SCHED_SIGNATURES.items()):
+            + list(SCHED_SIGNATURES.items()) + list(ADJ_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

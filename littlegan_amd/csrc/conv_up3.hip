@@ -31,6 +31,7 @@
 #include <type_traits>
 #include <utility>
 #include "lg_internal.h"
+#include "../../include/littlegan_adj.h"
 
 namespace {
 
@@ -75,6 +76,14 @@ struct U3Params {
   double* spart;       // [B][tpi][3] or null
   int B, Hs, Ws, tpi_x, tpi, nitems;
   LgNormFuse nf;       // FUSE instantiation: norm-backward sums of the produced gradient (lg_common.h)
+  // NSK instantiation: src is the RAW bf16 z of the level below; h = bf16(leaky(norm(z)) + skip) is formed per halo piece
+  // between its buffer load and its LDS store.  The skip comes as two row ranges, samples [0, b1) from sk0 and [b1, B) from sk1, each
+  // either the normalised bf16 map (its records pointer null) or a raw z normalised with its own records on the way.
+  const float* zstats;             // [B][8] finished statistics records of src
+  const __bf16 *sk0, *sk1;         // [b1][Hs][Ws][CS], [B - b1][Hs][Ws][CS]
+  const float *sks0, *sks1;        // [b1][8], [B - b1][8] or null
+  int b1;
+  float nalpha;
 };
 
 __device__ __forceinline__ int pix32(int r) {
@@ -90,9 +99,10 @@ constexpr int ntaps_of(int cls) { return nk(cls >> 1) * nk(cls & 1); }
 constexpr int tap_k(int p, int a) { return p ? 2 * a : 2 * a + 1; }
 constexpr int tap_d(int p, int a) { return (p + 1 - tap_k(p, a)) / 2; }
 
-template <int CS, int N, bool STATS, bool FUSE = false, int NTT = 2 / (N / 32)>
+template <int CS, int N, bool STATS, bool FUSE = false, int NTT = 2 / (N / 32), bool NSK = false>
 __global__ __launch_bounds__((Cfg<CS, N, NTT>::THREADS), 2) void conv_up3_kernel(const U3Params p) {
   static_assert(!(STATS && FUSE), "forward moments and backward sums are never needed together");
+  static_assert(!NSK || (STATS && NTT == 1), "the normalising form is a forward form with one tile (one sample) per step");
   using C = Cfg<CS, N, NTT>;
   constexpr int NTH = C::THREADS, NWV = C::NWAVES;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -150,6 +160,12 @@ __global__ __launch_bounds__((Cfg<CS, N, NTT>::THREADS), 2) void conv_up3_kernel
   // loses the count at the join and drains the weight ring with s_waitcnt vmcnt(0) at every commit; see conv_down3.hip).
   constexpr unsigned OOB = 0x80000000u;   // >= num_records for every supported shape (checked on the host)
   const int sample_elems = p.Hs * p.Ws * CS;
+  // NSK: the skip pieces of the halo in flight (same offsets as the z pieces, through a descriptor over the sample's skip), which of
+  // the pieces lie inside the image (bit u: the others must stay ZERO in LDS — it is h that is zero-padded, not z), and the sample
+  u32x4 sv[NSK ? C::PPT : 1];
+  unsigned inm = 0;
+  int hn = 0;
+  (void)sv; (void)inm; (void)hn;
   auto issue = [&](int step, u32x4 (&v)[C::PPT]) {
     int n[C::NT], y0[C::NT], x0[C::NT];
     bool ok[C::NT];
@@ -161,6 +177,20 @@ __global__ __launch_bounds__((Cfg<CS, N, NTT>::THREADS), 2) void conv_up3_kernel
     //  it had been there since round 2: 54 -> 8 v_readfirstlane per kernel.  cdna_hip_programming.md T20.)
     const int nrec = __builtin_amdgcn_readfirstlane((p.B - n[0] >= 2 ? 2 : 1) * sample_elems * 2);
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(p.src + (long long)n[0] * sample_elems), 0, nrec, 0x00027000);
+    __amdgpu_buffer_rsrc_t rk = rs;
+    if constexpr (NSK) {
+      // the sample's skip: row n of the first range or row n - b1 of the second.  Address and size go through readfirstlane for the
+      // reason given above: a select hipcc forms on the VALU would put every skip load into a waterfall loop.
+      hn = __builtin_amdgcn_readfirstlane(n[0]);
+      const bool first = hn < p.b1;
+      const unsigned long long sa = (unsigned long long)(first ? p.sk0 : p.sk1) +
+                                    (unsigned long long)(first ? hn : hn - p.b1) * (unsigned long long)sample_elems * 2ull;
+      const unsigned slo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)sa);
+      const unsigned shi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(sa >> 32));
+      rk = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<__bf16*>(((unsigned long long)shi << 32) | slo), 0,
+                                             __builtin_amdgcn_readfirstlane(sample_elems * 2), 0x00027000);
+      inm = 0;
+    }
 #pragma unroll
     for (int u = 0; u < C::PPT; ++u) {
       const bool t1 = C::NT == 2 && (pyx[u] >> 20) != 0;  // selects, not runtime-indexed arrays (those go to scratch)
@@ -170,9 +200,46 @@ __global__ __launch_bounds__((Cfg<CS, N, NTT>::THREADS), 2) void conv_up3_kernel
       const bool in = pl[u] >= 0 && tok && (unsigned)sy < (unsigned)p.Hs && (unsigned)sx < (unsigned)p.Ws;
       const unsigned off = in ? (unsigned)((((dn * p.Hs + sy) * p.Ws + sx) * CS + ((pyx[u] >> 12) & 255) * 8) * 2) : OOB;
       v[u] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
+      if constexpr (NSK) {
+        sv[u] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rk, off, 0, 0));
+        inm |= (in ? 1u : 0u) << u;
+      }
     }
   };
   auto commit = [&](const u32x4 (&v)[C::PPT]) {
+    if constexpr (NSK) {
+      // h = bf16(leaky(a ((z - mu) - mul) + b) + skip): apply16p_kernel<2> (norm.hip) operation by operation — the skip is added in
+      // fp32 BEFORE the one rounding — on the skip map apply16_kernel<0> would have stored (lg_norm8) where the range is raw.
+      // Behind a scheduling fence: the unpack must not be hoisted in front of the staging pass, where it would wait out the loads.
+      __builtin_amdgcn_sched_barrier(0);
+      const lg_const_f32p zr = lg_as_const(p.zstats + (long long)hn * LG_NSTAT);
+      const float mu = lg_uniform(zr[0]), a = lg_uniform(zr[2]), b = lg_uniform(zr[3]), mul = lg_uniform(zr[4]);
+      const bool first = hn < p.b1;
+      const float* sks = first ? p.sks0 : p.sks1;
+      const bool raw = sks != nullptr;
+      // always a valid record (the sample's own where the range is a normalised map: read, not used): no branch around a load
+      const lg_const_f32p sr = lg_as_const(raw ? sks + (long long)(first ? hn : hn - p.b1) * LG_NSTAT : p.zstats + (long long)hn * LG_NSTAT);
+      const float smu = lg_uniform(sr[0]), sa = lg_uniform(sr[2]), sb = lg_uniform(sr[3]), smul = lg_uniform(sr[4]);
+      typedef __bf16 up3_bf16x2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+      for (int u = 0; u < C::PPT; ++u) {
+        const u32x4 z8 = v[u];
+        u32x4 s8 = sv[u];
+        if (raw) s8 = lg_norm8(s8, smu, smul, sa, sb, p.nalpha);
+        u32x4 h8;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float t0 = __builtin_bit_cast(float, z8[k] << 16), t1 = __builtin_bit_cast(float, z8[k] & 0xffff0000u);
+          t0 = a * ((t0 - mu) - mul) + b; t1 = a * ((t1 - mu) - mul) + b;
+          t0 = lg_leaky(t0, p.nalpha); t1 = lg_leaky(t1, p.nalpha);
+          t0 += __builtin_bit_cast(float, s8[k] << 16); t1 += __builtin_bit_cast(float, s8[k] & 0xffff0000u);
+          h8[k] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{t0, t1}, up3_bf16x2));
+        }
+        if (!((inm >> u) & 1u)) h8 = u32x4{0u, 0u, 0u, 0u};
+        if (pl[u] >= 0) *reinterpret_cast<u32x4*>(smem + pl[u]) = h8;
+      }
+      return;
+    }
 #pragma unroll
     for (int u = 0; u < C::PPT; ++u)
       if (pl[u] >= 0) *reinterpret_cast<u32x4*>(smem + pl[u]) = v[u];
@@ -488,7 +555,7 @@ __global__ __launch_bounds__((Cfg<CS, N, NTT>::THREADS), 2) void conv_up3_kernel
 }
 
 template <int CS, int N, int NTT = 2 / (N / 32)>
-int launch_up3(U3Params p, bool stats, hipStream_t st, bool fuse = false) {
+int launch_up3(U3Params p, bool stats, hipStream_t st, bool fuse = false, bool nsk = false) {
   using C = Cfg<CS, N, NTT>;
   static bool attr_set = false;
   const int nblk = (C::NWAVES == 8 ? 1 : 2) * lg_grid_cus();  // one 8-wave workgroup per CU, or two independent 4-wave ones
@@ -497,9 +564,17 @@ int launch_up3(U3Params p, bool stats, hipStream_t st, bool fuse = false) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_up3_kernel<CS, N, true, false, NTT>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_up3_kernel<CS, N, false, false, NTT>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_up3_kernel<CS, N, false, true, NTT>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
+    if constexpr (NTT == 1)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_up3_kernel<CS, N, true, false, NTT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
   }
   const int nsteps = (p.nitems + C::NT - 1) / C::NT;
   const int grid = nsteps < nblk ? nsteps : nblk;
+  if constexpr (NTT == 1) {
+    if (nsk) {
+      hipLaunchKernelGGL((conv_up3_kernel<CS, N, true, false, NTT, true>), dim3(grid), dim3(C::THREADS), C::LDS, st, p);
+      return LG_OK;
+    }
+  }
   if (fuse) hipLaunchKernelGGL((conv_up3_kernel<CS, N, false, true, NTT>), dim3(grid), dim3(C::THREADS), C::LDS, st, p);
   else if (stats) hipLaunchKernelGGL((conv_up3_kernel<CS, N, true, false, NTT>), dim3(grid), dim3(C::THREADS), C::LDS, st, p);
   else hipLaunchKernelGGL((conv_up3_kernel<CS, N, false, false, NTT>), dim3(grid), dim3(C::THREADS), C::LDS, st, p);
@@ -556,5 +631,42 @@ extern "C" int lg_conv_up3_nf_try(const void* src16, const void* wpack_up, const
   LG_CHECK_LAUNCH("lg_conv_up3");
   lg_note_kernel(tiling == U3_N64 ? "conv_up3_kernel<128,64>" : "conv_up3_kernel<64,32,4w>");
   if (stats || fuse) *nparts_out = p.tpi;
+  return LG_OK;
+}
+
+// ---- the forward that normalises its source and adds the skip while it stages the halo (NSK form; include/littlegan_adj.h) -------
+// Both forward tilings run one tile per step, so both have the form; the kill switches of the plain forward hold here too.
+extern "C" int lgadj_convT_s2_fwd_ns_supported(int B, int Hs, int Ws, int cb, int cs, int dtype) {
+  return (dtype == LG_DT_BF16 && lg_halo_enabled() && up3_tiling(B, Hs, Ws, cs, cb) != U3_NONE) ? 1 : 0;
+}
+extern "C" int lgadj_convT_s2_fwd_stats_ns(const void* z16, const float* zstats, float alpha, const void* skip0, const float* skip0_stats,
+                                           const void* skip1, const float* skip1_stats, int b1, const void* pack, const float* bias,
+                                           void* y16, int B, int Hs, int Ws, int cb, int cs, int dtype, void* spart, size_t spart_bytes,
+                                           int* nparts, void* stream) {
+  if (nparts) *nparts = 0;
+  LG_CHECK_ARG(z16 && zstats && pack && y16 && spart && nparts, "lgadj_convT_s2_fwd_stats_ns: null pointer");
+  LG_CHECK_ARG(B > 0 && b1 >= 0 && b1 <= B, "lgadj_convT_s2_fwd_stats_ns: the first skip range has %d of %d samples", b1, B);
+  LG_CHECK_ARG((b1 == 0 || skip0) && (b1 == B || skip1), "lgadj_convT_s2_fwd_stats_ns: null pointer (a skip range that has samples)");
+  if (!lgadj_convT_s2_fwd_ns_supported(B, Hs, Ws, cb, cs, dtype)) {
+    lg_set_error("lgadj_convT_s2_fwd_stats_ns: shape B=%d %dx%d cb=%d cs=%d has no normalising forward (see ..._ns_supported)", B, Hs, Ws, cb, cs);
+    return LG_ERR_UNSUPPORTED;
+  }
+  const U3Tiling tiling = up3_tiling(B, Hs, Ws, cs, cb);
+  U3Params p{};
+  p.src = (const __bf16*)z16; p.wp = (const char*)pack + lg_conv_pack_up_offset(cb, cs, dtype); p.bias = bias; p.out = (__bf16*)y16;
+  p.B = B; p.Hs = Hs; p.Ws = Ws; p.tpi_x = Ws / TW; p.tpi = p.tpi_x * (Hs / TH);
+  const long long nitems = (long long)B * p.tpi;
+  LG_CHECK_ARG(nitems < (1ll << 30), "lgadj_convT_s2_fwd_stats_ns: too many tiles");
+  LG_CHECK_ARG((size_t)B * p.tpi * 3 * sizeof(double) <= spart_bytes, "lgadj_convT_s2_fwd_stats_ns: workspace too small (lg_conv_stats_workspace_bytes)");
+  p.nitems = (int)nitems;
+  p.spart = (double*)spart;
+  p.zstats = zstats; p.sk0 = (const __bf16*)skip0; p.sk1 = (const __bf16*)skip1; p.sks0 = skip0_stats; p.sks1 = skip1_stats;
+  p.b1 = b1; p.nalpha = alpha;
+  hipStream_t st = (hipStream_t)stream;
+  if (tiling == U3_N64) launch_up3<128, 64>(p, true, st, false, true);
+  else launch_up3<64, 32, 1>(p, true, st, false, true);
+  LG_CHECK_LAUNCH("lgadj_convT_s2_fwd_stats_ns");
+  lg_note_kernel(tiling == U3_N64 ? "conv_up3_kernel<128,64>" : "conv_up3_kernel<64,32,4w>");
+  *nparts = p.tpi;
   return LG_OK;
 }

@@ -121,7 +121,7 @@ class Encoder(_ConvStack):
         return cs
 
     def __call__(self, inputs, ctx: Optional[dict] = None, tails=None, keep_maps: bool = True, top_only: bool = False,
-                 drop: Optional[ops.Drop] = None):
+                 drop: Optional[ops.Drop] = None, raw_skips: bool = False):
         """Returns the 4 maps (model.py:27).  f32 path: fp32 tensors.  bf16 path: maps 1-3 are the bf16 mirrors the next
         conv reads anyway (they are also what the Adjuster's decoder adds as skips), map 4 (8x8, heads input) is fp32;
         the raw conv outputs z are kept in HBM as bf16 only (moments from the fp32 accumulators of the conv epilogue).
@@ -136,7 +136,13 @@ class Encoder(_ConvStack):
         context holds no x / x16 for the level above.  Bit-identical results.
         drop (ops.Drop naming the step's key and this pass's call slot; `inputs` are rows 0.. of the call's batch): the 4 maps are
         post-dropout, and the context records each level's drop context — backward() reads it there and nowhere else, so it cannot
-        disagree with the forward.  The fused route of top_only knows no mask: with an active one every level runs its apply pass."""
+        disagree with the forward.  The fused route of top_only knows no mask: with an active one every level runs its apply pass.
+        raw_skips (bf16 path, with tails): the caller accepts maps 1 and 2 UN-normalised and no tape will ask this pass for a weight
+        gradient (the Adjuster's own encoder pass).  Where the route is adopted (ops.enc_raw_skip_adopted: the next conv
+        can normalise while it stages, and the batch is large enough for the trade to pay), the own part of
+        such a pair is an ops.Raw (z16, statistics) and the map is never written; the consumers (the decoder's skip adds) normalise on
+        the way in, bit-identically.  Level 3's apply stays (the pair form of conv4 has no normalising variant); an active mask falls
+        back to the apply route, as top_only does."""
         x = inputs
         a = self.args.leaky_alpha
         packs = self.packs()
@@ -146,14 +152,16 @@ class Encoder(_ConvStack):
         x16 = None
         if top_only and (tails is not None or not m16 or (drop is not None and drop.active)):
             top_only = False
+        raw_skips = raw_skips and tails is not None and m16 and not (drop is not None and drop.active)
         drops = [drop.at(level=i, r0=0) for i in range(1, 5)] if drop is not None else None
         raw = None   # (z, stats) of the level below when its apply pass was left out
         for i, (cb, cs) in enumerate(self.chans, 1):
             gm, bt = self._w[f"norm{i}.gamma"], self._w[f"norm{i}.beta"]
             # does the NEXT conv normalise this level's output itself?
             Bn, Hn, Wn = (x if x is not None else x16 if x16 is not None else raw[0]).shape[:3]
-            skip_apply = (top_only and i < 4 and
-                          ops.conv2d_s2_fwd_stats_zn_supported(Bn, Hn // 2, Wn // 2, cs, self.chans[i][1], self.dtype))
+            nxt = (Bn, Hn // 2, Wn // 2, cs, self.chans[i][1] if i < 4 else 0, self.dtype)
+            skip_apply = ((top_only and i < 4 and ops.conv2d_s2_fwd_stats_zn_supported(*nxt)) or
+                          (raw_skips and i < 3 and ops.enc_raw_skip_adopted(*nxt)))
             if raw is not None:
                 z, st = ops.conv2d_s2_fwd_stats_zn(raw[0], raw[1], a, packs[i - 1], self._w[f"conv{i}.bias"], cs, self.dtype, gm, bt)
             else:
@@ -163,7 +171,7 @@ class Encoder(_ConvStack):
                 st = ops.instnorm_stats(z, gm, bt, 0, a)
             if skip_apply:
                 st = ops.stats_tensor(st)
-                outs.append(None)
+                outs.append(None if top_only else (ops.Raw(z, st), tails[i - 1]))
                 saved.append((x, z, st, x16))
                 x, x16, raw = None, None, (z, st)
                 continue
@@ -330,8 +338,13 @@ class Decoder(_ConvStack):
     def _bias_dim(cb, cs):
         return cb
 
-    def __call__(self, inputs, ctx: Optional[dict] = None, raw_last: bool = False):
-        """raw_last (bf16 path, when the final layer can normalise while it stages — ops.convT_s1_tanh_fwd_z16_supported): the
+    def __call__(self, inputs, ctx: Optional[dict] = None, raw_last: bool = False, no_wgrad: bool = False):
+        """A skip (add[i]) is a map, an ops.Raw (an encoder level handed over un-normalised: normalised inside the pass that adds
+        it), or a pair of those (first rows, remaining rows) of the batch.
+        no_wgrad (bf16 path): no tape will ask this pass for a weight gradient (the Adjuster) — the normalised map of
+        a level is then not written where the next conv forms it while staging (ops.convT_s2_fwd_ns_adopted); the context holds no
+        x / x16 for the level above such a level.  Bit-identical results.
+        raw_last (bf16 path, when the final layer can normalise while it stages — ops.convT_s1_tanh_fwd_z16_supported): the
         last level's InstanceNorm + LeakyReLU pass is NOT run; returns (None, None) and leaves that level's raw (z16, stats) in
         ctx["dec"][3] for the consumer.  Only for callers whose tapes never need the normalised level-4 map: it is the operand
         of the final layer's WEIGHT gradient, so the Generator keeps it; the Adjuster (trains its dense + norm only) does not."""
@@ -350,13 +363,29 @@ class Decoder(_ConvStack):
             x16 = None
         if m16 and x16 is None:
             raise ValueError("Decoder: the bf16 path needs the bf16 mirror of its input (_DenseNorm.__call__(want16=True))")
+        fused = None   # (z, stats, skip) of the level below when its norm + skip pass was left to this level's conv
         for i, (cb, cs) in enumerate(self.chans, 1):
             gm, bt = self._w[f"norm{i}.gamma"], self._w[f"norm{i}.beta"]
-            z, st = ops.convT_s2_fwd_stats(x, packs[i - 1], self._w[f"conv{i}.bias"], cb, self.dtype, gm, bt, x16=x16,
-                                           z16=m16, alpha=a, defer_stats=m16)
+            if fused is not None:
+                z, st = ops.convT_s2_fwd_stats_ns(fused[0], fused[1], a, fused[2], packs[i - 1], self._w[f"conv{i}.bias"], cb,
+                                                  self.dtype, gm, bt, defer_stats=True)
+                fused = None
+            else:
+                z, st = ops.convT_s2_fwd_stats(x, packs[i - 1], self._w[f"conv{i}.bias"], cb, self.dtype, gm, bt, x16=x16,
+                                               z16=m16, alpha=a, defer_stats=m16)
             if st is None:
                 st = ops.instnorm_stats(z, gm, bt, 0, a)
             skip = add[i] if i < 4 else None
+            # A caller that never takes weight gradients has ONE reader of h_i = leaky(norm(z_i)) + skip: the next transposed conv.
+            # Where that conv can form h_i while it stages its operand (ops.convT_s2_fwd_stats_ns), the norm + skip pass and the map
+            # are left out; the level above records no input (backward(need_wgrad=False) works from z and the statistics alone).
+            if (no_wgrad and m16 and i < 4 and skip is not None and z.dtype == torch.bfloat16 and
+                    ops.convT_s2_fwd_ns_adopted(z.shape[0], z.shape[1], z.shape[2], self.chans[i][0], cb, self.dtype)):
+                st = ops.stats_tensor(st)   # no apply pass here: the stand-alone finalize
+                saved.append((x, z, st, x16))
+                fused = (z, st, skip)
+                x, x16 = None, None
+                continue
             # levels 1-3 feed only the next transposed conv and its weight gradient, level 4 the final 3-channel
             # layer: where those kernels read the bf16 mirror, the fp32 copy is not written at all
             if i < 4:
@@ -773,7 +802,8 @@ class Adjuster(_Module):
         else:  # the trailing samples of `image` were already encoded by D in this step (same weights): reuse
             # `image` holds the leading samples only (or the whole batch: then its trailing rows are the ones already encoded)
             own = cond.shape[0] - enc_tails[0].shape[0]
-            enc = self.encoder(image[:own], None, tails=enc_tails, drop=drop)
+            # (no tape asks this pass for a weight gradient, and the decoder below takes un-normalised skips: raw_skips)
+            enc = self.encoder(image[:own], None, tails=enc_tails, drop=drop, raw_skips=True)
         # the decoder's first skip (the encoder's top map, model.py:131-135) is added by the dense-norm apply launch
         c4 = self._dn(cond, ctx, skip=enc[3], want16=self.dtype == DT_BF16)
         # the Adjuster's tape differentiates dense + norm only (eager_trainer.py:51,62,163): nothing ever reads the decoder's
@@ -781,7 +811,7 @@ class Adjuster(_Module):
         side = self.args.init_dim * 16
         raw = self.conv.raw_supported(side, side)
         dctx = ctx if ctx is not None else ({} if raw else None)
-        x, x16 = self.decoder([c4, [None] + enc[::-1][1:]], dctx, raw_last=raw)
+        x, x16 = self.decoder([c4, [None] + enc[::-1][1:]], dctx, raw_last=raw, no_wgrad=True)
         if raw and x is None and x16 is None:
             img = self.conv.from_raw(dctx["dec"][3][1], dctx["dec"][3][2])
         else:

@@ -492,6 +492,23 @@ def stats_tensor(st):
     return st.stats
 
 
+class Raw:
+    """A level's output handed over UN-normalised: the raw bf16 conv output z [B,H,W,C] and its finished statistics
+    records [B, NSTAT], standing for the map bf16(LeakyReLU(InstanceNorm(z))) that was never written.  The consumers that take one
+    (instnorm_apply as a skip, convT_s2_fwd_stats_ns) normalise on the way in, bit-identically to reading the stored map."""
+    __slots__ = ("z", "stats")
+
+    def __init__(self, z, stats):
+        if not (isinstance(z, torch.Tensor) and z.dtype == torch.bfloat16 and z.is_contiguous()):
+            raise ValueError("Raw: z must be a contiguous bf16 tensor")
+        _chk(stats, (z.shape[0], NSTAT), "Raw.stats")
+        self.z, self.stats = z, stats
+
+    @property
+    def shape(self):
+        return self.z.shape
+
+
 def instnorm_stats(x, gamma, beta, pre_leaky, alpha, stats=None, x16_out=None):
     """x16_out (optional bf16 tensor like x): also receives bf16(x) in the same pass."""
     B = x.shape[0]
@@ -598,6 +615,13 @@ def instnorm_apply(x, stats, skip, pre_leaky, post_leaky, alpha, out=None, out16
         else:
             stats = stats_tensor(stats)
     _chk(stats, (B, NSTAT), "stats")
+    raw_skip = skip if isinstance(skip, Raw) else None
+    if raw_skip is not None:   # the skip is a raw (z, records) pair: normalised inside the launch (norm_rs.hip)
+        if not x_is16 or pre_leaky or drop is not None:
+            raise ValueError("instnorm_apply: a raw skip needs the bf16 input path, pre_leaky=0 and no dropout")
+        if raw_skip.z.numel() != x.numel():
+            raise ValueError("instnorm_apply: skip has a different size")
+        skip = None
     skip16 = skip is not None and skip.dtype == torch.bfloat16
     if skip is not None:
         if skip16:
@@ -632,6 +656,19 @@ def instnorm_apply(x, stats, skip, pre_leaky, post_leaky, alpha, out=None, out16
         else:
             check(lib.lg_instnorm_leaky_apply_drop(_p(x), _p(stats), _p(out), _p(out16), B, Ln, float(alpha), *drop._args(), _stream()),
                   "lg_instnorm_leaky_apply_drop")
+        return out
+    if raw_skip is not None:
+        lib = _lib.load()
+        if pend is not None:
+            m = pend.m
+            part = m.ws.data_ptr() + pend.lo * m.nparts * 3 * 8
+            check(lib.lgadj_instnorm_apply_p_rs(_p(x), part, m.nparts, _p(m.gamma), _p(m.beta), _p(stats), _p(raw_skip.z),
+                                                _p(raw_skip.stats), _p(out), _p(out16), B, Ln, int(post_leaky), float(alpha), _stream()),
+                  "lgadj_instnorm_apply_p_rs")
+            m.covered += B
+        else:
+            check(lib.lgadj_instnorm_apply_rs(_p(x), _p(stats), _p(raw_skip.z), _p(raw_skip.stats), _p(out), _p(out16), B, Ln,
+                                              int(post_leaky), float(alpha), _stream()), "lgadj_instnorm_apply_rs")
         return out
     if pend is not None:
         m = pend.m
@@ -1061,6 +1098,88 @@ def convT_s2_fwd_stats(x, pack, bias, cb, dtype, gamma, beta, x16=None, z16=Fals
     st = _fwd_stats("lg_convT_s2_fwd_stats", x, x16, pack, bias, out, B, Hs, Ws, cb, cs, dtype, gamma, beta, "conv_igemm_up", fl,
                     up=True)
     return out, st
+
+
+_NS_OK = {}
+
+
+def convT_s2_fwd_ns_supported(B, Hs, Ws, cb, cs, dtype):
+    """Hs x Ws: the map the transposed conv reads (as convT_s2_fwd_stats).  True where convT_s2_fwd_stats_ns runs."""
+    key = (B, Hs, Ws, cb, cs, dtype)
+    if key not in _NS_OK:
+        _NS_OK[key] = bool(_lib.load().lgadj_convT_s2_fwd_ns_supported(*key))
+    return _NS_OK[key]
+
+
+_GRID_CUS = []
+
+
+def _fills_the_grid(B, Hm, Wm):
+    """B maps of Hm x Wm tile origins (8 x 16 tiles of conv_up3 / conv_down3) give every CU's persistent workgroup at least one tile"""
+    if not _GRID_CUS:
+        _GRID_CUS.append(int(_lib.load().lg_grid_cus()))
+    return B * (Hm // 8) * (Wm // 16) >= max(_GRID_CUS[0], 1)
+
+
+# Adoption of the Adjuster's fused routes (DESIGN.md §29, "Adoption").  Each route trades apply launches for ONE stand-alone finalize
+# launch (~5 us) in front of the consuming conv: the decoder's two apply launches of a level, the encoder's one.  It pays where the
+# apply passes are HBM-bound, which is where it was measured (2B = 512, B = 256: every level wins).  A batch that does not even give
+# every CU one tile of the consuming conv is launch-bound: an apply launch there costs what the finalize launch costs, the encoder's
+# trade is one launch for one launch, and nothing was measured — such a batch stays on the apply route.
+def convT_s2_fwd_ns_adopted(B, Hs, Ws, cb, cs, dtype):
+    """Hs x Ws: the map the transposed conv reads.  True where the Adjuster's decoder leaves norm + skip to convT_s2_fwd_stats_ns."""
+    return convT_s2_fwd_ns_supported(B, Hs, Ws, cb, cs, dtype) and _fills_the_grid(B, Hs, Ws)
+
+
+def enc_raw_skip_adopted(B, H, W, cb, cs, dtype):
+    """H x W: the map the conv reads (as conv2d_s2_fwd_stats_zn_supported).  True where the Adjuster's own encoder pass hands that
+    map over un-normalised and feeds the conv through conv2d_s2_fwd_stats_zn."""
+    return conv2d_s2_fwd_stats_zn_supported(B, H, W, cb, cs, dtype) and _fills_the_grid(B, H // 2, W // 2)
+
+
+def convT_s2_fwd_stats_ns(zin16, zin_stats, alpha, skip, pack, bias, cb, dtype, gamma, beta, defer_stats=False):
+    """convT_s2_fwd_stats (bf16 path) of the input h = bf16(LeakyReLU(InstanceNorm(zin16)) + skip), formed while the kernel stages its
+    operand: h is never written (bit-identical to instnorm_apply with that skip + convT_s2_fwd_stats).  zin16 [B,Hs,Ws,cs]: the raw
+    bf16 output of the level below, zin_stats its FINISHED records.  skip: a bf16 map or an ops.Raw of zin16's shape, or a pair of them
+    (first rows, remaining rows) of the batch.  -> (z16 [B,2Hs,2Ws,cb] bf16, stats: [B, NSTAT], or unfinished Moments if defer_stats)."""
+    import ctypes
+    lib = _lib.load()
+    B, Hs, Ws, cs = zin16.shape
+    _chk16(zin16, zin16, "zin16")
+    _chk(zin_stats, (B, NSTAT), "zin_stats")
+    _chk(bias, (cb,), "bias")
+    if not convT_s2_fwd_ns_supported(B, Hs, Ws, cb, cs, dtype):
+        raise ValueError(f"convT_s2_fwd_stats_ns: shape {tuple(zin16.shape)} -> {cb} is outside the normalising kernel's tiling")
+    parts = skip if isinstance(skip, tuple) else (skip, None)
+    b1 = parts[0].shape[0] if parts[0] is not None else 0
+    if not 0 <= b1 <= B or (b1 < B and parts[1] is None):
+        raise ValueError("convT_s2_fwd_stats_ns: the skip parts do not cover the batch")
+    args = []
+    for part, rows in zip(parts, (b1, B - b1)):
+        if part is None or rows == 0:
+            args += [0, 0]
+            continue
+        z = part.z if isinstance(part, Raw) else part
+        if tuple(z.shape) != (rows, Hs, Ws, cs):
+            raise ValueError(f"convT_s2_fwd_stats_ns: a skip part has shape {tuple(z.shape)}, expected {(rows, Hs, Ws, cs)}")
+        _chk16(z, z, "skip")
+        args += [_p(z), _p(part.stats) if isinstance(part, Raw) else 0]
+    ws = workspace(int(lib.lg_conv_stats_workspace_bytes(1, B, Hs, Ws, cb)), zin16.device, "statpart")
+    z16 = torch.empty(B, 2 * Hs, 2 * Ws, cb, dtype=torch.bfloat16, device=zin16.device)
+    nparts = ctypes.c_int(0)
+    e0 = _pb()
+    check(lib.lgadj_convT_s2_fwd_stats_ns(_p(zin16), _p(zin_stats), float(alpha), *args, b1, _p(pack), _p(bias), _p(z16), B, Hs, Ws, cb,
+                                          cs, dtype, _p(ws), ws.numel(), ctypes.addressof(nparts), _stream()),
+          "lgadj_convT_s2_fwd_stats_ns")
+    _pe(e0, "conv_igemm_up", 50.0 * B * Hs * Ws * cb * cs)
+    if nparts.value <= 0:
+        raise _lib.LittleGanHipError("lgadj_convT_s2_fwd_stats_ns: no moment partials came back")
+    if defer_stats:
+        return z16, Moments(ws, nparts.value, gamma, beta, B)
+    stats = torch.empty(B, NSTAT, dtype=torch.float32, device=zin16.device)
+    check(lib.lg_instnorm_stats_finalize(_p(ws), nparts.value, _p(stats), _p(gamma), _p(beta), B, _stream()),
+          "lg_instnorm_stats_finalize")
+    return z16, stats
 
 
 # ------------------------------------------------------------------ step inputs on the device (eager_trainer.py:125-131)
