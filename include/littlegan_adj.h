@@ -10,9 +10,9 @@
  * Entry points with the `lgadj_` prefix, exported by liblittlegan_hip.so under the conventions of littlegan_hip_ext.h — plain C, device
  * pointers, `stream` a hipStream_t passed as void* (NULL = default stream), return LG_OK (0) or LG_ERR_* with the message in
  * lg_last_error(), no allocation, no synchronisation, no atomics, every argument checked on the host before any launch, every launch
- * noted for lg_last_kernel().  lg_abi_version() stays 1: nothing declared in littlegan_hip*.h changes.  (A header of its own, bound by
- * _lib.ADJ_SIGNATURES: tests/test_adj_fused_cpu.py holds it to the three properties tests/test_abi.py holds the other headers to, and
- * tests/test_adj_fused_gpu.py runs every entry point between guard bands.) */
+ * noted for lg_last_kernel().  lg_abi_version() stays 1: nothing declared in littlegan_hip*.h changes.  (Part of the C ABI like every
+ * include/littlegan_*.h: bound by _lib.SIGNATURES, held to it by tests/test_abi.py; tests/test_memory_contract_gpu.py runs every entry
+ * point between guard bands.) */
 #ifndef LITTLEGAN_ADJ_H
 #define LITTLEGAN_ADJ_H
 #include <stddef.h>

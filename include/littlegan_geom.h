@@ -3,8 +3,8 @@
  * Entry points with the `lgeo_` prefix, exported by liblittlegan_hip.so under the conventions of littlegan_hip_ext.h — plain C, device
  * pointers, fp32, `stream` a hipStream_t passed as void* (NULL = default stream), return LG_OK (0) or LG_ERR_* with the message in
  * lg_last_error(), no allocation, no synchronisation, every argument checked on the host before any launch.  lg_abi_version() stays 1:
- * nothing declared in littlegan_hip*.h changes.  (A header of its own, bound by _lib.GEOM_SIGNATURES: tests/test_geom_cpu.py holds it to
- * the three properties tests/test_abi.py holds the other headers to.)
+ * nothing declared in littlegan_hip*.h changes.  (Part of the C ABI like every include/littlegan_*.h: bound by _lib.SIGNATURES, held
+ * to it by tests/test_abi.py.)
  *
  * ---- the definition (THIS PROJECT's; Karras et al. 2020, "Training GANs with limited data", pixel blitting + geometric group) ------ *
  * diff_augment (littlegan_hip.h) has colour, integer translation and cutout.  This is the other group: x-flip, quarter turns, isotropic

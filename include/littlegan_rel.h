@@ -4,8 +4,8 @@
  * Entry points with the `lgrel_` prefix, exported by liblittlegan_hip.so under the conventions of littlegan_hip_ext.h — plain C, device
  * pointers, fp32, `stream` a hipStream_t passed as void* (NULL = default stream), return LG_OK (0) or LG_ERR_* with the message in
  * lg_last_error(), no allocation, no synchronisation, no atomics, every argument checked on the host before any launch.
- * lg_abi_version() stays 1: nothing declared in littlegan_hip*.h changes.  (A header of its own, bound by _lib.REL_SIGNATURES:
- * tests/test_rel_cpu.py holds it to the three properties tests/test_abi.py holds the other headers to.)
+ * lg_abi_version() stays 1: nothing declared in littlegan_hip*.h changes.  (Part of the C ABI like every include/littlegan_*.h:
+ * bound by _lib.SIGNATURES, held to it by tests/test_abi.py.)
  *
  * ---- the definition (THIS PROJECT's; Jolicoeur-Martineau 2018, relativistic pairing; Huang et al. 2024, R1 + R2) ------------------- *
  * f0 = the ROLE-0 (D real) function of a logit-side kind of littlegan_hip_obj.h, evaluated by the device function that

@@ -4,8 +4,8 @@
  * Entry points with the `lgsch_` prefix, exported by liblittlegan_hip.so under the conventions of littlegan_hip_ext.h — plain C, device
  * pointers, fp32, `stream` a hipStream_t passed as void* (NULL = default stream), return LG_OK (0) or LG_ERR_* with the message in
  * lg_last_error(), no allocation, no synchronisation, no atomics, every argument checked on the host before any launch, every launch
- * noted for lg_last_kernel().  lg_abi_version() stays 1: nothing declared in littlegan_hip*.h changes.  (A header of its own, bound by
- * _lib.SCHED_SIGNATURES: tests/test_lr_schedule_cpu.py holds it to the three properties tests/test_abi.py holds the other headers to.)
+ * noted for lg_last_kernel().  lg_abi_version() stays 1: nothing declared in littlegan_hip*.h changes.  (Part of the C ABI like every
+ * include/littlegan_*.h: bound by _lib.SIGNATURES, held to it by tests/test_abi.py.)
  *
  * ---- the definition (THIS PROJECT's) ---------------------------------------------------------------------------------------------- *
  * k = the number of training steps taken so far, over the whole run and across epochs; W = warmup, N = decay_steps, r = the fp32 value

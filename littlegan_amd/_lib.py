@@ -1,4 +1,4 @@
-"""ctypes binding of liblittlegan_hip.so.  The C ABI is every function declared in include/littlegan_hip*.h; SIGNATURES below is its one
+"""ctypes binding of liblittlegan_hip.so.  The C ABI is every function declared in include/littlegan_*.h; SIGNATURES below is its one
 table (tests/test_abi.py holds it to the headers and to the symbols the library exports).
 
 The product path has NO fallback: if the shared library is missing this module raises at
@@ -161,38 +161,21 @@ SIGNATURES = {
     # gan_loss (objective.hip): the heads forward that keeps the logit of output_pr, and the loss on it
     "lgo_heads_fwd": (I, [P, P, P, P, P, P, P, P, Z, I, I, I, P]),
     "lgo_gan_heads_loss_fwd_bwd": (I, [P, P, P, I, I, F, F, P, P, I, I, I, P]),
-}
-
-
-# include/littlegan_geom.h: geometric augmentation of D's inputs (geom.hip).  A table of its own: SIGNATURES is the ABI of
-# include/littlegan_hip*.h, this one that of the `lgeo_` header; load() binds both (tests/test_geom_cpu.py holds it to its header)
-GEOM_SIGNATURES = {
+    # geometric augmentation of D's inputs (include/littlegan_geom.h; geom.hip): the per-row draw, Geo and its adjoint
     "lgeo_draw": (I, [P, I, I, I, I, I, P, P, P]),
     "lgeo_fwd": (I, [P, P, P, I, I, P]),
     "lgeo_bwd": (I, [P, P, P, I, I, P]),
-}
-
-# include/littlegan_rel.h: the relativistic pairing objective and the R1 + R2 seed (objective.hip, r1.hip).  A table of its
-# own for the same reason; load() binds it too (tests/test_rel_cpu.py holds it to its header)
-REL_SIGNATURES = {
+    # the relativistic pairing objective and the R1 + R2 seed (include/littlegan_rel.h; objective.hip, r1.hip)
     "lgrel_pair_heads_loss_fwd_bwd": (I, [P, P, P, P, I, I, F, F, P, P, I, I, I, I, P]),
     "lgrel_r12_workspace_bytes": (Z, [I, L]),
     "lgrel_r12_seed": (I, [P, P, P, P, P, P, F, F, P, Z, I, L, P]),
-}
-
-# include/littlegan_sched.h: the learning-rate schedule on the device and the Adam passes that read their rate from its state (sched.hip,
-# loss_optim.hip).  A table of its own for the same reason; load() binds it too (tests/test_lr_schedule_cpu.py holds it to
-# its header)
-SCHED_SIGNATURES = {
+    # the learning-rate schedule on the device and the Adam passes that read their rate from its state (include/littlegan_sched.h;
+    # sched.hip, loss_optim.hip)
     "lgsch_init": (I, [P, I, P]),
     "lgsch_step": (I, [P, I, I, I, F, F, F, F, P]),
     "lgsch_clip_adam_update": (I, [P, P, P, P, L, P, P, F, F, F, F, F, P]),
     "lgsch_clip_adam_ema_update": (I, [P, P, P, P, P, L, L, L, P, P, P, F, F, F, F, F, F, P]),
-}
-
-# include/littlegan_adj.h: the Adjuster's forward without its single-reader normalised maps (norm_rs.hip, conv_up3.hip).  A
-# table of its own for the same reason; load() binds it too (tests/test_adj_fused_cpu.py holds it to its header)
-ADJ_SIGNATURES = {
+    # the Adjuster's forward without its single-reader normalised maps (include/littlegan_adj.h; norm_rs.hip, conv_up3.hip)
     "lgadj_instnorm_apply_rs": (I, [P, P, P, P, P, P, I, L, I, F, P]),
     "lgadj_instnorm_apply_p_rs": (I, [P, P, I, P, P, P, P, P, P, P, I, L, I, F, P]),
     "lgadj_convT_s2_fwd_ns_supported": (I, [I, I, I, I, I, I]),
@@ -232,8 +215,7 @@ def load():
     # before torch, the system runtime it links against would come in as a SECOND runtime and its kernels would see no device.
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name, (res, args) in list(SIGNATURES.items()) + list(GEOM_SIGNATURES.items()) + list(REL_SIGNATURES.items()) \
-            + list(SCHED_SIGNATURES.items()) + list(ADJ_SIGNATURES.items()):
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

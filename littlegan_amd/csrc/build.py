@@ -40,11 +40,9 @@ def build(force=False, verbose=True, variant=None):
     if not variant and os.environ.get("LG_EXTRA_FLAGS"):
         raise SystemExit("LG_EXTRA_FLAGS needs --variant NAME: ablation builds never replace the product library")
     os.makedirs(objdir, exist_ok=True)
-    # every source includes lg_internal.h, and through it lg_common.h and the public header: all headers are every object's dependencies
+    # every source includes lg_internal.h, and through it lg_common.h and the public headers: all headers are every object's dependencies
     inc = os.path.join(os.path.dirname(PKG), "include")
-    headers = sorted(glob.glob(os.path.join(HERE, "*.h"))) + sorted(glob.glob(os.path.join(inc, "littlegan_hip*.h"))) + \
-        [os.path.join(inc, "littlegan_geom.h"), os.path.join(inc, "littlegan_rel.h"), os.path.join(inc, "littlegan_sched.h"),
-         os.path.join(inc, "littlegan_adj.h")]
+    headers = sorted(glob.glob(os.path.join(HERE, "*.h"))) + sorted(glob.glob(os.path.join(inc, "littlegan_*.h")))
 
     # LG_EXTRA_FLAGS carries the ablation macros of scripts/probe/*.sh ("results wrong, timing only"): the flag set an object
     # was built with is recorded beside it, and an object (hence the library) built with OTHER flags is stale — a probe build

@@ -14,8 +14,9 @@ import re
 import torch
 
 # What a name of the C ABI looks like, for every check that has to tell one from anything else (tests/test_abi.py, the recorder below):
-# `lg`, an optional lower-case letter, `_`.  The letter groups names for the reader; no check keys off it.
-ABI_NAME = r"lg[a-z]?_\w+"
+# `lg`, any number of lower-case letters, `_`.  The letters group names for the reader (`lgx_`, `lgeo_`, `lgadj_`, ...: one group per
+# header); no check keys off them.
+ABI_NAME = r"lg[a-z]*_\w+"
 
 ZONE_MIN = 64 << 10   # bytes: a red zone is max(payload, 64 KiB), so an overrun by a whole payload (one more tile, row block, sample) stays inside
 ALIGN = 256           # the payload keeps the alignment of a plain torch device allocation (lg_conv_wgrad_m16 routes on dw & 15)

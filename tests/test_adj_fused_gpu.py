@@ -10,7 +10,7 @@ Every fused form is bit-identical to the route through the stored maps by constr
   * lgadj_instnorm_apply_rs / _p_rs (the apply pass whose skip is raw) against normalise-then-apply, at a sample length that is no
     multiple of the block's unroll and for one sample;
   * the same fused launch twice: equal outputs;
-  * every new entry point between guard bands (tests/guards.py), operands included;
+  * (every new entry point between guard bands, operands included: the adj-* rows of tests/test_memory_contract_gpu.py);
   * the whole Adjuster forward + backward_own at the smallest configuration that reaches every new route, against the same run with
     the predicates forced off: image, loss and the four gradients."""
 import ctypes
@@ -19,8 +19,6 @@ import itertools
 import numpy as np
 import pytest
 import torch
-
-import guards
 
 pytestmark = pytest.mark.gpu
 
@@ -194,66 +192,6 @@ def test_apply_with_a_raw_skip_equals_normalise_then_apply(ops, B, L8, post_leak
         outs.append((y16, mom.stats.clone()))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     assert torch.equal(outs[1][0], want16) and torch.equal(outs[1][1], st)
-
-
-def test_memory_contract_of_the_new_entry_points(ops, monkeypatch):
-    """outputs, workspaces and operands inside guard bands: nothing outside the declared extents changes, and nothing outside an
-    operand is read into the result (the bands hold NaN)"""
-    lib = ops._lib.load()
-    ws = guards.exact_workspaces(monkeypatch, ops)
-    # ---- the fused forward, both tilings, an uneven split of a raw and a stored part
-    for cs, cb, hs, wd in ((128, 64, 8, 16), (64, 32, 8, 32)):
-        lay = Layer(ops, cs, cb, seed=31 + cs)
-        B, b1 = 3, 1
-        z, zst, parts = lay.operands(ops, B, hs, wd, b1, ("raw", "map"))
-        want = lay.two_pass(ops, z, zst, parts, b1)[0]
-        gz, gst = guards.guard(z), guards.guard(zst)
-        gs0, gs0st, gs1 = guards.guard(parts[0].z), guards.guard(parts[0].stats), guards.guard(parts[1])
-        gout = guards.Guarded(want.shape, torch.bfloat16, "cuda")
-        nbytes = int(lib.lg_conv_stats_workspace_bytes(1, B, hs, wd, cb))
-        gws = guards.Guarded((nbytes,), torch.uint8, "cuda")
-        nparts = ctypes.c_int(0)
-        rc = lib.lgadj_convT_s2_fwd_stats_ns(gz.t.data_ptr(), gst.t.data_ptr(), ALPHA, gs0.t.data_ptr(), gs0st.t.data_ptr(), gs1.t.data_ptr(),
-                                             0, b1, lay.pack.data_ptr(), lay.bias.data_ptr(), gout.t.data_ptr(), B, hs, wd, cb, cs, BF16,
-                                             gws.t.data_ptr(), nbytes, ctypes.addressof(nparts), 0)
-        assert rc == 0, lib.lg_last_error()
-        torch.cuda.synchronize()
-        assert nparts.value * B * 24 <= nbytes
-        for name, g in (("z16", gout), ("workspace", gws), ("z", gz), ("records", gst), ("skip 0", gs0), ("skip 1", gs1)):
-            assert not g.intact(), f"{name}: {guards.describe(g.intact())}"
-        assert torch.equal(gout.t, want)
-    # ---- the apply forms
-    rng = np.random.default_rng(3)
-    B, L = 2, 8 * 1029
-    gm, bt = f32([1.1]), f32([0.05])
-    z, s = bf16(rng, B, L), bf16(rng, B, L, shift=0.4)
-    raw = ops.Raw(s, records(ops, s, gm, bt))
-    st = records(ops, z, gm, bt)
-    want16 = torch.empty_like(z)
-    want = ops.instnorm_apply(z, st, stored_map(ops, raw), 0, 1, ALPHA, out16=want16)
-    gz, gs, gst, gsst = guards.guard(z), guards.guard(s), guards.guard(st), guards.guard(raw.stats)
-    gy, gy16 = guards.Guarded(z.shape, torch.float32, "cuda"), guards.Guarded(z.shape, torch.bfloat16, "cuda")
-    rc = lib.lgadj_instnorm_apply_rs(gz.t.data_ptr(), gst.t.data_ptr(), gs.t.data_ptr(), gsst.t.data_ptr(), gy.t.data_ptr(), gy16.t.data_ptr(),
-                                     B, L, 1, ALPHA, 0)
-    assert rc == 0, lib.lg_last_error()
-    torch.cuda.synchronize()
-    for g in (gz, gs, gst, gsst, gy, gy16):
-        assert not g.intact(), guards.describe(g.intact())
-    assert torch.equal(gy.t, want) and torch.equal(gy16.t, want16)
-    mom = hand_moments(ops, z, 5, gm, bt)
-    want_st = ops.stats_tensor(hand_moments(ops, z, 5, gm, bt))
-    ops.instnorm_apply(z, want_st, stored_map(ops, raw), 0, 1, ALPHA, out16=want16, want_f32=False)
-    gpart = guards.guard(mom.ws)
-    gstat = guards.Guarded(st.shape, torch.float32, "cuda")
-    gy16 = guards.Guarded(z.shape, torch.bfloat16, "cuda")
-    rc = lib.lgadj_instnorm_apply_p_rs(gz.t.data_ptr(), gpart.t.data_ptr(), 5, gm.data_ptr(), bt.data_ptr(), gstat.t.data_ptr(), gs.t.data_ptr(),
-                                       gsst.t.data_ptr(), 0, gy16.t.data_ptr(), B, L, 1, ALPHA, 0)
-    assert rc == 0, lib.lg_last_error()
-    torch.cuda.synchronize()
-    for g in (gz, gs, gsst, gpart, gstat, gy16):
-        assert not g.intact(), guards.describe(g.intact())
-    assert torch.equal(gstat.t, want_st) and torch.equal(gy16.t, want16)
-    ws.assert_intact()
 
 
 def test_refusals_without_a_launch(ops):

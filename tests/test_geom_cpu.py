@@ -1,7 +1,6 @@
 """Geometric augmentation of D's inputs (geom_augment) without a GPU: the restatement of the definition, of its adjoint
-and of the per-row draws (the oracle of tests/test_geom_gpu.py and tests/test_geom_contract_gpu.py), the C ABI of the three entry points
-of include/littlegan_geom.h (declared, exported, bound, validating before any launch, each with a guard-band row) and the configuration /
-trainer behaviour.
+and of the per-row draws (the oracle of tests/test_geom_gpu.py and of the geom rows of tests/test_memory_contract_gpu.py), the three entry points of
+include/littlegan_geom.h (their names, and that they validate before any launch) and the configuration / trainer behaviour.
 
 The definition (include/littlegan_geom.h), per sample x[S][S][3] with the record {a, b, c, d}, h = (S - 1) / 2, u = y - h, v = x - h:
   sy = (a u + b v) + h,  sx = (c u + d v) + h,  y0 = floor(sy),  x0 = floor(sx)
@@ -15,9 +14,6 @@ gates the block with third word 3; v_j = word_j >> 8: flip iff v0 < 2^23, k = v1
 theta = 2 pi (v3 2^-24 - 0.5); M = R(theta) Q^k F / s in float64, rounded to fp32 once."""
 import ctypes as C
 import os
-import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -26,7 +22,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from oracle import input_oracle as IO  # noqa: E402
-from test_abi import _ctype  # noqa: E402
+from test_abi import _protos  # noqa: E402
 from test_diffaug_cpu import _cpu_trainer, key_of  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -380,54 +376,13 @@ def lib():
     return _lib
 
 
-def geom_protos():
-    """name -> (return type, [parameter declarations]) of the prototypes of include/littlegan_geom.h"""
-    src = re.sub(r"/\*.*?\*/", "", open(GEOM_HEADER).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"(?:^|\n)\s*(const char\*|int|size_t)\s+(\w+)\s*\((.*?)\)\s*;", src, flags=re.S):
-        ret, name, args = m.group(1), m.group(2), " ".join(m.group(3).split())
-        assert name not in out, f"{name} is declared twice"
-        out[name] = (ret, [] if args in ("", "void") else [a.strip() for a in args.split(",")])
-    return out
+def test_geom_header_declares_the_entry_points(lib):
+    assert set(_protos(GEOM_HEADER)) == set(ENTRY_POINTS) == {n for n in lib.SIGNATURES if n.startswith("lgeo_")}
 
 
-def test_the_ledger_of_the_new_header(lib):
-    """The three properties tests/test_abi.py and tests/test_guards_cpu.py hold include/littlegan_hip*.h to, for include/littlegan_geom.h:
-    declared == bound with the declared types; exported and bound by load(); every pointer-taking function has a guard-band row."""
-    import glob
-    from guards import ABI_NAME
-    import test_geom_contract_gpu as GC
-    protos = geom_protos()
-    assert set(protos) == set(lib.GEOM_SIGNATURES) == set(ENTRY_POINTS)
-    assert all(n.startswith("lgeo_") and not re.fullmatch(ABI_NAME, n) for n in protos)     # outside the closed ABI table
-    assert not set(lib.GEOM_SIGNATURES) & set(lib.SIGNATURES)
-    assert GEOM_HEADER not in glob.glob(os.path.join(ROOT, "include", "littlegan_hip*.h"))
-    handle = lib.load()
-    for name, (ret, plist) in protos.items():
-        res, args = lib.GEOM_SIGNATURES[name]
-        assert len(args) == len(plist), name
-        for a, decl in zip(args, plist):
-            assert a is _ctype(decl), (name, decl)
-        assert ret == "int" and res is C.c_int
-        fn = getattr(handle, name)
-        assert fn.argtypes == args and fn.restype is res, f"{name}: load() did not bind it"
-    nm = os.path.join("/opt/rocm/lib/llvm/bin", "llvm-nm")
-    nm = nm if os.path.exists(nm) else (shutil.which("llvm-nm") or shutil.which("nm"))
-    if nm:     # (without an nm the getattr above has already found each symbol)
-        out = subprocess.run([nm, "-D", "--defined-only", os.path.join(ROOT, "littlegan_amd", "liblittlegan_hip.so")],
-                             stdout=subprocess.PIPE, text=True, check=True).stdout
-        exported = {line.split()[-1] for line in out.splitlines() if line.split() and line.split()[-1].startswith("lgeo_")}
-        assert exported == set(protos), exported ^ set(protos)
-    covered = {n for r in GC.CASES for n in r.covers}
-    pointer_taking = {n for n, (_, plist) in protos.items() if any("*" in d for d in plist)}
-    assert pointer_taking == set(ENTRY_POINTS) and not pointer_taking - covered, pointer_taking - covered
-    assert all(r.covers and callable(r.run) and callable(r.check) for r in GC.CASES)
-    # geom.hip declares nothing itself and sees the header
-    text = open(os.path.join(ROOT, "littlegan_amd", "csrc", "geom.hip")).read()
-    assert re.search(r'^#include "lg_internal\.h"', text, flags=re.M) and "littlegan_geom.h" in text
-    assert not re.search(r'^extern "C" [^{;]*;', re.sub(r"//[^\n]*", "", text), flags=re.M)
+def test_the_source_includes_the_header_and_is_built():
     from littlegan_amd.csrc import build as B
-    assert "geom.hip" in B.SOURCES
+    assert "littlegan_geom.h" in open(os.path.join(ROOT, "littlegan_amd", "csrc", "geom.hip")).read() and "geom.hip" in B.SOURCES
 
 
 def test_argument_validation_without_gpu(lib):

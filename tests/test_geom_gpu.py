@@ -22,6 +22,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from oracle import np_oracle as O  # noqa: E402
 from oracle import torch_oracle as TO  # noqa: E402
+from guards import called  # noqa: E402
 from test_diffaug_cpu import diffaug_adjoint_np, diffaug_np, diffaug_torch, draw_params  # noqa: E402
 from test_diffaug_gpu import FULL as DIFF_FULL, SMALL, _same_state, dev, dev_key  # noqa: E402
 from test_geom_cpu import (BITS, FULL, IDENTITY, extreme_records, geom_adjoint_np, geom_np, geom_records, geom_torch, key_of,  # noqa: E402
@@ -330,18 +331,7 @@ def test_feature_off_is_the_step_without_the_key(ops, monkeypatch):
     cfg = O.Cfg(**SMALL)
     W = perturbed(cfg, 1)
     inp = dev_inputs(f32_round(O.make_inputs(cfg, cfg.batch_size, seed=5)))
-    fetched = []
-
-    class Recorder:
-        def __init__(self, handle):
-            object.__setattr__(self, "_handle", handle)
-
-        def __getattr__(self, name):
-            fetched.append(name)
-            return getattr(self._handle, name)
-
-    real = ops._lib.load
-    monkeypatch.setattr(ops._lib, "load", lambda *a, **k: Recorder(real(*a, **k)))
+    fetched = called(monkeypatch, ops)
     off, never = build_geo(cfg, W, "f32", geom=""), build(cfg, W, "f32")
     assert not hasattr(make_args(cfg, "f32"), "geom_augment") and off.geom == 0 and not off.augmenting
     for b in (1, 12):

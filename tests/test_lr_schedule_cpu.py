@@ -1,5 +1,5 @@
 """Per-network learning rates and the device-side schedule (lr_g / lr_d / lr_adj, lr_schedule, lr_warmup_steps, lr_decay_steps,
-lr_final_ratio) without a GPU: the header include/littlegan_sched.h held to the three properties of the other headers;
+lr_final_ratio) without a GPU: the names of the header include/littlegan_sched.h;
 every host-side refusal of its four entry points; the configuration keys; the host restatement config.lr_factor that
 tests/test_lr_schedule_gpu.py holds the device to; and a trainer built without a device, whose default path knows nothing of the schedule.
 
@@ -7,20 +7,17 @@ The definition (this project's), in fp64 with k the steps taken so far, W the wa
   up = k < W ? (k + 1) / W : 1      t = k < W ? 0 : min((k - W) / N, 1)      d = 1 | 1 - (1 - r) t | r + (1 - r) 0.5 (1 + cos(pi t))
   s = float32(up d)                 lr_m = float32(base_m) * s"""
 import ctypes as C
-import glob
 import json
 import os
 import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from guards import ABI_NAME  # noqa: E402
-from test_abi import ROOT, _ctype  # noqa: E402
+from guards import called  # noqa: E402
+from test_abi import ROOT, _protos  # noqa: E402
 from test_diffaug_cpu import _cpu_trainer  # noqa: E402
 
 SCHED_HEADER = os.path.join(ROOT, "include", "littlegan_sched.h")
@@ -44,53 +41,18 @@ def lib():
     return _lib
 
 
-def sched_protos():
-    """name -> (return type, [parameter declarations]) of the prototypes of include/littlegan_sched.h"""
-    src = re.sub(r"/\*.*?\*/", "", open(SCHED_HEADER).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"(?:^|\n)\s*(const char\*|int|size_t)\s+(\w+)\s*\((.*?)\)\s*;", src, flags=re.S):
-        ret, name, args = m.group(1), m.group(2), " ".join(m.group(3).split())
-        assert name not in out, f"{name} is declared twice"
-        out[name] = (ret, [] if args in ("", "void") else [a.strip() for a in args.split(",")])
-    return out
+def test_sched_header_declares_the_entry_points(lib):
+    assert set(_protos(SCHED_HEADER)) == set(ENTRY_POINTS) == {n for n in lib.SIGNATURES if n.startswith("lgsch_")}
 
 
-def test_the_ledger_of_the_new_header(lib):
-    """The three properties tests/test_rel_cpu.py::test_the_ledger_of_the_new_header holds its header to, for include/littlegan_sched.h:
-    declared == bound with the declared types; exported and bound by load(); every pointer-taking function has a guard-band row."""
-    import test_lr_schedule_gpu as SG
-    protos = sched_protos()
-    assert set(protos) == set(lib.SCHED_SIGNATURES) == set(ENTRY_POINTS)
-    assert all(n.startswith("lgsch_") and not re.fullmatch(ABI_NAME, n) for n in protos)     # outside the closed ABI table
-    assert not set(lib.SCHED_SIGNATURES) & (set(lib.SIGNATURES) | set(lib.GEOM_SIGNATURES) | set(lib.REL_SIGNATURES))
-    assert SCHED_HEADER not in glob.glob(os.path.join(ROOT, "include", "littlegan_hip*.h"))
-    handle = lib.load()
-    for name, (ret, plist) in protos.items():
-        res, args = lib.SCHED_SIGNATURES[name]
-        assert len(args) == len(plist), name
-        for a, decl in zip(args, plist):
-            assert a is _ctype(decl), (name, decl)
-        assert res is {"int": C.c_int, "size_t": C.c_size_t}[ret], name
-        fn = getattr(handle, name)
-        assert fn.argtypes == args and fn.restype is res, f"{name}: load() did not bind it"
-    assert handle.lg_abi_version() == 1
-    nm = os.path.join("/opt/rocm/lib/llvm/bin", "llvm-nm")
-    nm = nm if os.path.exists(nm) else (shutil.which("llvm-nm") or shutil.which("nm"))
-    if nm:     # (without an nm the getattr above has already found each symbol)
-        out = subprocess.run([nm, "-D", "--defined-only", os.path.join(ROOT, "littlegan_amd", "liblittlegan_hip.so")],
-                             stdout=subprocess.PIPE, text=True, check=True).stdout
-        exported = {line.split()[-1] for line in out.splitlines() if line.split() and line.split()[-1].startswith("lgsch_")}
-        assert exported == set(protos), exported ^ set(protos)
-    covered = {n for r in SG.CONTRACT_CASES for n in r.covers}
-    pointer_taking = {n for n, (_, plist) in protos.items() if any("*" in d for d in plist)}
-    assert pointer_taking == set(ENTRY_POINTS) and not pointer_taking - covered, pointer_taking - covered
-    # the Adam variants sit beside clip_adam_element, which stays the one definition of the arithmetic; the schedule kernel has a
-    # file of its own; both see the header, neither declares anything itself
+def test_the_sources_include_the_header_and_are_built():
     from littlegan_amd.csrc import build as B
     for name in ("loss_optim.hip", "sched.hip"):
-        text = open(os.path.join(ROOT, "littlegan_amd", "csrc", name)).read()
-        assert re.search(r'^#include "lg_internal\.h"', text, flags=re.M) and "littlegan_sched.h" in text and name in B.SOURCES
-        assert not re.search(r'^extern "C" [^{;]*;', re.sub(r"//[^\n]*", "", text), flags=re.M)
+        assert "littlegan_sched.h" in open(os.path.join(ROOT, "littlegan_amd", "csrc", name)).read() and name in B.SOURCES
+
+
+def test_the_adam_arithmetic_is_written_once():
+    """the Adam variants sit beside clip_adam_element, which stays the one definition of the arithmetic"""
     lo = open(os.path.join(ROOT, "littlegan_amd", "csrc", "loss_optim.hip")).read()
     assert len(re.findall(r"\bfloat clip_adam_element\(", lo)) == 1
     assert len(re.findall(r"sqrtf\(vv\) \+ eps", lo)) == 1                                   # the update is written once
@@ -282,21 +244,9 @@ def test_host_restatement():
 
 # ---------------------------------------------------------------------------------------------------------------------
 # a trainer without a device
-class _Recorder:
-    def __init__(self, handle, names):
-        object.__setattr__(self, "_handle", handle)
-        object.__setattr__(self, "_names", names)
-
-    def __getattr__(self, name):
-        self._names.append(name)
-        return getattr(self._handle, name)
-
-
 def test_the_default_path_knows_nothing_of_the_schedule(monkeypatch):
     from littlegan_amd import ops
-    names = []
-    real = ops._lib.load
-    monkeypatch.setattr(ops._lib, "load", lambda *a, **k: _Recorder(real(*a, **k), names))
+    names = called(monkeypatch, ops)
     base, cfg = _cpu_trainer()
     assert base.lr_state is None and base.lr_now() is None and base.lr_sched["device"] is False
     assert [base.opt_cfg[m][0] for m in "GDA"] == [float(F32(cfg.lr))] * 3

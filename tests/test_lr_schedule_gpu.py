@@ -1,11 +1,10 @@
 """Per-network learning rates and the device-side schedule on the device: lgsch_step against the host restatement
 (config.lr_factor) at every edge of warm-up, decay and the counter's saturation; the two Adam passes that read their rate from device
-memory against the existing ones, bit for bit, at the one-block, block-edge and grid-stride edges of a 4096 x 256 grid; the memory
-contract of the four entry points with the guard bands of tests/guards.py (CONTRACT_CASES: one row per pointer-taking entry point); and
+memory against the existing ones, bit for bit, at the one-block, block-edge and grid-stride edges of a 4096 x 256 grid; (their memory
+contract: the sched-* rows of tests/test_memory_contract_gpu.py); and
 whole training steps: against a trainer whose rates are set on the host before every step, through replayed graphs, across a checkpoint,
 with the keys at their defaults, with rates per network alone, with the weight average, and on two data-parallel ranks."""
 import os
-import re
 import sys
 
 import numpy as np
@@ -15,10 +14,9 @@ import torch.multiprocessing as mp
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from oracle import np_oracle as O  # noqa: E402
-from guards import ABI_NAME, describe, exact_workspaces  # noqa: E402
+from guards import called  # noqa: E402
 from test_dp_gpu import CFG as DP_CFG, _free_port, _join_all  # noqa: E402
 from test_lr_schedule_cpu import KINDS, NS, RS, WS, settings  # noqa: E402
-from test_memory_contract_gpu import Alloc, Row, _diff, _stale  # noqa: E402
 from test_step_gpu import dev_inputs, f32_round, load_weights, make_args, perturbed  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -41,27 +39,6 @@ def _bits(t):
 
 def _np_bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
-
-
-class _Recorder:
-    """every name of the C ABI and of the lgsch_ header that a piece of code fetched from the library handle (guards.called records the
-    closed ABI pattern alone, which the lgsch_ names are outside of)"""
-
-    def __init__(self, handle, names):
-        object.__setattr__(self, "_handle", handle)
-        object.__setattr__(self, "_names", names)
-
-    def __getattr__(self, name):
-        if name.startswith("lgsch_") or re.fullmatch(ABI_NAME, name):
-            self._names.append(name)
-        return getattr(self._handle, name)
-
-
-def fetched(monkeypatch, ops):
-    names = []
-    real = ops._lib.load
-    monkeypatch.setattr(ops._lib, "load", lambda *a, **k: _Recorder(real(*a, **k), names))
-    return names
 
 
 # ---------------------------------------------------------------------------------------------------------------- lgsch_step
@@ -190,113 +167,6 @@ def test_ema_adam_variant_is_bit_identical(ops, n):
                 assert not torch.equal(runs[0][3], d["ema"]) and (lo == hi) == torch.equal(runs[0][0], d["w"])
 
 
-# ---------------------------------------------------------------------------------------------------------------- memory contract
-CONTRACT_CASES = []
-ROW_SETTINGS = dict(schedule="cosine", W=3, N=7, r=0.1)
-
-
-def _init_row(k0):
-    def run(ops, alloc):
-        return dict(state=ops.sched_init(k0, out=alloc.out("state", (8,))))
-
-    def check(res):
-        assert _bits(res["state"]).tolist() == [k0, 0, 0, 0, 0, 0, 0, 0]
-
-    CONTRACT_CASES.append(Row(f"init-{k0}", ("lgsch_init",), run, check))
-
-
-def _step_row(k):
-    def run(ops, alloc):
-        c = settings(ROW_SETTINGS["schedule"], W=ROW_SETTINGS["W"], N=ROW_SETTINGS["N"], r=ROW_SETTINGS["r"], **RATES)
-        words = np.array([k, 0, 0, 0, 0, 0, 0, 0], np.int32).view(np.float32)
-        state = alloc.state("state", words)
-        ops.sched_step(state, c["kind"], c["warmup"], c["decay"], c["final_ratio"], c["lr_g"], c["lr_d"], c["lr_adj"])
-        return dict(state=state)
-
-    def check(res):
-        from littlegan_amd import config
-        c = settings(ROW_SETTINGS["schedule"], W=ROW_SETTINGS["W"], N=ROW_SETTINGS["N"], r=ROW_SETTINGS["r"], **RATES)
-        got = _bits(res["state"])
-        assert got[0] == k + 1 and not got[5:].any() and abs(int(got[1]) - int(_np_bits([config.lr_factor(k, c)])[0])) <= 1
-        s = res["state"].cpu().numpy()[1]
-        assert got[2:5].tolist() == _np_bits([F32(c[m]) * s for m in ("lr_g", "lr_d", "lr_adj")]).tolist()
-
-    CONTRACT_CASES.append(Row(f"step-{k}", ("lgsch_step",), run, check))
-
-
-def _adam_row(n, ema):
-    def data():
-        rng = np.random.default_rng(900 + n)
-        return {k: rng.standard_normal(n).astype(np.float32) * sc for k, sc in (("w", 1.0), ("g", 1.0), ("m", 0.1), ("e", 1.0))}, \
-            np.abs(rng.standard_normal(n)).astype(np.float32) * 0.1
-
-    lo, hi = (4 * (n // 12), 4 * (n // 6)) if ema else (0, n)
-
-    def run(ops, alloc):
-        d, v0 = data()
-        w, m, v = alloc.state("w", d["w"]), alloc.state("m", d["m"]), alloc.state("v", v0)
-        g, st, lr = alloc.inp("g", d["g"]), alloc.inp("adam_state", np.array([0.25, 0.81], np.float32)), alloc.inp("lr", np.array([1e-2], np.float32))
-        if not ema:
-            ops.sched_clip_adam_update(w, g, m, v, st, lr, B1, B2, EPS, 0.5, 0.5)
-            return dict(w=w, m=m, v=v)
-        e = alloc.state("ema", d["e"])
-        count = alloc.inp("ema_state", np.array([7], np.int32))
-        ops.sched_clip_adam_ema_update(w, g, m, v, e, lo, hi, st, count, lr, B1, B2, EPS, 0.5, 0.5, 0.99)
-        return dict(w=w, m=m, v=v, ema=e)
-
-    def check(res):
-        from littlegan_amd import ops
-        d, v0 = data()
-        dev = lambda a: torch.from_numpy(a).cuda()
-        w, m, v, g, e = dev(d["w"]), dev(d["m"]), dev(v0), dev(d["g"]), dev(d["e"])
-        st = torch.tensor([0.25, 0.81], dtype=torch.float32, device="cuda")
-        if ema:
-            ops.clip_adam_ema_update(w, g, m, v, e, lo, hi, st, torch.tensor([7], dtype=torch.int32, device="cuda"), 1e-2, B1, B2, EPS, 0.5, 0.5, 0.99)
-            assert torch.equal(_t(res["ema"]), _t(e)) and 0 < lo < hi < n
-        else:
-            ops.clip_adam_update(w, g, m, v, st, 1e-2, B1, B2, EPS, 0.5, 0.5)
-        assert torch.equal(_t(res["w"]), _t(w)) and torch.equal(_t(res["m"]), _t(m)) and torch.equal(_t(res["v"]), _t(v))
-
-    CONTRACT_CASES.append(Row(f"adam{'-ema' if ema else ''}-{n}", ("lgsch_clip_adam_ema_update" if ema else "lgsch_clip_adam_update",), run, check))
-
-
-_init_row(5)
-_step_row(6)        # strictly inside the cosine decay
-_adam_row(257, False)
-_adam_row(1028, True)
-
-
-def _once(row_, ops, monkeypatch, mode, byte=0xFF):
-    alloc = Alloc(mode, byte)
-    with monkeypatch.context() as mp_:
-        ws = exact_workspaces(mp_, ops, fill=byte) if mode == "guard" else None
-        names = fetched(mp_, ops)
-        res = dict(row_.run(ops, alloc))
-        torch.cuda.synchronize()
-    return res, alloc, ws, set(names)
-
-
-@pytest.mark.parametrize("case", CONTRACT_CASES, ids=lambda r: r.id)
-def test_sched_memory_contract(case, ops, monkeypatch):
-    plain, _, _, names = _once(case, ops, monkeypatch, "plain")
-    missing = set(case.covers) - names
-    assert not missing, f"the row claims entry points it never fetched: {sorted(missing)} (fetched {sorted(names)})"
-    plain2, _, _, _ = _once(case, ops, monkeypatch, "plain")
-    d = _diff("two plain runs differ (the op is not reproducible; nothing below can be read)", plain, plain2)
-    assert not d, d
-    for tag, byte in (("A (0xFF)", 0xFF), ("B (0x00)", 0x00), ("C (0x3F)", 0x3F)):
-        got, alloc, ws, _ = _once(case, ops, monkeypatch, "guard", byte)
-        bad = alloc.problems() + [f"{what}: written outside its advertised size: {describe(offs)}" for what, offs in ws.damaged()]
-        assert not bad, f"run {tag}: " + " | ".join(bad)
-        assert not ws.handed      # no entry point of this header takes a workspace
-        if byte == 0xFF:
-            stale = _stale(plain, got)
-            assert not stale, f"run {tag}: " + " | ".join(stale)
-        d = _diff(f"run {tag} differs from the plain run (foreign bytes or stale output contents show in the result)", plain, got)
-        assert not d, d
-    case.check(plain)
-
-
 # ---------------------------------------------------------------------------------------------------------------- whole steps
 SCHED_KW = dict(lr_schedule="linear", lr_warmup_steps=2, lr_decay_steps=6, **RATES)
 STEPS = tuple(range(7, 15))      # 10 is a partition step; from 11 on the Adjuster trains
@@ -352,7 +222,7 @@ def _eager_run(ema=False):
 def _against_host_set_rates(ops, monkeypatch, ema):
     from littlegan_amd import config
     with monkeypatch.context() as mp_:
-        names = fetched(mp_, ops)
+        names = called(mp_, ops)
         cfg, W, snaps, tr = _eager_run(ema)
         names = list(names)
     assert tr.lr_state is not None and tr.lr_sched["device"] and tr.lr_now().shape == (3,)
@@ -398,7 +268,7 @@ def test_graph_replay_walks_the_schedule(ops, monkeypatch):
     kinds = [tg.step_kind(b) for b in STEPS]
     for k, b in enumerate(STEPS):
         with monkeypatch.context() as mp_:
-            names = fetched(mp_, ops)
+            names = called(mp_, ops)
             tg.graph_step(b, dev_inputs(_step_inputs(cfg, b)))
             torch.cuda.synchronize()
         assert not names or names[0] == "lgsch_step", (b, names[:3])      # the step's first launch (a replay fetches nothing)
@@ -450,7 +320,7 @@ def test_defaults_have_no_state_and_the_parents_bits(ops, monkeypatch):
     seen = []
     for tr in (absent, off):
         with monkeypatch.context() as mp_:
-            names = fetched(mp_, ops)
+            names = called(mp_, ops)
             for b in (1, 5, 12):
                 tr.train_step_from_inputs(b, dev_inputs(_step_inputs(cfg, b)))
             torch.cuda.synchronize()
@@ -465,7 +335,7 @@ def test_rates_per_network_alone(ops, monkeypatch):
     W = perturbed(cfg, 2)
     base, other = _build(cfg, W), _build(cfg, W, lr_d=4 * cfg.lr)
     assert other.lr_state is None and other.opt_cfg["D"][0] == float(F32(4 * cfg.lr)) and other.opt_cfg["G"] == base.opt_cfg["G"]
-    names = fetched(monkeypatch, ops)
+    names = called(monkeypatch, ops)
     inp = dev_inputs(_step_inputs(cfg, 12))
     before = base.store.flat.clone()
     base.train_step_from_inputs(12, inp)

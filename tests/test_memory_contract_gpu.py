@@ -13,12 +13,13 @@ still reaches the kernel it names.  `alloc` hands it every device buffer.  The t
 and asserts  1. control: plain == plain2 bit for bit;  2. same route: the advertised workspace size selects the kernel the pool
 selects (lg_last_kernel after every call of the chain);  3. same bits: every result of A, B and C equals plain — the result does not
 depend on bytes outside the inputs, nor on what the workspace or the outputs held before;  4. nothing else touched: every red zone
-intact, every input bit-identical to what went in;  5. everything written: no output element of A still holds 0xFF..FF where the
+intact, every input bit-identical to what went in (and, for a row with exact_sizing, the workspaces handed over are exactly its sizing
+entries);  5. everything written: no output element of A still holds 0xFF..FF where the
 plain result is finite;  6. oracle: plain against oracle/np_oracle.py (or the op's bit-exact restatement) at the tolerances the op
 has in its own test module — imported from there, none is introduced here.
 
 Each row names the entry points it covers; tests/test_guards_cpu.py checks that every pointer-taking function of the C ABI (every
-include/littlegan_hip*.h) is named by a row or listed in EXEMPT with its reason, so a new entry point fails there until it gets a row."""
+include/littlegan_*.h) is named by a row or listed in EXEMPT with its reason, so a new entry point fails there until it gets a row."""
 import ctypes
 import functools
 import os
@@ -51,6 +52,12 @@ from test_ada_gpu import FULL, PER_ROW, heads_mix, u32, words  # noqa: E402
 from test_gan_loss_cpu import (EXACT_LOSS0 as GAN_LOSS0, EXACT_W_PR, KIND_NO, ROLE_D_FAKE, ROLE_D_REAL, ROLE_G,  # noqa: E402
                                exact_case)
 from test_gan_loss_gpu import HEADS_CASES as LOGIT_HEADS_CASES, _heads_data, _heads_operands  # noqa: E402
+from test_geom_cpu import FULL as GEOM_FULL, extreme_records as geom_extreme_records, geom_adjoint_np, geom_np, geom_records, key_of, usable  # noqa: E402
+from test_rel_cpu import EXACT_LOSS0 as PAIR_LOSS0, EXACT_W_PR as PAIR_W_PR, KIND_NO as PAIR_KIND_NO, SIDE_OTHER, SIDE_SELF, exact_pair_case  # noqa: E402
+from test_rel_gpu import W_FAKE, _seed_halves  # noqa: E402
+from test_lr_schedule_cpu import settings as sched_settings  # noqa: E402
+from test_lr_schedule_gpu import B1, B2, EPS, RATES  # noqa: E402
+from test_adj_fused_gpu import hand_moments  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -155,10 +162,12 @@ class Trace:
 class Row:
     """id; covers: the entry points the row runs; run(ops, alloc) -> dict of results (tensors, or plain Python values; "_route":
     the Trace); check(res): the oracle comparison of the plain results; route: substrings the plain route must contain; sizing:
-    [(*_workspace_bytes name, args)] of the workspaces the row uses; wgrad: (B, Hs, Ws, cb, cs, dtype) of a conv weight gradient."""
+    [(*_workspace_bytes name, args)] of the workspaces the row uses; wgrad: (B, Hs, Ws, cb, cs, dtype) of a conv weight gradient;
+    exact_sizing: the guarded runs are handed exactly one workspace per sizing entry, of that size (an older row may list a size once
+    and take it several times, or take the heads' workspace without an entry)."""
 
-    def __init__(self, id, covers, run, check=None, route=(), sizing=(), wgrad=None):
-        self.id, self.covers, self.run, self.check = id, tuple(covers), run, check
+    def __init__(self, id, covers, run, check=None, route=(), sizing=(), wgrad=None, exact_sizing=False):
+        self.id, self.covers, self.run, self.check, self.exact_sizing = id, tuple(covers), run, check, exact_sizing
         self.route = (route,) if isinstance(route, str) else tuple(route)
         self.sizing, self.wgrad = list(sizing), wgrad
         if wgrad is not None:
@@ -252,6 +261,10 @@ def test_memory_contract(case, ops, monkeypatch):
         # 4. nothing else touched
         bad = alloc.problems() + [f"{what}: written outside its advertised size: {describe(offs)}" for what, offs in ws.damaged()]
         assert not bad, f"run {tag}: " + " | ".join(bad)
+        if case.exact_sizing:   # the workspaces handed over are the row's sizing entries, no more and no fewer (none for a row without one)
+            handed = sorted(nb for _, nb, _ in ws.handed)
+            sized = sorted(int(getattr(ops._lib.load(), fn)(*args)) for fn, args in case.sizing)
+            assert handed == sized, f"run {tag}: workspaces of {handed} bytes handed over, the sizing entries give {sized}"
         # 5. everything written
         if byte == 0xFF:
             stale = _stale(plain, got)
@@ -1918,3 +1931,320 @@ heads_logit_row(LOGIT_HEADS_CASES[0])
 gan_loss_row("hinge", ROLE_D_REAL, 1, 1)
 gan_loss_row("lsgan", ROLE_D_FAKE, 4, 3)
 gan_loss_row("wgan", ROLE_G, 1024, 40)
+
+
+# ------------------------------------------------------------------------------------------------------------------ geometric augmentation
+def geom_draw_row():
+    """the draw, plain and gated, against the restatement of tests/test_geom_cpu.py at the bound of tests/test_geom_gpu.py"""
+    rows, S, seed_arg, step = 300, 16, 3, 7        # two blocks of the one-thread-per-row launch, the second partly empty
+    seed, koff = key_of(seed_arg, 1, step)
+
+    def run(ops, alloc):
+        key = alloc.inp("key", np.array([seed, koff], np.int64))
+        state = alloc.inp("state", np.array([0.3, 0, 0, 0], np.float32))
+        return {"plain": ops.geom_draw(key, 1, 5, rows, S, GEOM_FULL, out=alloc.out("geo", (rows, 4))),
+                "gated": ops.geom_draw(key, 0, 0, rows, S, GEOM_FULL, state=state, out=alloc.out("geo_gated", (rows, 4)))}
+
+    def check(res):
+        for name, want in (("plain", geom_records(seed, koff, 1, 5, rows, S, GEOM_FULL)),
+                           ("gated", geom_records(seed, koff, 0, 0, rows, S, GEOM_FULL, p=0.3))):
+            got = res[name].cpu().numpy()
+            assert (np.abs(got.astype(np.float64) - want) <= 2.0 ** -23 * np.maximum(1, np.abs(want))).all(), name
+            exact = (np.abs(want) == 1) | (want == 0)        # what a selected identity leaves
+            assert np.array_equal(got[exact], want[exact]), name
+
+    row("geom-draw-300", ("lgeo_draw",), run, check, exact_sizing=True)
+
+
+def geom_map_row(id_, S, recs, seed):
+    """Geo and its adjoint: lgeo_fwd within 8 2^-24 max|x| per row of the restatement (one rounding per weight product, per term, per
+    add), lgeo_bwd within (n + 3) 2^-24 sum |w g| per source pixel of the scatter restatement; an unusable record gives zeros"""
+    B = len(recs)
+    rng = np.random.default_rng(seed)
+    x = rng.uniform(-1, 1, (B, S, S, 3)).astype(np.float32)
+    g = rng.uniform(-1, 1, (B, S, S, 3)).astype(np.float32)
+
+    def run(ops, alloc):
+        geo = alloc.inp("geo", recs)
+        return {"out": ops.geom_fwd(alloc.inp("x", x), geo, out=alloc.out("out", x.shape)),
+                "gx": ops.geom_bwd(alloc.inp("g", g), geo, out=alloc.out("gx", g.shape))}
+
+    def check(res):
+        assert torch.isfinite(res["out"]).all() and torch.isfinite(res["gx"]).all()
+        err = np.abs(f64(res["out"]) - geom_np(x, recs)).reshape(B, -1).max(1)
+        bound = 8 * 2.0 ** -24 * np.abs(x).reshape(B, -1).max(1)
+        assert (err <= bound).all(), (err, bound)
+        ref, cnt, mag = geom_adjoint_np(g, recs, stats=True)
+        bound = (cnt[..., None] + 3) * 2.0 ** -24 * mag
+        assert (np.abs(f64(res["gx"]) - ref) <= bound).all(), float((np.abs(f64(res["gx"]) - ref) - bound).max())
+        dead = [n for n, r in enumerate(recs) if not usable(r)]
+        assert not res["out"][dead].any() and not res["gx"][dead].any()
+
+    row(id_, ("lgeo_fwd", "lgeo_bwd"), run, check, exact_sizing=True)
+
+
+def geom_arbitrary_records():
+    """Record bits a kernel has to survive: random 32-bit patterns (NaN, infinities, every exponent), entries with random mantissas near
+    1, nearly singular matrices at both sides of the 2^-20 bound, huge entries with a finite determinant, denormals and negative zeros.
+    The records are device data that the host cannot validate, so the kernels compare every coordinate as a float before it becomes an
+    index: the row checks that property (nothing read outside x, nothing written outside out)."""
+    rng = np.random.default_rng(2026)
+    recs = [rng.integers(0, 1 << 32, 4, dtype=np.uint64).astype(np.uint32).view(np.float32) for _ in range(8)]
+    recs += [rng.uniform(-1.5, 1.5, 4).astype(np.float32) for _ in range(4)]
+    recs += [np.array(r, np.float32) for r in (
+        [1, 1, 1, 1 + 2.0 ** -19], [1, 1, 1, 1 + 2.0 ** -21], [2.0 ** -9, 0, 0, 2.0 ** -9], [1e30, 0, 0, 1e-30], [1e30, -1e30, 1, 0],
+        [3e38, 3e38, -3e38, 3e38], [1e-40, 0, 0, 1e-40], [-0.0, 1, -1, -0.0], [np.nan] * 4, [np.inf, 0, 0, -np.inf], [0, 0, 0, 0],
+        [1e19, 1, 1e-19, 1], [512, 0, 0, 2.0 ** -9])]
+    return np.stack(recs).astype(np.float32)
+
+
+geom_draw_row()
+geom_map_row("geom-extreme-records-16", 16, geom_extreme_records(), 11)
+geom_map_row("geom-arbitrary-records-8", 8, geom_arbitrary_records(), 12)
+geom_map_row("geom-workload-row-128", 128, geom_extreme_records()[[0, 10]], 13)      # the workload's row length: many blocks, the row stride
+
+
+# ------------------------------------------------------------------------------------------------------------------ relativistic pairing, R1 + R2
+def rel_pair_row(kind, side, n, m, c):
+    """the pairing loss in exact arithmetic: tests/test_rel_gpu.py (data: tests/test_rel_cpu.py)"""
+    def run(ops, alloc):
+        p, t_c = _heads_data(n, c, 23 * n + c)
+        z, zr, _, _ = exact_pair_case(kind, side, n, m)
+        loss, dz = alloc.state("loss", np.array([PAIR_LOSS0], np.float32)), alloc.out("dz", (n, 1 + c))
+        ops.pair_heads_loss(alloc.inp("p", p.astype(np.float32)), alloc.inp("z", z), alloc.inp("z_ref", zr), alloc.inp("t_c", t_c.astype(np.float32)),
+                            PAIR_KIND_NO[kind], side, PAIR_W_PR, 1.0, loss, dz, True)
+        return dict(loss=loss, dz=dz)
+
+    def check(res):
+        p, t_c = _heads_data(n, c, 23 * n + c)
+        _, _, dz_w, term_w = exact_pair_case(kind, side, n, m)
+        assert torch.equal(res["dz"][:, 0].cpu(), torch.from_numpy(dz_w))
+        exp = PAIR_LOSS0 + float(term_w) + O.bce_mean(t_c, p[:, 1:])
+        assert abs(float(res["loss"]) - exp) < 2e-6 * abs(exp) + 1e-6
+        assert rel(res["dz"][:, 1:], O.bce_mean_bwd(t_c, p[:, 1:]) * p[:, 1:] * (1 - p[:, 1:])) < 1e-5
+
+    row(f"rel-pair-{kind}-{side}-{n}x{m}x{c}", ("lgrel_pair_heads_loss_fwd_bwd",), run, check, exact_sizing=True)
+
+
+def rel_seed_row(B, L):
+    """the joint R1 + R2 seed bit for bit: the exact case of tests/test_r1_cpu.py as the real half, tests/test_rel_gpu.py::_seed_halves"""
+    def run(ops, alloc):
+        g = alloc.inp("g", _seed_halves(B, L)[0])
+        loss = alloc.state("loss", np.array([R1_LOSS0], np.float32))
+        r1l, r2l = alloc.out("r1_loss", (1,)), alloc.out("r2_loss", (1,))
+        u0, r2 = alloc.out("u0", (2 * B, L)), alloc.out("r2", (2 * B,))
+        lib = ops._lib.load()
+        ws = ops.workspace(int(lib.lgrel_r12_workspace_bytes(B, L)), g.device, "r1")   # (the wrapper allocates its outputs: guarded ones here)
+        ops._lib.check(lib.lgrel_r12_seed(g.data_ptr(), u0.data_ptr(), r2.data_ptr(), loss.data_ptr(), r1l.data_ptr(), r2l.data_ptr(), EXACT_WEIGHT,
+                                          W_FAKE, ws.data_ptr(), ws.numel(), B, L, torch.cuda.current_stream().cuda_stream), "lgrel_r12_seed")
+        return dict(u0=u0, r2=r2, loss=loss, r1_loss=r1l, r2_loss=r2l)
+
+    def check(res):
+        _, u0, r2, t1, t2, loss = _seed_halves(B, L)
+        assert np.array_equal(i32(res["u0"]), np_i32(u0)) and np.array_equal(i32(res["r2"]), np_i32(r2))
+        assert np.array_equal(i32(res["r1_loss"]), np_i32([t1])) and np.array_equal(i32(res["r2_loss"]), np_i32([t2]))
+        assert np.array_equal(i32(res["loss"]), np_i32([loss]))
+
+    row(f"rel-r12-seed-{B}x{L}", ("lgrel_r12_seed",), run, check, sizing=[("lgrel_r12_workspace_bytes", (B, L))], exact_sizing=True)
+
+
+rel_pair_row("hinge", SIDE_SELF, 1, 1, 1)
+rel_pair_row("lsgan", SIDE_OTHER, 6, 3, 3)
+rel_seed_row(1, 4)
+rel_seed_row(4, 4100)
+
+
+# ------------------------------------------------------------------------------------------------------------------ learning-rate schedule
+def sched_init_row(k0):
+    def run(ops, alloc):
+        return dict(state=ops.sched_init(k0, out=alloc.out("state", (8,))))
+
+    def check(res):
+        assert i32(res["state"]).tolist() == [k0, 0, 0, 0, 0, 0, 0, 0]
+
+    row(f"sched-init-{k0}", ("lgsch_init",), run, check, exact_sizing=True)
+
+
+def sched_step_row(k):
+    """one step of the schedule against config.lr_factor: tests/test_lr_schedule_gpu.py"""
+    def run(ops, alloc):
+        c = sched_settings("cosine", W=3, N=7, r=0.1, **RATES)
+        words_ = np.array([k, 0, 0, 0, 0, 0, 0, 0], np.int32).view(np.float32)
+        state = alloc.state("state", words_)
+        ops.sched_step(state, c["kind"], c["warmup"], c["decay"], c["final_ratio"], c["lr_g"], c["lr_d"], c["lr_adj"])
+        return dict(state=state)
+
+    def check(res):
+        from littlegan_amd import config
+        c = sched_settings("cosine", W=3, N=7, r=0.1, **RATES)
+        got = i32(res["state"])
+        assert got[0] == k + 1 and not got[5:].any() and abs(int(got[1]) - int(np_i32([config.lr_factor(k, c)])[0])) <= 1
+        s = res["state"].cpu().numpy()[1]
+        assert got[2:5].tolist() == np_i32([np.float32(c[m]) * s for m in ("lr_g", "lr_d", "lr_adj")]).tolist()
+
+    row(f"sched-step-{k}", ("lgsch_step",), run, check, exact_sizing=True)
+
+
+def sched_adam_row(n, ema):
+    """the Adam passes that read their rate from device memory, bit for bit against the ones that take it as a scalar"""
+    def data():
+        rng = np.random.default_rng(900 + n)
+        return {k: rng.standard_normal(n).astype(np.float32) * sc for k, sc in (("w", 1.0), ("g", 1.0), ("m", 0.1), ("e", 1.0))}, \
+            np.abs(rng.standard_normal(n)).astype(np.float32) * 0.1
+
+    lo, hi = (4 * (n // 12), 4 * (n // 6)) if ema else (0, n)
+
+    def run(ops, alloc):
+        d, v0 = data()
+        w, m, v = alloc.state("w", d["w"]), alloc.state("m", d["m"]), alloc.state("v", v0)
+        g, st, lr = alloc.inp("g", d["g"]), alloc.inp("adam_state", np.array([0.25, 0.81], np.float32)), alloc.inp("lr", np.array([1e-2], np.float32))
+        if not ema:
+            ops.sched_clip_adam_update(w, g, m, v, st, lr, B1, B2, EPS, 0.5, 0.5)
+            return dict(w=w, m=m, v=v)
+        e = alloc.state("ema", d["e"])
+        count = alloc.inp("ema_state", np.array([7], np.int32))
+        ops.sched_clip_adam_ema_update(w, g, m, v, e, lo, hi, st, count, lr, B1, B2, EPS, 0.5, 0.5, 0.99)
+        return dict(w=w, m=m, v=v, ema=e)
+
+    def check(res):
+        from littlegan_amd import ops
+        d, v0 = data()
+        dev = lambda a: torch.from_numpy(a).cuda()   # noqa: E731
+        w, m, v, g, e = dev(d["w"]), dev(d["m"]), dev(v0), dev(d["g"]), dev(d["e"])
+        st = torch.tensor([0.25, 0.81], dtype=torch.float32, device="cuda")
+        if ema:
+            ops.clip_adam_ema_update(w, g, m, v, e, lo, hi, st, torch.tensor([7], dtype=torch.int32, device="cuda"), 1e-2, B1, B2, EPS, 0.5, 0.5, 0.99)
+            assert _same(res["ema"], e) and 0 < lo < hi < n
+        else:
+            ops.clip_adam_update(w, g, m, v, st, 1e-2, B1, B2, EPS, 0.5, 0.5)
+        assert _same(res["w"], w) and _same(res["m"], m) and _same(res["v"], v)
+
+    row(f"sched-adam{'-ema' if ema else ''}-{n}", ("lgsch_clip_adam_ema_update" if ema else "lgsch_clip_adam_update",), run, check,
+        exact_sizing=True)
+
+
+sched_init_row(5)
+sched_step_row(6)        # strictly inside the cosine decay
+sched_adam_row(257, False)
+sched_adam_row(1028, True)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the Adjuster's fused forward
+@functools.lru_cache(maxsize=None)
+def _records16(ops, seed, shape, scale, shift, gamma, beta):
+    """a bf16 map (seeded) and its finished statistics records, from the library's own statistics pass on its fp32 value -> CPU tensors.
+    Cached: the pass runs once, in the row's first run, on the pooled workspace, and never between guard bands."""
+    a = bf(arr(seed, *shape, scale=scale, shift=shift))
+    gm, bt = (torch.tensor([v], dtype=F32, device="cuda") for v in (gamma, beta))
+    return a, ops.instnorm_stats(a.cuda().float(), gm, bt, 0, ALPHA).cpu()
+
+
+def _stored_map(ops, z, stats):
+    """the bf16 map the encoder's apply pass stores for a raw level (z, records)"""
+    h = torch.empty_like(z)
+    ops.instnorm_apply(z, stats, None, 0, 1, ALPHA, out16=h, want_f32=False)
+    return h
+
+
+def adj_fused_row(cs, cb, Hs, Ws):
+    """lgadj_convT_s2_fwd_stats_ns with an uneven split of a raw and a stored skip part, bit for bit against the route through the
+    stored maps (instnorm_apply per skip part + convT_s2_fwd_stats): tests/test_adj_fused_gpu.py"""
+    B, b1 = 3, 1
+    s = crc("adj-fused", cs, cb, Hs, Ws)
+    nbytes = _stats_bytes(True, B, Hs, Ws, cb)
+
+    def data(ops):
+        z, zst = _records16(ops, s, (B, Hs, Ws, cs), 1.3, 0.2, 0.9, 0.15)
+        s0, s0st = _records16(ops, s + 1, (b1, Hs, Ws, cs), 0.8, -0.3, 1.1, -0.2)
+        return z, zst, s0, s0st, bf(arr(s + 2, B - b1, Hs, Ws, cs)), arr(s + 3, 5, 5, cb, cs, scale=0.05), arr(s + 4, cb, scale=0.2)
+
+    def run(ops, alloc):
+        z, zst, s0, s0st, s1, w, b = data(ops)
+        tr = Trace(ops)
+        lib, P = ops._lib.load(), lambda v: v.data_ptr()   # noqa: E731
+        zd, zstd = alloc.inp("z16", z), alloc.inp("z_stats", zst)
+        s0d, s0std, s1d = alloc.inp("skip0", s0), alloc.inp("skip0_stats", s0st), alloc.inp("skip1", s1)
+        pack, bd = _pack(ops, alloc, w, cb, cs, 1), alloc.inp("bias", b)
+        gm, bt = _gb(alloc, 1.2, -0.1)
+        out, stats = alloc.out("out16", (B, 2 * Hs, 2 * Ws, cb), BF16), alloc.out("stats", (B, 8))
+        want = int(getattr(lib, nbytes[0])(*nbytes[1]))
+        ws = ops.workspace(want, zd.device, "statpart")          # (the wrapper allocates its outputs: guarded ones here)
+        nparts, st_ = ctypes.c_int(0), torch.cuda.current_stream().cuda_stream
+        ops._lib.check(lib.lgadj_convT_s2_fwd_stats_ns(P(zd), P(zstd), ALPHA, P(s0d), P(s0std), P(s1d), 0, b1, P(pack), P(bd), P(out), B, Hs, Ws,
+                                                       cb, cs, 1, P(ws), ws.numel(), ctypes.addressof(nparts), st_), "lgadj_convT_s2_fwd_stats_ns")
+        tr("fwd")
+        ops._lib.check(lib.lg_instnorm_stats_finalize(P(ws), nparts.value, P(stats), P(gm), P(bt), B, st_), "lg_instnorm_stats_finalize")
+        return dict(pack=pack, out16=out, stats=stats, nparts=nparts.value, ws_bytes=want, _route=tr)
+
+    def check(res):
+        from littlegan_amd import ops
+        z, zst, s0, s0st, s1, _, b = (t.cuda() if torch.is_tensor(t) else t for t in data(ops))
+        assert 0 < res["nparts"] * B * 24 <= res["ws_bytes"]
+        h = torch.empty_like(z)
+        ops.instnorm_apply(z[:b1], zst[:b1], _stored_map(ops, s0, s0st), 0, 1, ALPHA, out16=h[:b1], want_f32=False)
+        ops.instnorm_apply(z[b1:], zst[b1:], s1, 0, 1, ALPHA, out16=h[b1:], want_f32=False)
+        gm, bt = (torch.tensor([v], dtype=F32, device="cuda") for v in (1.2, -0.1))
+        out, st = ops.convT_s2_fwd_stats(None, res["pack"], torch.from_numpy(b).cuda(), cb, 1, gm, bt, x16=h, z16=True, alpha=ALPHA)
+        assert _same(res["out16"], out) and _same(res["stats"], st)
+        assert torch.isfinite(out.float()).all() and out.float().abs().max() > 0.1
+
+    row(f"adj-fused-fwd-{B}x{Hs}x{Ws}x{cs}-{cb}", ("lgadj_convT_s2_fwd_stats_ns",), run, check, route="fwd=conv_up3_kernel",
+        sizing=[nbytes], exact_sizing=True)
+
+
+def adj_apply_row(B, L, nparts):
+    """the apply pass whose skip is raw, bit for bit against normalise-then-apply; nparts 0: finished records (lgadj_instnorm_apply_rs,
+    through the wrapper), else the finalize of nparts partial records per sample folded in (lgadj_instnorm_apply_p_rs)"""
+    s = crc("adj-apply", B, L, nparts)
+
+    def data(ops):
+        z, zst = _records16(ops, s, (B, L), 1.0, 0.0, 1.1, 0.05)
+        sk, skst = _records16(ops, s + 1, (B, L), 1.0, 0.4, 1.1, 0.05)
+        return z, zst, sk, skst
+
+    @functools.lru_cache(maxsize=None)
+    def partials(ops):
+        gm, bt = (torch.tensor([v], dtype=F32, device="cuda") for v in (1.1, 0.05))
+        return hand_moments(ops, data(ops)[0].cuda(), nparts, gm, bt).ws.cpu()
+
+    def run(ops, alloc):
+        z, zst, sk, skst = data(ops)
+        tr = Trace(ops)
+        zd, skd, skstd = alloc.inp("z16", z), alloc.inp("skip", sk), alloc.inp("skip_stats", skst)
+        y16 = alloc.out("y16", (B, L), BF16)
+        if not nparts:
+            y = ops.instnorm_apply(zd, alloc.inp("z_stats", zst), ops.Raw(skd, skstd), 0, 1, ALPHA, out=alloc.out("y", (B, L)), out16=y16)
+            tr("apply")
+            return dict(y=y, y16=y16, _route=tr)
+        part, stats = alloc.inp("partials", partials(ops)), alloc.out("stats", (B, 8))   # (ops.Moments allocates the records: guarded ones here)
+        gm, bt = _gb(alloc, 1.1, 0.05)
+        lib, P = ops._lib.load(), lambda v: v.data_ptr()   # noqa: E731
+        ops._lib.check(lib.lgadj_instnorm_apply_p_rs(P(zd), P(part), nparts, P(gm), P(bt), P(stats), P(skd), P(skstd), 0, P(y16), B, L, 1, ALPHA,
+                                                     torch.cuda.current_stream().cuda_stream), "lgadj_instnorm_apply_p_rs")
+        tr("apply")
+        return dict(stats=stats, y16=y16, _route=tr)
+
+    def check(res):
+        from littlegan_amd import ops
+        z, zst, sk, skst = (t.cuda() for t in data(ops))
+        smap, want16 = _stored_map(ops, sk, skst), torch.empty_like(z)
+        if not nparts:
+            want = ops.instnorm_apply(z, zst, smap, 0, 1, ALPHA, out16=want16)
+            assert _same(res["y"], want)
+        else:
+            gm, bt = (torch.tensor([v], dtype=F32, device="cuda") for v in (1.1, 0.05))
+            want_st = ops.stats_tensor(ops.Moments(partials(ops).cuda(), nparts, gm, bt, B))
+            ops.instnorm_apply(z, want_st, smap, 0, 1, ALPHA, out16=want16, want_f32=False)
+            assert _same(res["stats"], want_st)
+        assert _same(res["y16"], want16)
+
+    if nparts:
+        row(f"adj-apply-p-rs-{B}x{L}-{nparts}", ("lgadj_instnorm_apply_p_rs",), run, check, route="apply=apply16p_rs_kernel", exact_sizing=True)
+    else:
+        row(f"adj-apply-rs-{B}x{L}", ("lgadj_instnorm_apply_rs",), run, check, route="apply=apply16_rs_kernel", exact_sizing=True)
+
+
+adj_fused_row(128, 64, 8, 16)       # both tilings of conv_up3's normalising form
+adj_fused_row(64, 32, 8, 32)
+adj_apply_row(2, 8 * 1029, 0)       # a sample length that is no multiple of the block's unroll
+adj_apply_row(2, 8 * 1029, 5)

@@ -1,19 +1,16 @@
 """Relativistic pairing and the R2 penalty (relativistic / r2_gamma) without a GPU: the float64 restatement that
 tests/test_rel_gpu.py holds the device to (the autograd gradient of "relativistic terms minus the kind's §25 terms", per tape, composed
 with tests/test_gan_loss_cpu.py::step_reference, anchored against a direct torch restatement of the whole step; R1 + R2 by one double
-backward over 2B rows against two tests/test_r1_cpu.py::torch_r1 calls); the header include/littlegan_rel.h held to the three properties
-of the other headers; every host-side refusal of its entry points; the configuration keys and the trainer's refusals; and the data of
+backward over 2B rows against two tests/test_r1_cpu.py::torch_r1 calls); the names of the header include/littlegan_rel.h
+(its types, exports, binding and guard-band rows are tests/test_abi.py's and the ledger's); every host-side refusal of its entry points; the configuration keys and the trainer's refusals; and the data of
 the exact-arithmetic kernel cases with the conditions under which "bit for bit" is a fair demand.
 
 The definition (this project's): f0 = the D-real function of the kind — logistic softplus(-t), hinge max(0, 1 - t), lsgan (t - 1)^2 / 2;
   disc  mean_b f0(z_r[b] - z_f[b])        gen  mean_b f0(z_f[b] - z_r[b]), z_r constant        adj  mean_i f0(z_a[i] - z_r[i mod B])"""
 import ctypes as C
-import glob
 import json
 import os
 import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -23,8 +20,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from oracle import np_oracle as O  # noqa: E402
 from oracle import torch_oracle as TO  # noqa: E402
-from guards import ABI_NAME  # noqa: E402
-from test_abi import ROOT, _ctype  # noqa: E402
+from test_abi import ROOT, _protos  # noqa: E402
 from test_diffaug_cpu import _cpu_trainer, diffaug_torch  # noqa: E402
 from test_gan_loss_cpu import (ROLE_D_FAKE, ROLE_D_REAL, ROLE_G, _logit, _np_grads, _t64, _tiny_step, np_term, step_reference, term,  # noqa: E402
                                with_objective)
@@ -207,53 +203,18 @@ def lib():
     return _lib
 
 
-def rel_protos():
-    """name -> (return type, [parameter declarations]) of the prototypes of include/littlegan_rel.h"""
-    src = re.sub(r"/\*.*?\*/", "", open(REL_HEADER).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"(?:^|\n)\s*(const char\*|int|size_t)\s+(\w+)\s*\((.*?)\)\s*;", src, flags=re.S):
-        ret, name, args = m.group(1), m.group(2), " ".join(m.group(3).split())
-        assert name not in out, f"{name} is declared twice"
-        out[name] = (ret, [] if args in ("", "void") else [a.strip() for a in args.split(",")])
-    return out
+def test_rel_header_declares_the_entry_points(lib):
+    assert set(_protos(REL_HEADER)) == set(ENTRY_POINTS) == {n for n in lib.SIGNATURES if n.startswith("lgrel_")}
 
 
-def test_the_ledger_of_the_new_header(lib):
-    """The three properties tests/test_abi.py and tests/test_guards_cpu.py hold include/littlegan_hip*.h to, for include/littlegan_rel.h:
-    declared == bound with the declared types; exported and bound by load(); every pointer-taking function has a guard-band row."""
-    import test_rel_gpu as RG
-    protos = rel_protos()
-    assert set(protos) == set(lib.REL_SIGNATURES) == set(ENTRY_POINTS)
-    assert all(n.startswith("lgrel_") and not re.fullmatch(ABI_NAME, n) for n in protos)     # outside the closed ABI table
-    assert not set(lib.REL_SIGNATURES) & (set(lib.SIGNATURES) | set(lib.GEOM_SIGNATURES))
-    assert REL_HEADER not in glob.glob(os.path.join(ROOT, "include", "littlegan_hip*.h"))
-    handle = lib.load()
-    for name, (ret, plist) in protos.items():
-        res, args = lib.REL_SIGNATURES[name]
-        assert len(args) == len(plist), name
-        for a, decl in zip(args, plist):
-            assert a is _ctype(decl), (name, decl)
-        assert res is {"int": C.c_int, "size_t": C.c_size_t}[ret], name
-        fn = getattr(handle, name)
-        assert fn.argtypes == args and fn.restype is res, f"{name}: load() did not bind it"
-    assert handle.lg_abi_version() == 1
-    nm = os.path.join("/opt/rocm/lib/llvm/bin", "llvm-nm")
-    nm = nm if os.path.exists(nm) else (shutil.which("llvm-nm") or shutil.which("nm"))
-    if nm:     # (without an nm the getattr above has already found each symbol)
-        out = subprocess.run([nm, "-D", "--defined-only", os.path.join(ROOT, "littlegan_amd", "liblittlegan_hip.so")],
-                             stdout=subprocess.PIPE, text=True, check=True).stdout
-        exported = {line.split()[-1] for line in out.splitlines() if line.split() and line.split()[-1].startswith("lgrel_")}
-        assert exported == set(protos), exported ^ set(protos)
-    covered = {n for r in RG.CONTRACT_CASES for n in r.covers}
-    pointer_taking = {n for n, (_, plist) in protos.items() if any("*" in d for d in plist)}
-    assert pointer_taking == {"lgrel_pair_heads_loss_fwd_bwd", "lgrel_r12_seed"} and not pointer_taking - covered, pointer_taking - covered
-    # the kernels sit beside the code they share (gan_term in objective.hip, the seed's pass in r1.hip): both see the header, neither
-    # declares anything itself, and the shared device function has ONE definition
+def test_the_sources_include_the_header_and_are_built():
     from littlegan_amd.csrc import build as B
     for name in ("objective.hip", "r1.hip"):
-        text = open(os.path.join(ROOT, "littlegan_amd", "csrc", name)).read()
-        assert re.search(r'^#include "lg_internal\.h"', text, flags=re.M) and "littlegan_rel.h" in text and name in B.SOURCES
-        assert not re.search(r'^extern "C" [^{;]*;', re.sub(r"//[^\n]*", "", text), flags=re.M)
+        assert "littlegan_rel.h" in open(os.path.join(ROOT, "littlegan_amd", "csrc", name)).read() and name in B.SOURCES
+
+
+def test_the_shared_device_code_has_one_definition():
+    """the kernels sit beside the code they share (gan_term in objective.hip, the seed's pass in r1.hip): ONE definition, two call sites"""
     obj = open(os.path.join(ROOT, "littlegan_amd", "csrc", "objective.hip")).read()
     assert len(re.findall(r"\bvoid gan_term\(", obj)) == 1 and len(re.findall(r"\bgan_term\(kind, LGO_ROLE_D_REAL,", obj)) == 2
     r1 = open(os.path.join(ROOT, "littlegan_amd", "csrc", "r1.hip")).read()

@@ -4,7 +4,7 @@ Kernels: lgrel_pair_heads_loss_fwd_bwd bit for bit in exact arithmetic (tests/te
 bit for bit against lgo_gan_heads_loss_fwd_bwd where the two must agree (SELF against an all-zero z_ref is role 0), the two halves of a
 pair against each other, on random data against fp64 (the bounds of tests/test_tail_ops_gpu.py::test_bce_heads_loss_sizes), NaNs;
 lgrel_r12_seed bit for bit against two lgr_r1_seed calls on the halves and against exact arithmetic, repeated and under a one-CU budget.
-Their memory contract with the guard bands of tests/guards.py (CONTRACT_CASES: one row per pointer-taking entry point).
+Their memory contract: the rel-* rows of tests/test_memory_contract_gpu.py.
 Whole steps against the float64 reference of tests/test_rel_cpu.py at the tolerances of tests/test_step_gpu.py; the joint R1 + R2 pass
 alone against the torch double backward over 2B rows and against two r1_penalty passes; the off state; determinism, graph replay, two
 gloo ranks and the CLI."""
@@ -21,10 +21,9 @@ import torch.multiprocessing as mp
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))  # the spawned ranks import this module by name too
 from oracle import np_oracle as O  # noqa: E402
-from guards import ABI_NAME, describe, exact_workspaces  # noqa: E402
+from guards import called  # noqa: E402
 from test_gan_loss_cpu import objective_delta, with_objective  # noqa: E402
 from test_gan_loss_gpu import _heads_data, rel  # noqa: E402
-from test_memory_contract_gpu import Alloc, Row, _diff, _stale  # noqa: E402
 from test_r1_cpu import EXACT_LOSS0 as SEED_LOSS0, EXACT_WEIGHT, SEED_SHAPES, ZERO_GRADS, exact_seed_case, torch_r1  # noqa: E402
 from test_r1_gpu import one_cu  # noqa: E402
 from test_rel_cpu import (EXACT_KINDS, EXACT_LOSS0, EXACT_SHAPES, EXACT_W_PR, KIND_NO, REL_KINDS, SIDE_OTHER, SIDE_SELF, exact_pair_case,  # noqa: E402
@@ -60,28 +59,6 @@ def _np_bits(a):
 
 def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
-
-
-class _Recorder:
-    """every name of the C ABI and of the lgrel_ header that a piece of code fetched from the library handle (guards.called records the
-    closed ABI pattern alone, which the lgrel_ names are outside of)"""
-
-    def __init__(self, handle, names):
-        object.__setattr__(self, "_handle", handle)
-        object.__setattr__(self, "_names", names)
-
-    def __getattr__(self, name):
-        import re
-        if name.startswith("lgrel_") or re.fullmatch(ABI_NAME, name):
-            self._names.append(name)
-        return getattr(self._handle, name)
-
-
-def fetched(monkeypatch, ops):
-    names = []
-    real = ops._lib.load
-    monkeypatch.setattr(ops._lib, "load", lambda *a, **k: _Recorder(real(*a, **k), names))
-    return names
 
 
 # ---------------------------------------------------------------------------------------------------------------- pair kernel, exact
@@ -302,90 +279,6 @@ def test_joint_seed_on_random_data(ops, B, L):
         assert abs(float(got) - term) <= 1e-5 * abs(term)
 
 
-# ---------------------------------------------------------------------------------------------------------------- memory contract
-CONTRACT_CASES = []
-
-
-def _pair_row(kind, side, n, m, c):
-    def run(ops, alloc):
-        p, t_c = _heads_data(n, c, 23 * n + c)
-        z, zr, _, _ = exact_pair_case(kind, side, n, m)
-        loss, dz = alloc.state("loss", np.array([EXACT_LOSS0], np.float32)), alloc.out("dz", (n, 1 + c))
-        ops.pair_heads_loss(alloc.inp("p", p.astype(np.float32)), alloc.inp("z", z), alloc.inp("z_ref", zr), alloc.inp("t_c", t_c.astype(np.float32)),
-                            KIND_NO[kind], side, EXACT_W_PR, 1.0, loss, dz, True)
-        return dict(loss=loss, dz=dz)
-
-    def check(res):
-        p, t_c = _heads_data(n, c, 23 * n + c)
-        _, _, dz_w, term_w = exact_pair_case(kind, side, n, m)
-        assert torch.equal(res["dz"][:, 0].cpu(), torch.from_numpy(dz_w))
-        exp = EXACT_LOSS0 + float(term_w) + O.bce_mean(t_c, p[:, 1:])
-        assert abs(float(res["loss"]) - exp) < 2e-6 * abs(exp) + 1e-6
-        assert rel(res["dz"][:, 1:], O.bce_mean_bwd(t_c, p[:, 1:]) * p[:, 1:] * (1 - p[:, 1:])) < 1e-5
-
-    CONTRACT_CASES.append(Row(f"pair-{kind}-{side}-{n}x{m}x{c}", ("lgrel_pair_heads_loss_fwd_bwd",), run, check))
-
-
-def _seed_row(B, L):
-    def run(ops, alloc):
-        g = alloc.inp("g", _seed_halves(B, L)[0])
-        loss = alloc.state("loss", np.array([SEED_LOSS0], np.float32))
-        r1l, r2l = alloc.out("r1_loss", (1,)), alloc.out("r2_loss", (1,))
-        u0, r2 = alloc.out("u0", (2 * B, L)), alloc.out("r2", (2 * B,))
-        lib = ops._lib.load()
-        ws = ops.workspace(int(lib.lgrel_r12_workspace_bytes(B, L)), g.device, "r1")   # (the wrapper allocates its outputs: guarded ones here)
-        ops._lib.check(lib.lgrel_r12_seed(g.data_ptr(), u0.data_ptr(), r2.data_ptr(), loss.data_ptr(), r1l.data_ptr(), r2l.data_ptr(), EXACT_WEIGHT,
-                                          W_FAKE, ws.data_ptr(), ws.numel(), B, L, torch.cuda.current_stream().cuda_stream), "lgrel_r12_seed")
-        return dict(u0=u0, r2=r2, loss=loss, r1_loss=r1l, r2_loss=r2l)
-
-    def check(res):
-        _, u0, r2, t1, t2, loss = _seed_halves(B, L)
-        assert np.array_equal(_bits(res["u0"]), _np_bits(u0)) and np.array_equal(_bits(res["r2"]), _np_bits(r2))
-        assert np.array_equal(_bits(res["r1_loss"]), _np_bits([t1])) and np.array_equal(_bits(res["r2_loss"]), _np_bits([t2]))
-        assert np.array_equal(_bits(res["loss"]), _np_bits([loss]))
-
-    CONTRACT_CASES.append(Row(f"r12-seed-{B}x{L}", ("lgrel_r12_seed",), run, check, sizing=[("lgrel_r12_workspace_bytes", (B, L))]))
-
-
-_pair_row("hinge", SIDE_SELF, 1, 1, 1)
-_pair_row("lsgan", SIDE_OTHER, 6, 3, 3)
-_seed_row(1, 4)
-_seed_row(4, 4100)
-
-
-def _once(row_, ops, monkeypatch, mode, byte=0xFF):
-    alloc = Alloc(mode, byte)
-    with monkeypatch.context() as mp_:
-        ws = exact_workspaces(mp_, ops, fill=byte) if mode == "guard" else None
-        names = fetched(mp_, ops)
-        res = dict(row_.run(ops, alloc))
-        torch.cuda.synchronize()
-    return res, alloc, ws, set(names)
-
-
-@pytest.mark.parametrize("case", CONTRACT_CASES, ids=lambda r: r.id)
-def test_rel_memory_contract(case, ops, monkeypatch):
-    plain, _, _, names = _once(case, ops, monkeypatch, "plain")
-    missing = set(case.covers) - names
-    assert not missing, f"the row claims entry points it never fetched: {sorted(missing)} (fetched {sorted(names)})"
-    plain2, _, _, _ = _once(case, ops, monkeypatch, "plain")
-    d = _diff("two plain runs differ (the op is not reproducible; nothing below can be read)", plain, plain2)
-    assert not d, d
-    for tag, byte in (("A (0xFF)", 0xFF), ("B (0x00)", 0x00), ("C (0x3F)", 0x3F)):
-        got, alloc, ws, _ = _once(case, ops, monkeypatch, "guard", byte)
-        bad = alloc.problems() + [f"{what}: written outside its advertised size: {describe(offs)}" for what, offs in ws.damaged()]
-        assert not bad, f"run {tag}: " + " | ".join(bad)
-        for name, args in case.sizing:      # the workspace handed over is exactly what the sizing function advertises
-            want = int(getattr(ops._lib.load(), name)(*args))
-            assert [nb for _, nb, _ in ws.handed] == [want], (name, args, ws.handed)
-        if byte == 0xFF:
-            stale = _stale(plain, got)
-            assert not stale, f"run {tag}: " + " | ".join(stale)
-        d = _diff(f"run {tag} differs from the plain run (foreign bytes, stale workspace or stale output contents show in the result)", plain, got)
-        assert not d, d
-    case.check(plain)
-
-
 # ---------------------------------------------------------------------------------------------------------------- whole steps
 def _build(cfg, W, mfma, gan_loss="logistic", relativistic=True, **kw):
     from littlegan_amd.eager_trainer import EagerTrainer
@@ -477,7 +370,7 @@ def test_the_recipe_step(ops, monkeypatch, mfma):
     b = 4
     cfg, W, inp, ref = _reference("logistic", b)
     tr = _build(cfg, W, mfma, "logistic", r1_gamma=G1, r2_gamma=G2, r1_interval=1)
-    names = fetched(monkeypatch, ops)
+    names = called(monkeypatch, ops)
     outs = tr.train_step_from_inputs(b, dev_inputs(inp))
     torch.cuda.synchronize()
     assert names.count("lgrel_r12_seed") == 1 and "lgr_r1_seed" not in names and names.count("lgrel_pair_heads_loss_fwd_bwd") == 3
@@ -493,7 +386,7 @@ def test_r2_alone(ops, monkeypatch, mfma):
     cfg, W, inp, ref = _reference("hinge", b)
     tr = _build(cfg, W, mfma, "hinge", r2_gamma=G2, r1_interval=1)
     assert tr.r1 is None and "r1" not in tr.losses
-    names = fetched(monkeypatch, ops)
+    names = called(monkeypatch, ops)
     outs = tr.train_step_from_inputs(b, dev_inputs(inp))
     torch.cuda.synchronize()
     assert names.count("lgr_r1_seed") == 1 and "lgrel_r12_seed" not in names
@@ -511,7 +404,7 @@ def test_lazy_interval(ops, monkeypatch, mfma):
     tr.losses["r1"].fill_(7.0)
     tr.losses["r2"].fill_(8.0)
     with monkeypatch.context() as mp_:
-        names = fetched(mp_, ops)
+        names = called(mp_, ops)
         tr.train_step_from_inputs(1, dev_inputs(inp))
         off.train_step_from_inputs(1, dev_inputs(inp))
         torch.cuda.synchronize()
@@ -650,7 +543,7 @@ def test_defaults_fetch_nothing_and_agree(ops, monkeypatch):
     absent, off = _build(cfg, W, "f32", None, None), _build(cfg, W, "f32", "bce", False, r2_gamma=0.0)
     assert not hasattr(absent.args, "relativistic") and not hasattr(absent.args, "r2_gamma")
     assert absent.relativistic is False and absent.r2 is None and off.relativistic is False and off.r2 is None and "r2" not in off.losses
-    names = fetched(monkeypatch, ops)
+    names = called(monkeypatch, ops)
     for b in (1, 5, 12, 16):
         inp = dev_inputs(_step_inputs(cfg, b))
         absent.train_step_from_inputs(b, inp)
@@ -669,7 +562,7 @@ def test_r1_alone_keeps_its_launches_and_bits(ops, monkeypatch):
     seen = []
     for tr in (new, old):
         with monkeypatch.context() as mp_:
-            names = fetched(mp_, ops)
+            names = called(mp_, ops)
             for b in (4, 12):
                 tr.train_step_from_inputs(b, dev_inputs(_step_inputs(cfg, b)))
             torch.cuda.synchronize()
