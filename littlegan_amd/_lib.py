@@ -183,6 +183,21 @@ SIGNATURES = {
 }
 
 
+# Global-norm gradient clipping and the non-finite step guard (include/gradguard.h; gradguard.hip, loss_optim.hip).  A
+# table of its own: the names are not `lg*_` names and their header is not one of include/littlegan_*.h, so SIGNATURES and what holds it
+# to the headers stay as they are; tests/test_grad_guard_cpu.py holds THIS table to its header and to the library's exports.
+GG_SIGNATURES = {
+    "gg_partials_count": (I, [L]),
+    "gg_workspace_bytes": (Z, [L]),
+    "gg_init": (I, [P, I, I, P]),
+    "gg_sumsq_partial": (I, [P, L, P, Z, P]),
+    "gg_finalise": (I, [P, L, P, F, F, I, P]),
+    "gg_clip_adam_update": (I, [P, P, P, P, L, P, P, P, F, F, F, F, P]),
+    "gg_clip_adam_ema_update": (I, [P, P, P, P, P, L, L, L, P, P, P, P, F, F, F, F, F, P]),
+    "gg_adam_advance": (I, [P, P, F, F, P]),
+}
+
+
 class LittleGanHipError(RuntimeError):
     pass
 
@@ -215,7 +230,7 @@ def load():
     # before torch, the system runtime it links against would come in as a SECOND runtime and its kernels would see no device.
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(GG_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -26,7 +26,12 @@ lr_g / lr_d / lr_adj (base learning rate of the Generator's, the Discriminator's
 ("constant" | "linear" | "cosine") / lr_warmup_steps / lr_decay_steps / lr_final_ratio (a factor s(k) on all three rates, k the number of
 training steps taken over the whole run: (k + 1) / lr_warmup_steps during warm-up, then a linear or cosine decay over lr_decay_steps from 1
 to lr_final_ratio, where it stays; it is computed on the device from a counter on the device, so replayed graphs follow it, and the
-counter is part of the checkpoint; constant without warm-up = the step as it was)."""
+counter is part of the checkpoint; constant without warm-up = the step as it was),
+clip_norm (null = off, or a number > 0: each optimizer's gradient is scaled so that its global L2 norm, taken in fp64 on the device after
+the all-reduce, is at most clip_norm; the element-wise clip_range of D acts after it) / skip_nonfinite (bool: a network whose gradient
+holds a NaN or an Inf this step keeps its weights, Adam slots and beta powers, and the event is counted; the norms and the counters live
+on the device, so replayed graphs clip and skip by their own gradients, and the counters are part of the checkpoint; both off = the step
+as it was)."""
 import json
 import os
 from argparse import ArgumentParser
@@ -129,6 +134,12 @@ DEFAULTS = {
     # a cosine) and stays there.  lr_decay_steps is required by linear / cosine and refused with constant.  s is computed on the device.
     'lr_g': None, 'lr_d': None, 'lr_adj': None, 'lr_schedule': 'constant', 'lr_warmup_steps': 0, 'lr_decay_steps': None,
     'lr_final_ratio': 0.0,
+    # global-norm gradient clipping and the non-finite step guard (the reference clips D element-wise and nothing else).
+    # clip_norm: null = off, else each of the three optimizers scales its gradient by min(1, clip_norm / (N + 1e-6)), N the L2 norm of
+    # the (all-reduced, averaged) gradient range it trains this step; clip_range still acts on D, after the scaling.  skip_nonfinite: a
+    # network whose gradient holds a NaN or an Inf is left exactly as it was for this step (weights, Adam slots, beta powers) and the
+    # skip is counted.  Allowed with every other key.
+    'clip_norm': None, 'skip_nonfinite': False,
 }
 
 GAN_LOSS_KINDS = {"bce": 0, "logistic": 1, "hinge": 2, "lsgan": 3, "wgan": 4}   # the `kind` of lgo_gan_heads_loss_fwd_bwd; 0 = not its
@@ -343,6 +354,51 @@ def lr_rates(k, settings):
     return tuple(np.float32(settings[m]) * s for m in ("lr_g", "lr_d", "lr_adj"))
 
 
+def grad_guard_settings(clip_norm=None, skip_nonfinite=False):
+    """The two keys of the gradient guard, validated: None when both are off (no state exists and no gg_* function is
+    fetched), else {clip_norm: the fp32 value it is used at, 0.0 = no clipping; skip: bool}.  Raises ValueError for a clip_norm that is
+    neither null nor a finite number > 0 that fits fp32 (bools and strings refused) and for a skip_nonfinite that is no bool."""
+    import math
+    import numpy as np
+    if not isinstance(skip_nonfinite, bool):
+        raise ValueError(f"skip_nonfinite must be true or false, got {skip_nonfinite!r}")
+    c = 0.0
+    if clip_norm is not None:
+        if isinstance(clip_norm, bool) or not isinstance(clip_norm, (int, float)) or not math.isfinite(clip_norm):
+            raise ValueError(f"clip_norm must be null (off) or a finite number > 0, got {clip_norm!r}")
+        with np.errstate(over="ignore"):
+            c = float(np.float32(clip_norm))
+        if not 0.0 < c < float("inf"):
+            raise ValueError(f"clip_norm must be null (off) or a finite number > 0 that fits fp32, got {clip_norm!r}")
+    if clip_norm is None and not skip_nonfinite:
+        return None
+    return {"clip_norm": c, "skip": skip_nonfinite}
+
+
+def grad_guard_restate(g, gscale, clip_norm, skip, sumsq=None):
+    """The record of DESIGN.md §30 as the device computes it (gg_finalise), restated in numpy: S = the fp64 sum of the squares of g (or
+    `sumsq` when given: the device's own S, ops.grad_sumsq — g is then not read), then the fp32 steps of the definition.  clip_norm 0 = no
+    clipping.  -> {S (float64), bad, N, c, eff (float32), skip_now (bool)}.  The order of numpy's additions is not the device's: N agrees
+    to 1 fp32 ulp, and c, eff follow bit for bit from a given N.  For the log and the tests."""
+    import numpy as np
+    f32, f64 = np.float32, np.float64
+    with np.errstate(over="ignore", invalid="ignore"):
+        if sumsq is None:
+            g64 = np.asarray(g, dtype=f32).astype(f64).reshape(-1)
+            S = f64(np.sum(g64 * g64))
+        else:
+            S = f64(sumsq)
+        bad = not bool(np.isfinite(S))
+        gs = f32(gscale)
+        N = f32(np.sqrt(S) * f64(gs))
+        c = f32(1.0)
+        if f32(clip_norm) != 0 and not bad:
+            q = f32(clip_norm) / (N + f32(1e-6))
+            c = q if q < f32(1.0) else f32(1.0)
+        eff = gs * c
+    return {"S": S, "bad": bad, "N": N, "c": f32(c), "eff": f32(eff), "skip_now": bool(bad and skip)}
+
+
 METRIC_NAMES = ("fid", "kid", "prdc")
 
 
@@ -394,6 +450,7 @@ class Arg:
         r2_settings(self.r2_gamma, self.r1_interval)
         lr_schedule_settings(self.lr, self.lr_g, self.lr_d, self.lr_adj, self.lr_schedule, self.lr_warmup_steps, self.lr_decay_steps,
                              self.lr_final_ratio)   # a misspelt schedule fails here, not at the first step
+        grad_guard_settings(self.clip_norm, self.skip_nonfinite)
         self.evaluate_metrics = metric_list(self.evaluate_metrics)   # a misspelt metric fails here, not after the sampling run
         if int(self.kid_subsets) < 0 or int(self.kid_subset_size) < 2 or not 1 <= int(self.prdc_k) <= 15:
             raise ValueError("need kid_subsets >= 0, kid_subset_size >= 2 and 1 <= prdc_k <= 15")

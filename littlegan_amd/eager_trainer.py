@@ -17,8 +17,8 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from .config import (ada_settings, diff_augment_bits, gan_loss_kind, geom_augment_bits, lr_schedule_settings, r1_settings, r2_settings,
-                     relativistic_setting)
+from .config import (ada_settings, diff_augment_bits, gan_loss_kind, geom_augment_bits, grad_guard_settings, lr_schedule_settings,
+                     r1_settings, r2_settings, relativistic_setting)
 from .dist import GradSync
 from .model import Adjuster, Discriminator, Generator, ParamStore
 from .utils import save_image, soft
@@ -161,6 +161,21 @@ class EagerTrainer:
         # {k, s, rate of G, D, A, 0, 0, 0} on the device (lgsch_init: written from a launch scalar), advanced by the first launch of every
         # step; None = the rates are constants.  No host mirror: nothing on the host depends on k
         self.lr_state = ops.sched_init(0, device=self.device) if self.lr_sched["device"] else None
+        # global-norm clipping and the non-finite step guard (the reference has neither): None = off, no state and no
+        # launch of its own; else three 32-byte records {N, eff, skip_now, skipped, nonfinite, c, 0, 0} on the device (G, D, A; gg_init:
+        # written from launch scalars), one partials workspace sized for the largest network, and, without a schedule, the three base
+        # rates on the device (filled once, here: the guarded Adam passes always read their rate through a pointer)
+        self.guard = grad_guard_settings(getattr(args, "clip_norm", None), getattr(args, "skip_nonfinite", False))
+        if self.guard is not None:
+            self.guard_state = torch.empty(24, dtype=torch.float32, device=self.device)
+            self._guard_rec = {m: self.guard_state[8 * i:8 * i + 8] for i, m in enumerate("GDA")}
+            for m in "GDA":
+                ops.guard_init(0, 0, out=self._guard_rec[m])
+            n_max = max(e - s for s, e in (self.store.model_range(m) for m in "GDA"))
+            self._guard_ws = torch.empty(ops.guard_workspace_bytes(n_max), dtype=torch.uint8, device=self.device)
+            self._guard_lr = None
+            if self.lr_state is None:
+                self._guard_lr = torch.tensor([self.opt_cfg[m][0] for m in "GDA"], dtype=torch.float32, device=self.device)
         self._init_dir()
         # eager_trainer.py:36-43: restore the newest checkpoint (weights, the three optimizers' slots and beta powers)
         # and the epoch from status.json when args.restore is set
@@ -419,11 +434,29 @@ class EagerTrainer:
         (no synchronisation; float() of an element waits like float() of a loss), None when the rates are constants (opt_cfg)."""
         return None if self.lr_state is None else self.lr_state[2:5]
 
+    def grad_norm_now(self):
+        """The gradient norms N of G, D, A of the most recent step each trained in, under clip_norm or skip_nonfinite: the 3-element
+        device view of the records' first words (no synchronisation; float() of an element waits like float() of a loss), None when
+        the guard is off."""
+        return None if self.guard is None else self.guard_state.view(3, 8)[:, 0]
+
+    def guard_counts(self):
+        """{"G" | "D" | "A": (steps skipped, steps with a non-finite gradient)} so far, read from the device (synchronises: for the
+        log and checkpoints), None when the guard is off."""
+        if self.guard is None:
+            return None
+        words = self.guard_state.detach().cpu().view(torch.int32).view(3, 8)
+        return {m: (int(words[i, 3]), int(words[i, 4])) for i, m in enumerate("GDA")}
+
     def _apply_optimizers(self, batch_no: int, run_adj: bool):
         a, st = self.args, self.store
         gscale = 1.0 / self.sync.world_size
         # under a schedule the Adam passes read their rate from the state the step's first launch wrote (1-element views of it)
         lr_view = None if self.lr_state is None else {m: self.lr_state[i:i + 1] for m, i in (("G", 2), ("D", 3), ("A", 4))}
+        gd = self.guard
+        g_lr = lr_view
+        if gd is not None and lr_view is None:   # the guarded passes read their rate from device memory whether it is scheduled or not
+            g_lr = {m: self._guard_lr[i:i + 1] for i, m in enumerate("GDA")}
         for m in self.adam_order:
             trained = m != "A" or run_adj
             if not trained and st.ema is None:
@@ -434,6 +467,23 @@ class EagerTrainer:
             s, e = st.model_range(m, lo, hi)
             if trained:
                 self.sync.wait(m)
+            if gd is not None and trained:
+                # the norm of the (all-reduced) range this step trains, finished into the network's record, which the Adam pass and the
+                # advance of the beta powers read: two more launches, nothing on the host
+                rec = self._guard_rec[m]
+                ops.guard_sumsq_partial(st.grad[s:e], self._guard_ws)
+                ops.guard_finalise(self._guard_ws, e - s, rec, gscale, gd["clip_norm"], gd["skip"])
+                if st.ema is None:
+                    ops.guard_clip_adam_update(st.flat[s:e], st.grad[s:e], st.m[s:e], st.v[s:e], self.opt_state[m], g_lr[m], rec, b1, b2,
+                                               ADAM_EPS, clip)
+                else:
+                    s0, e0 = st.model_range(m)
+                    ops.guard_clip_adam_ema_update(st.flat[s0:e0], st.grad[s0:e0], st.m[s0:e0], st.v[s0:e0], st.ema[s0:e0], s - s0, e - s0,
+                                                   self.opt_state[m], st.ema_updates, g_lr[m], rec, b1, b2, ADAM_EPS, clip,
+                                                   self.ema_decay)
+                ops.guard_adam_advance(self.opt_state[m], rec, b1, b2)
+                continue
+            # (under the guard only an Adjuster that does not train this step gets here: today's call, the average alone)
             if st.ema is None and lr_view is not None:
                 ops.sched_clip_adam_update(st.flat[s:e], st.grad[s:e], st.m[s:e], st.v[s:e], self.opt_state[m], lr_view[m], b1, b2,
                                            ADAM_EPS, clip, gscale)
@@ -714,7 +764,12 @@ class EagerTrainer:
                     if self.r2 is not None:
                         r1 += f" R2 {float(self.losses['r2']):.4f}"
                     lrs = "" if self.lr_state is None else " LR g/d/a " + "/".join(f"{x:.3e}" for x in self.lr_now().tolist())
-                    print(f"  [{seen}] LossG {lg:.4f} LossD {ld:.4f} LossA {la:.4f}{r1}{aug_p}{lrs}")
+                    gn = ""
+                    if self.guard is not None:   # the norms of the most recent step and the skips so far, read where the losses are
+                        cnt = self.guard_counts()
+                        gn = " GN g/d/a " + "/".join(f"{x:.3e}" for x in self.grad_norm_now().tolist()) \
+                             + " Skip g/d/a " + "/".join(str(cnt[m][0]) for m in "GDA")
+                    print(f"  [{seen}] LossG {lg:.4f} LossD {ld:.4f} LossA {la:.4f}{r1}{aug_p}{lrs}{gn}")
                 if b % a.freq_test == 0 and io and self.test_cond is not None:
                     self.predict(self.test_noise, self.test_cond, self.test_image,
                                  os.path.join(a.result_dir, "test", "gen", "%d-%d.jpg" % (e, b)),
@@ -855,6 +910,9 @@ class EagerTrainer:
             ck["ada_state"] = self.ada_state.detach().cpu().view(torch.int32)
         if self.lr_state is not None:   # the schedule's step counter (absent when the rates are constants)
             ck["lr_sched_state"] = ops.sched_read(self.lr_state)[0]
+        if self.guard is not None:   # the six counters {skipped, non-finite} of G, D, A (absent when the guard is off)
+            cnt = self.guard_counts()
+            ck["grad_guard_state"] = [int(x) for m in "GDA" for x in cnt[m]]
         return ck
 
     def save_checkpoint(self, tag: str) -> str:
@@ -902,6 +960,14 @@ class EagerTrainer:
             lr_k = ck["lr_sched_state"]
             if isinstance(lr_k, bool) or not isinstance(lr_k, int) or not 0 <= lr_k < 2 ** 31:
                 raise ValueError(f"{path}: lr_sched_state {lr_k!r} is not a step counter (one integer, 0 <= k < 2^31)")
+        guard_cnt = None
+        if self.guard is not None and "grad_guard_state" in ck:   # checked before anything is loaded, like the words above
+            guard_cnt = ck["grad_guard_state"]
+            if not (isinstance(guard_cnt, (list, tuple)) and len(guard_cnt) == 6
+                    and all(isinstance(x, int) and not isinstance(x, bool) and 0 <= x < 2 ** 31 for x in guard_cnt)
+                    and all(guard_cnt[i] <= guard_cnt[i + 1] for i in (0, 2, 4))):
+                raise ValueError(f"{path}: grad_guard_state {guard_cnt!r} is not the guard's counters (six integers {{skipped, non-finite}} "
+                                 "of G, D, A, 0 <= skipped <= non-finite < 2^31)")
         st.flat.copy_(ck["flat"])
         st.m.copy_(ck["adam_m"])
         st.v.copy_(ck["adam_v"])
@@ -925,6 +991,11 @@ class EagerTrainer:
             if lr_k is None:
                 print(f"{path}: no learning-rate step counter in this checkpoint; the schedule starts at k = 0")
             ops.sched_init(lr_k or 0, out=self.lr_state)
+        if self.guard is not None:   # (a checkpoint's counters are ignored when this run guards nothing; without them they start at zero)
+            if guard_cnt is None:
+                print(f"{path}: no gradient-guard counters in this checkpoint; they start at zero")
+            for i, m in enumerate("GDA"):
+                ops.guard_init(*(guard_cnt[2 * i:2 * i + 2] if guard_cnt is not None else (0, 0)), out=self._guard_rec[m])
         st.bump()
 
     def export_model_checkpoint(self):

@@ -1857,3 +1857,117 @@ def sched_clip_adam_ema_update(w, g, m, v, ema, lo, hi, state, ema_state, lr, b1
     check(_lib.load().lgsch_clip_adam_ema_update(_p(w), _p(g), _p(m), _p(v), _p(ema), n, int(lo), int(hi), _p(state), _p(ema_state),
                                                  _p(_chk_rate(lr)), float(b1), float(b2), float(eps), float(clip), float(gscale),
                                                  float(decay), _stream()), "lgsch_clip_adam_ema_update")
+
+
+# ------------------------------------------------------------------ global-norm gradient clipping and the non-finite step guard (gradguard.hip, loss_optim.hip; include/gradguard.h)
+GUARD_CHUNK, GUARD_MAX_PARTIALS = 16384, 1024      # GG_CHUNK, GG_MAX_PARTIALS
+
+
+def _chk_guard(t, who):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (8,)):
+        raise ValueError(f"{who}: the guard's record is a contiguous fp32 [8] CUDA tensor, got {t.dtype} {t.device} {tuple(t.shape)}")
+    return t
+
+
+def _chk_grad(g, who):
+    if not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.dim() == 1 and g.numel() >= 1):
+        raise ValueError(f"{who}: need a contiguous 1-d fp32 CUDA tensor of at least one element, got {g.dtype} {g.device} {tuple(g.shape)}")
+    return g
+
+
+def _chk_partial(p, who):
+    if not (p.is_cuda and p.dtype in (torch.uint8, torch.float64) and p.is_contiguous()):
+        raise ValueError(f"{who}: the partials are a contiguous uint8 or fp64 CUDA tensor, got {p.dtype} {p.device}")
+    return p
+
+
+def guard_partials_count(n):
+    """P(n) = min(1024, ceil(n / 16384)): the fp64 partials of a sum of squares over n elements (gg_partials_count)."""
+    return int(_lib.load().gg_partials_count(int(n)))
+
+
+def guard_workspace_bytes(n):
+    """8 P(n): the bytes of those partials (gg_workspace_bytes)."""
+    return int(_lib.load().gg_workspace_bytes(int(n)))
+
+
+def guard_init(skipped=0, nonfinite=0, device="cuda", out=None):
+    """The guard's record {N, eff, skip_now, skipped, nonfinite, c, 0, 0} (fp32 [8]; words 2..4 int32) with every word zero but the two
+    counters, written by a one-block kernel from launch scalars: no host-to-device copy."""
+    if out is None:
+        out = torch.empty(8, dtype=torch.float32, device=device)
+    _chk_guard(out, "guard_init")
+    check(_lib.load().gg_init(_p(out), int(skipped), int(nonfinite), _stream()), "gg_init")
+    return out
+
+
+def guard_sumsq_partial(g, partial):
+    """partial[:P(n)] (fp64) = the per-workgroup sums of squares of g, in the order include/gradguard.h states; partial holds at least
+    guard_workspace_bytes(n) bytes."""
+    _chk_grad(g, "guard_sumsq_partial")
+    _chk_partial(partial, "guard_sumsq_partial")
+    check(_lib.load().gg_sumsq_partial(_p(g), g.numel(), _p(partial), partial.numel() * partial.element_size(), _stream()),
+          "gg_sumsq_partial")
+    return partial
+
+
+def guard_finalise(partial, n, rec, gscale, clip_norm, skip):
+    """The record of the n elements whose partials `partial` holds: S in index order, then N, c, eff, skip_now and the counters
+    (gg_finalise).  clip_norm 0 = no clipping."""
+    _chk_partial(partial, "guard_finalise")
+    _chk_guard(rec, "guard_finalise")
+    if partial.numel() * partial.element_size() < guard_workspace_bytes(n):
+        raise ValueError(f"guard_finalise: {partial.numel() * partial.element_size()} bytes of partials, n = {n} has {guard_workspace_bytes(n)}")
+    check(_lib.load().gg_finalise(_p(partial), int(n), _p(rec), float(gscale), float(clip_norm), int(bool(skip)), _stream()), "gg_finalise")
+    return rec
+
+
+def guard_read(rec):
+    """{N, eff, skip_now, skipped, nonfinite, c} of a record on the host.  Synchronises: for logs, checkpoints and tests, not for the step."""
+    _chk_guard(rec, "guard_read")
+    host = rec.detach().cpu()
+    words = host.view(torch.int32)
+    return dict(N=float(host[0]), eff=float(host[1]), skip_now=int(words[2]), skipped=int(words[3]), nonfinite=int(words[4]), c=float(host[5]))
+
+
+def grad_sumsq(g):
+    """S = the fp64 sum of the squares of g as the guard computes it: the device's partials, added in index order.  Synchronises."""
+    _chk_grad(g, "grad_sumsq")
+    ws = workspace(guard_workspace_bytes(g.numel()), g.device, "gradguard")
+    guard_sumsq_partial(g, ws)
+    s = 0.0
+    for x in ws[:8 * guard_partials_count(g.numel())].view(torch.float64).cpu().tolist():
+        s += x
+    return s
+
+
+def guard_clip_adam_update(w, g, m, v, state, lr, rec, b1, b2, eps, clip):
+    """sched_clip_adam_update with the gradient scale (rec word 1) and the skip flag (rec word 2) read on the device."""
+    n = w.numel()
+    for t, nm in ((w, "w"), (g, "g"), (m, "m"), (v, "v")):
+        _chk(t, name=nm)
+        if t.numel() != n:
+            raise ValueError("guard_clip_adam_update: size mismatch")
+    _chk(state, (2,), "state")
+    check(_lib.load().gg_clip_adam_update(_p(w), _p(g), _p(m), _p(v), n, _p(state), _p(_chk_rate(lr)), _p(_chk_guard(rec, "guard_clip_adam_update")),
+                                          float(b1), float(b2), float(eps), float(clip), _stream()), "gg_clip_adam_update")
+
+
+def guard_clip_adam_ema_update(w, g, m, v, ema, lo, hi, state, ema_state, lr, rec, b1, b2, eps, clip, decay):
+    """sched_clip_adam_ema_update with the gradient scale and the skip flag read on the device; a skipped step takes the average alone."""
+    n = w.numel()
+    for t, nm in ((w, "w"), (g, "g"), (m, "m"), (v, "v"), (ema, "ema")):
+        _chk(t, name=nm)
+        if t.numel() != n:
+            raise ValueError("guard_clip_adam_ema_update: size mismatch")
+    _chk(state, (2,), "state")
+    _chk_counter(ema_state, "ema_state")
+    check(_lib.load().gg_clip_adam_ema_update(_p(w), _p(g), _p(m), _p(v), _p(ema), n, int(lo), int(hi), _p(state), _p(ema_state),
+                                              _p(_chk_rate(lr)), _p(_chk_guard(rec, "guard_clip_adam_ema_update")), float(b1), float(b2),
+                                              float(eps), float(clip), float(decay), _stream()), "gg_clip_adam_ema_update")
+
+
+def guard_adam_advance(state, rec, b1, b2):
+    """adam_advance unless the record says that this step is skipped."""
+    _chk(state, (2,), "state")
+    check(_lib.load().gg_adam_advance(_p(state), _p(_chk_guard(rec, "guard_adam_advance")), float(b1), float(b2), _stream()), "gg_adam_advance")
