@@ -198,6 +198,15 @@ GG_SIGNATURES = {
 }
 
 
+# The faded blur of D's inputs (include/dblur.h; dblur.hip).  A table of its own for the same reasons;
+# tests/test_blur_cpu.py holds it to its header and to the library's exports.
+DBLUR_SIGNATURES = {
+    "dblur_init": (I, [P, L, P]),
+    "dblur_step": (I, [P, F, L, L, P]),
+    "dblur_apply": (I, [P, P, P, I, I, P]),
+}
+
+
 class LittleGanHipError(RuntimeError):
     pass
 
@@ -230,7 +239,7 @@ def load():
     # before torch, the system runtime it links against would come in as a SECOND runtime and its kernels would see no device.
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name, (res, args) in list(SIGNATURES.items()) + list(GG_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(GG_SIGNATURES.items()) + list(DBLUR_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

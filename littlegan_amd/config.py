@@ -31,7 +31,12 @@ clip_norm (null = off, or a number > 0: each optimizer's gradient is scaled so t
 the all-reduce, is at most clip_norm; the element-wise clip_range of D acts after it) / skip_nonfinite (bool: a network whose gradient
 holds a NaN or an Inf this step keeps its weights, Adam slots and beta powers, and the event is counted; the norms and the counters live
 on the device, so replayed graphs clip and skip by their own gradients, and the counters are part of the checkpoint; both off = the step
-as it was)."""
+as it was),
+blur_init_sigma / blur_fade_kimg (a Gaussian blur of every image the Discriminator reads in the training step, before geom_augment and
+diff_augment, differentiated through on the gen / adj tapes: sigma falls linearly from blur_init_sigma to 0 while D sees its first
+blur_fade_kimg thousand real images, computed on the device from a counter on the device, so replayed graphs follow it, and the counter
+is part of the checkpoint; after the fade the step is the one without the key, launch for launch; 0 = off; excludes use_gp and
+dropout_train)."""
 import json
 import os
 from argparse import ArgumentParser
@@ -140,6 +145,12 @@ DEFAULTS = {
     # network whose gradient holds a NaN or an Inf is left exactly as it was for this step (weights, Adam slots, beta powers) and the
     # skip is counted.  Allowed with every other key.
     'clip_norm': None, 'skip_nonfinite': False,
+    # blur of D's inputs (the discriminator-input blur of Karras et al. 2021): every image D reads in the training step is
+    # filtered with a normalised Gaussian of radius floor(3 sigma) (zero fill), before geom_augment and diff_augment, and the gen / adj
+    # tapes are differentiated through it.  sigma = blur_init_sigma * max(1 - images D has seen / (1000 blur_fade_kimg), 0), computed
+    # on the device; once the radius is 0 the step is the one without the key.  blur_init_sigma 0 = off (at most 10); blur_fade_kimg 200
+    # is StyleGAN3's.  Not gated by diff_augment_p.  Excludes use_gp and dropout_train.
+    'blur_init_sigma': 0.0, 'blur_fade_kimg': 200,
 }
 
 GAN_LOSS_KINDS = {"bce": 0, "logistic": 1, "hinge": 2, "lsgan": 3, "wgan": 4}   # the `kind` of lgo_gan_heads_loss_fwd_bwd; 0 = not its
@@ -399,6 +410,69 @@ def grad_guard_restate(g, gscale, clip_norm, skip, sumsq=None):
     return {"S": S, "bad": bad, "N": N, "c": f32(c), "eff": f32(eff), "skip_now": bool(bad and skip)}
 
 
+BLUR_MAX_SIGMA, BLUR_MAX_RADIUS, BLUR_MAX_FADE_IMAGES = 10.0, 30, 1 << 40
+
+
+def blur_settings(blur_init_sigma=0.0, blur_fade_kimg=200):
+    """The two keys of the Discriminator-input blur, validated: None when blur_init_sigma is 0 (no state exists and no
+    dblur_* function is fetched), else {sigma0: the fp32 value it is used at, fade_images: F = round(blur_fade_kimg * 1000)}.  Raises
+    ValueError for a blur_init_sigma that is not a finite number in [0, 10] (bools and strings refused) and for a blur_fade_kimg whose
+    image count is not an integer in [1, 2^40]."""
+    import math
+    import numpy as np
+    s0 = blur_init_sigma
+    if isinstance(s0, bool) or not isinstance(s0, (int, float)) or not math.isfinite(s0) or not 0.0 <= s0 <= BLUR_MAX_SIGMA:
+        raise ValueError(f"blur_init_sigma must be a finite number in [0, {BLUR_MAX_SIGMA:g}] (0 = off), got {s0!r}")
+    kimg = blur_fade_kimg
+    if isinstance(kimg, bool) or not isinstance(kimg, (int, float)) or not math.isfinite(kimg):
+        raise ValueError(f"blur_fade_kimg must be a number of thousand images, got {kimg!r}")
+    F = int(round(kimg * 1000))
+    if not 1 <= F <= BLUR_MAX_FADE_IMAGES:
+        raise ValueError(f"blur_fade_kimg: {kimg!r} thousand images is {F} images, outside [1, 2^40]")
+    s0 = float(np.float32(s0))
+    if s0 == 0.0:
+        return None
+    return {"sigma0": s0, "fade_images": F}
+
+
+def blur_radius(sigma):
+    """R of DESIGN.md §31 as dblur_apply derives it from the fp32 sigma: min((int)floorf(3.0f * sigma), 30), 0 for a sigma that is not
+    finite or not > 0."""
+    import numpy as np
+    sigma = np.float32(sigma)
+    if not (np.isfinite(sigma) and sigma > 0):
+        return 0
+    with np.errstate(over="ignore"):
+        t = np.float32(3.0) * sigma
+    return BLUR_MAX_RADIUS if t >= np.float32(BLUR_MAX_RADIUS) else int(np.floor(t))
+
+
+def blur_taps(sigma):
+    """(R, w fp32 [R + 1]) of DESIGN.md §31 for an fp32 sigma: t_i = exp2(-(i / sigma)^2) in fp64, Z = t_0 + 2 sum t_i in ascending i,
+    w_i = fp32(t_i / Z).  R == 0 gives the one tap 1."""
+    import numpy as np
+    R = blur_radius(sigma)
+    if R == 0:
+        return 0, np.ones(1, np.float32)
+    t = np.exp2(-(np.arange(R + 1, dtype=np.float64) / np.float64(np.float32(sigma))) ** 2)
+    rest = np.float64(0.0)
+    for v in t[1:]:
+        rest = rest + v
+    return R, (t / (t[0] + np.float64(2.0) * rest)).astype(np.float32)
+
+
+def blur_restate(k, n, settings):
+    """(sigma fp32, R, taps fp32 [R + 1]) of step k as the device computes them (dblur_step, dblur_apply), restated in numpy: k training
+    steps taken before this one, n real images D reads per step over all ranks, settings what blur_settings returned.  sigma is fp64
+    basic operations and one conversion, so it agrees bit for bit.  For the host mirror, the log and the tests."""
+    import numpy as np
+    f64 = np.float64
+    left = f64(1.0) - f64(max(int(k), 0) * int(n)) / f64(settings["fade_images"])
+    sigma = np.float32(f64(np.float32(settings["sigma0"])) * (left if left > 0 else f64(0.0)))
+    R, w = blur_taps(sigma)
+    return sigma, R, w
+
+
 METRIC_NAMES = ("fid", "kid", "prdc")
 
 
@@ -451,6 +525,7 @@ class Arg:
         lr_schedule_settings(self.lr, self.lr_g, self.lr_d, self.lr_adj, self.lr_schedule, self.lr_warmup_steps, self.lr_decay_steps,
                              self.lr_final_ratio)   # a misspelt schedule fails here, not at the first step
         grad_guard_settings(self.clip_norm, self.skip_nonfinite)
+        blur_settings(self.blur_init_sigma, self.blur_fade_kimg)
         self.evaluate_metrics = metric_list(self.evaluate_metrics)   # a misspelt metric fails here, not after the sampling run
         if int(self.kid_subsets) < 0 or int(self.kid_subset_size) < 2 or not 1 <= int(self.prdc_k) <= 15:
             raise ValueError("need kid_subsets >= 0, kid_subset_size >= 2 and 1 <= prdc_k <= 15")

@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
-SOURCES = ["capi.hip", "conv_igemm.hip", "conv_halo.hip", "conv_down3.hip", "conv_up3.hip", "n3_kernels.hip", "n3_pgemm.hip", "wgrad_igemm.hip", "pack.hip", "norm.hip", "dense.hip", "heads.hip", "loss_optim.hip", "augment.hip", "fid.hip", "fid_sqrt.hip", "wgrad_at.hip", "wgrad_at32.hip", "n3_rows.hip", "skinny_mfma.hip", "conv_up4.hip", "runtime.hip", "gp.hip", "input_u8.hip", "diffaug.hip", "pairs.hip", "ada.hip", "r1.hip", "objective.hip", "geom.hip", "sched.hip", "norm_rs.hip", "gradguard.hip"]
+SOURCES = ["capi.hip", "conv_igemm.hip", "conv_halo.hip", "conv_down3.hip", "conv_up3.hip", "n3_kernels.hip", "n3_pgemm.hip", "wgrad_igemm.hip", "pack.hip", "norm.hip", "dense.hip", "heads.hip", "loss_optim.hip", "augment.hip", "fid.hip", "fid_sqrt.hip", "wgrad_at.hip", "wgrad_at32.hip", "n3_rows.hip", "skinny_mfma.hip", "conv_up4.hip", "runtime.hip", "gp.hip", "input_u8.hip", "diffaug.hip", "pairs.hip", "ada.hip", "r1.hip", "objective.hip", "geom.hip", "sched.hip", "norm_rs.hip", "gradguard.hip", "dblur.hip"]
 LIB = os.path.join(PKG, "liblittlegan_hip.so")
 # -packed-fp32-ops (round 5): no v_pk_{add,mul,fma}_f32 anywhere in the library.  The one kernel build that ever gave launch-to-launch
 # different results lost the low half of a packed fp32 subtraction (VGPR pair, high-register select) with a second wave on the SIMD; without
@@ -43,7 +43,7 @@ def build(force=False, verbose=True, variant=None):
     # every source includes lg_internal.h, and through it lg_common.h and the public headers: all headers are every object's dependencies
     inc = os.path.join(os.path.dirname(PKG), "include")
     headers = sorted(glob.glob(os.path.join(HERE, "*.h"))) + sorted(glob.glob(os.path.join(inc, "littlegan_*.h"))) \
-        + [os.path.join(inc, "gradguard.h")]   # (lg_internal.h includes it: the gg_ group)
+        + [os.path.join(inc, "gradguard.h"), os.path.join(inc, "dblur.h")]   # (lg_internal.h includes them: the gg_ and dblur_ groups)
 
     # LG_EXTRA_FLAGS carries the ablation macros of scripts/probe/*.sh ("results wrong, timing only"): the flag set an object
     # was built with is recorded beside it, and an object (hence the library) built with OTHER flags is stale — a probe build

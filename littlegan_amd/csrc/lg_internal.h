@@ -7,6 +7,7 @@
 #pragma once
 #include "lg_common.h"
 #include "../../include/gradguard.h"   // the gg_ group: public, bound from _lib.GG_SIGNATURES, declared outside littlegan_*.h
+#include "../../include/dblur.h"       // the dblur_ group: public, bound from _lib.DBLUR_SIGNATURES, in the same way
 
 // Contraction forms of the implicit-GEMM convs (conv_igemm.hip, conv_halo.hip; chosen by capi.hip):
 //   DOWN : src [B,2Hm,2Wm,Cs] -> out [B,Hm,Wm,N]

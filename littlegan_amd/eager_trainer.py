@@ -17,7 +17,7 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from .config import (ada_settings, diff_augment_bits, gan_loss_kind, geom_augment_bits, grad_guard_settings, lr_schedule_settings,
+from .config import (ada_settings, blur_restate, blur_settings, diff_augment_bits, gan_loss_kind, geom_augment_bits, grad_guard_settings, lr_schedule_settings,
                      r1_settings, r2_settings, relativistic_setting)
 from .dist import GradSync
 from .model import Adjuster, Discriminator, Generator, ParamStore
@@ -176,6 +176,22 @@ class EagerTrainer:
             self._guard_lr = None
             if self.lr_state is None:
                 self._guard_lr = torch.tensor([self.opt_cfg[m][0] for m in "GDA"], dtype=torch.float32, device=self.device)
+        # blur of D's inputs (the reference has none): None = off, no state and no launch of its own; else {k, sigma, 0, 0}
+        # on the device (dblur_init: written from a launch scalar), advanced by dblur_step on every step whose restated radius is >= 1.
+        # _blur_k mirrors k on the host (every rank walks the same counter: no collective): it decides, before anything is enqueued,
+        # whether a step blurs at all.  sigma never rises, so once the radius is 0 the step is the one without the key
+        self.blur = blur_settings(getattr(args, "blur_init_sigma", 0.0), getattr(args, "blur_fade_kimg", 200))
+        if self.blur is not None:
+            if self.use_gp:
+                raise ValueError("blur_init_sigma and use_gp exclude each other: the penalty's double backward through the blur is not "
+                                 "built (DESIGN.md §31)")
+            if self.dropout:
+                raise ValueError("blur_init_sigma and dropout_train exclude each other: under the blur the Adjuster encodes `fake` itself "
+                                 "and the masks of the rows D used to hand over are not built for that pass (DESIGN.md §31)")
+            if int(getattr(args, "image_channel", 3)) != 3:
+                raise ValueError("blur_init_sigma needs 3-channel images")
+            self.blur_state = ops.blur_init(0, device=self.device)
+            self._blur_k, self._blur_k_step, self._blur_ticked = 0, 0, False
         self._init_dir()
         # eager_trainer.py:36-43: restore the newest checkpoint (weights, the three optimizers' slots and beta powers)
         # and the epoch from status.json when args.restore is set
@@ -195,7 +211,7 @@ class EagerTrainer:
         """inp: real_image_1, real_cond_1, real_image_2, real_cond_2, noise, new_image (device fp32, NHWC); with use_gp also
         gp_eps [B] (the penalty's interpolation weights, U[0,1)); with dropout_train also dropout_key (int64 [2] = {seed, key_offset} of
         the step's mask stream, draw_dropout_key); with diff_augment or geom_augment also diffaug_key (the same kind of pair, draw_diffaug_key:
-        both read it, on Philox blocks of their own).
+        both read it, on Philox blocks of their own; the blur of blur_init_sigma draws nothing and needs no key).
         Returns (fake_image, adj_image|None, gen_loss, disc_loss, adj_loss|None) — losses are 1-element device tensors
         (no host sync on the hot path)."""
         a = self.args
@@ -221,6 +237,15 @@ class EagerTrainer:
         # differentiable augmentation call slots: 0 = D on [new_image ; fake], 1 = D on the Adjuster's output.  D reads
         # T(image); `fake` itself (the L1 term, the Adjuster's input, the returned image) stays un-augmented.
         aug_key, S = None, img1.shape[1]
+        # blur of D's inputs: D reads T(Geo(Blur(image))).  Live while the restated radius of this step is >= 1; a step
+        # with live blur is an augmenting step (the Adjuster encodes `fake` itself), a faded one enqueues nothing of the blur's
+        blur = None
+        if self.blur is not None:
+            if not self._blur_ticked:   # (graph_step has counted this step already, whichever way it runs it)
+                self._blur_tick()
+            if self.blur_live(self._blur_k_step):
+                blur = self.blur_state
+        augmenting = self.augmenting or blur is not None
         if self.augmenting:
             aug_key = inp.get("diffaug_key")
             if aug_key is None:
@@ -244,6 +269,8 @@ class EagerTrainer:
         if self.lr_state is not None:   # the step's first launch: s(k) and the three rates of this step, then k += 1
             ls = self.lr_sched
             ops.sched_step(self.lr_state, ls["kind"], ls["warmup"], ls["decay"], ls["final_ratio"], *(self.opt_cfg[m][0] for m in "GDA"))
+        if blur is not None:   # the first of the blur's launches: sigma(k) of this step, then k += 1
+            ops.blur_step(blur, self.blur["sigma0"], self._blur_images_per_step(), self.blur["fade_images"])
         fake = G([noise, c2], ctx_g, out=d_in[B:])
         ctx_d: dict = {}
         run_adj = bool(a.train_adj and batch_no > 10)
@@ -255,9 +282,11 @@ class EagerTrainer:
         x_all = d_in         # ... and the whole batch D reads, [real ; fake]: the fake half is the R2 penalty's input
         kind = self.gan_kind
         lk = dict(logits=True) if kind else {}   # a logit-side objective: the heads keep z_pr (same launches, another finaliser)
-        if self.augmenting:
-            par0, geo0 = self._augment_draw(aug_key, 0, 2 * B, S)
-            d_aug = self._augment_fwd(d_in, par0, geo0)   # T(Geo(d_in)), either alone when the other key is off
+        par0 = geo0 = par1 = geo1 = None
+        if augmenting:
+            if self.augmenting:
+                par0, geo0 = self._augment_draw(aug_key, 0, 2 * B, S)
+            d_aug = self._augment_fwd(d_in, par0, geo0, blur)   # T(Geo(Blur(d_in))), each present only when its key is on / live
             x_real, x_all = d_aug[:B], d_aug
             p = D.forward_packed(d_aug, ctx_d, keep_maps=False, **lk)   # the maps are those of T(fake): not handed over
             if adaptive and not run_adj:   # after the step's last draw: step n + 1 is the first to see a new p
@@ -318,8 +347,8 @@ class EagerTrainer:
         else:
             ops.bce_heads_loss(p[B:], c2, soft(1.0), 1.0, 1.0, self.losses["gen"], dz_g, False)
         g_img = D.backward(ctx_d, dz_g, need_wgrad=False, need_input_grad=True, rows=slice(B, 2 * B))
-        if self.augmenting:   # the gen tape is differentiated through the augmentation, Geo^T(T^T g): rows B..2B of slot 0
-            g_img = self._augment_bwd(g_img, None if par0 is None else par0[B:], None if geo0 is None else geo0[B:])
+        if augmenting:   # the gen tape is differentiated through the augmentation, Blur(Geo^T(T^T g)): rows B..2B of slot 0
+            g_img = self._augment_bwd(g_img, None if par0 is None else par0[B:], None if geo0 is None else geo0[B:], blur)
         dpre = torch.empty_like(g_img)
         ops.l1_tanh_loss(img2, fake, g_img, dpre, self.losses["gen"], a.l1_lambda, True)
         rng_g = train_weight_range(a, "G", batch_no)
@@ -333,7 +362,7 @@ class EagerTrainer:
             ctx_a: dict = {}
             # encoder(fake) was computed by D above with the same weights: hand its 4 maps to the Adjuster.  Under diff_augment D
             # encoded T(fake), so `fake` is encoded here, by one more B-row pass whose maps take the same place
-            if self.augmenting:
+            if augmenting:
                 tails = A.encoder(fake)
             else:
                 tails = [m[B:] for m in ctx_d["enc_maps"]]  # fp32 maps (f32 path) / bf16 mirrors + the fp32 top map (bf16 path)
@@ -341,11 +370,12 @@ class EagerTrainer:
             # handed-over maps keep the masks call 0 drew for them — no tape differentiates through the skips)
             adj_image = A([img1, adj_in_cond], ctx_a, enc_tails=tails, drop=drop[1])
             ctx_d2: dict = {}
-            if self.augmenting:
-                par1, geo1 = self._augment_draw(aug_key, 1, 2 * B, S)
+            if augmenting:
+                if self.augmenting:
+                    par1, geo1 = self._augment_draw(aug_key, 1, 2 * B, S)
                 if adaptive:   # both draws of the step have read p: the real rows of slot 0 feed the controller
                     self._ada_control(p, B)
-                p_a = D.forward_packed(self._augment_fwd(adj_image, par1, geo1), ctx_d2, keep_maps=False, top_only=True, **lk)
+                p_a = D.forward_packed(self._augment_fwd(adj_image, par1, geo1, blur), ctx_d2, keep_maps=False, top_only=True, **lk)
             else:
                 p_a = D.forward_packed(adj_image, ctx_d2, keep_maps=False, top_only=True, drop=drop[2], **lk)
             dz_a = torch.empty(2 * B, 1 + c, dtype=torch.float32, device=self.device)
@@ -357,8 +387,8 @@ class EagerTrainer:
             else:
                 ops.bce_heads_loss(p_a, adj_t_cond, soft(1.0), 1.0, 1.0, self.losses["adj"], dz_a, False)
             g_adj = D.backward(ctx_d2, dz_a, need_wgrad=False, need_input_grad=True)
-            if self.augmenting:
-                g_adj = self._augment_bwd(g_adj, par1, geo1)
+            if augmenting:
+                g_adj = self._augment_bwd(g_adj, par1, geo1, blur)
             dpre_a = torch.empty_like(g_adj)
             # target = [img2 ; img1]: one call per half instead of a 2B-image concatenation (lambda / 2 over half the elements is
             # the same scale, exactly: the element count is a multiple of a power of two)
@@ -390,22 +420,52 @@ class EagerTrainer:
         geo = ops.geom_draw(key, call, 0, rows, S, self.geom, None if self.ada is None else self.ada_state) if self.geom else None
         return par, geo
 
-    def _augment_fwd(self, images, par, geo):
-        """What D reads of `images`: T(Geo(images)), Geo alone when diff_augment is off, T alone when geom_augment
-        is — then exactly the launches of the diff_augment step"""
+    def _augment_fwd(self, images, par, geo, blur=None):
+        """What D reads of `images`: T(Geo(Blur(images))), Geo alone when diff_augment is off, T alone when
+        geom_augment is — then exactly the launches of the diff_augment step; Blur (blur: its state) only while the blur is live"""
+        if blur is not None:
+            images = ops.blur_apply(images, blur)
         if geo is not None:
             images = ops.geom_fwd(images, geo)
         if par is not None:
             images = ops.diffaug_fwd(images, par)
         return images
 
-    def _augment_bwd(self, g, par, geo):
-        """The adjoint of _augment_fwd on an image gradient: Geo^T(T^T g)"""
+    def _augment_bwd(self, g, par, geo, blur=None):
+        """The adjoint of _augment_fwd on an image gradient: Blur(Geo^T(T^T g)) — the blur is its own adjoint"""
         if par is not None:
             g = ops.diffaug_bwd(g, par)
         if geo is not None:
             g = ops.geom_bwd(g, geo)
+        if blur is not None:
+            g = ops.blur_apply(g, blur)
         return g
+
+    # ------------------------------------------------------------------ faded blur of D's inputs (DESIGN.md §31)
+    def _blur_images_per_step(self):
+        """n of the schedule: the real images D reads per step over all ranks"""
+        return int(self.args.batch_size) * int(self.world)
+
+    def _blur_tick(self):
+        """Advances the host mirror of the blur's step counter, once per training step: at the top of train_step_from_inputs, or at the top
+        of graph_step for a step that goes through it (eager, captured or replayed).  _blur_k_step: the k of the step now running."""
+        self._blur_k_step = self._blur_k
+        self._blur_k += 1
+
+    def blur_live(self, k=None):
+        """Whether the step after k training steps blurs: the restated radius is >= 1.  k None = the step now running (inside one), else
+        the next one.  False for good once it has been false: sigma never rises."""
+        if self.blur is None:
+            return False
+        if k is None:
+            k = self._blur_k_step if self._blur_ticked else self._blur_k
+        return blur_restate(k, self._blur_images_per_step(), self.blur)[1] >= 1
+
+    def blur_sigma_now(self):
+        """The sigma of the most recent step that blurred: the 1-element device view of the state's second word (no synchronisation;
+        float() of it waits like float() of a loss), None when the key is off.  After the fade no launch writes it any more: it keeps the
+        last live value, and blur_live() says that the step no longer blurs."""
+        return None if self.blur is None else self.blur_state[1:2]
 
     def _ada_tick(self):
         """Advances the host mirror of the state's step counter, once per training step: at the top of train_step_from_inputs, or at
@@ -552,7 +612,10 @@ class EagerTrainer:
         — R1, R2 or both, which share a schedule; the last is constant with r1_gamma == 0 and r2_gamma == 0)."""
         a = self.args
         part = (batch_no // (a.partition_interval + 1)) % 3 if (a.use_partition and batch_no % (a.partition_interval + 1) == 0) else -1
-        return part, bool(a.train_adj and batch_no > 10), self.r1_step(batch_no) or self.r2_step(batch_no)
+        kind = part, bool(a.train_adj and batch_no > 10), self.r1_step(batch_no) or self.r2_step(batch_no)
+        if self.blur is not None:   # with blur_init_sigma also: whether this step blurs (DESIGN.md §31) — a faded step holds no blur launch
+            kind += (self.blur_live(),)
+        return kind
 
     def graph_step(self, batch_no: int, inp: Dict[str, torch.Tensor]):
         """train_step_from_inputs through a captured HIP graph, one graph per step kind (full step, the three partition
@@ -571,10 +634,15 @@ class EagerTrainer:
         if self.ada is not None and self.ada["target"] is not None:
             self._ada_tick()   # one training step, whether it runs eagerly, is captured and replayed, or is a replay alone
             self._ada_ticked = True
+        if self.blur is not None:
+            self._blur_tick()   # in the same way
+            self._blur_ticked = True
         try:
             return self._graph_step(batch_no, inp)
         finally:
             self._ada_ticked = False
+            if self.blur is not None:
+                self._blur_ticked = False
 
     def _graph_step(self, batch_no: int, inp: Dict[str, torch.Tensor]):
         kind = self.step_kind(batch_no)
@@ -769,7 +837,10 @@ class EagerTrainer:
                         cnt = self.guard_counts()
                         gn = " GN g/d/a " + "/".join(f"{x:.3e}" for x in self.grad_norm_now().tolist()) \
                              + " Skip g/d/a " + "/".join(str(cnt[m][0]) for m in "GDA")
-                    print(f"  [{seen}] LossG {lg:.4f} LossD {ld:.4f} LossA {la:.4f}{r1}{aug_p}{lrs}{gn}")
+                    bl = ""
+                    if self.blur is not None and self.blur_live(self._blur_k_step):   # the sigma of the step the losses are of
+                        bl = f" Blur {float(self.blur_sigma_now()):.4f}"
+                    print(f"  [{seen}] LossG {lg:.4f} LossD {ld:.4f} LossA {la:.4f}{r1}{aug_p}{lrs}{gn}{bl}")
                 if b % a.freq_test == 0 and io and self.test_cond is not None:
                     self.predict(self.test_noise, self.test_cond, self.test_image,
                                  os.path.join(a.result_dir, "test", "gen", "%d-%d.jpg" % (e, b)),
@@ -913,6 +984,8 @@ class EagerTrainer:
         if self.guard is not None:   # the six counters {skipped, non-finite} of G, D, A (absent when the guard is off)
             cnt = self.guard_counts()
             ck["grad_guard_state"] = [int(x) for m in "GDA" for x in cnt[m]]
+        if self.blur is not None:   # the blur's step counter, from the host mirror (absent when the key is off)
+            ck["blur_state"] = int(self._blur_k)
         return ck
 
     def save_checkpoint(self, tag: str) -> str:
@@ -968,6 +1041,11 @@ class EagerTrainer:
                     and all(guard_cnt[i] <= guard_cnt[i + 1] for i in (0, 2, 4))):
                 raise ValueError(f"{path}: grad_guard_state {guard_cnt!r} is not the guard's counters (six integers {{skipped, non-finite}} "
                                  "of G, D, A, 0 <= skipped <= non-finite < 2^31)")
+        blur_k = None
+        if self.blur is not None and "blur_state" in ck:   # checked before anything is loaded, like the words above
+            blur_k = ck["blur_state"]
+            if isinstance(blur_k, bool) or not isinstance(blur_k, int) or not 0 <= blur_k < 2 ** 31:
+                raise ValueError(f"{path}: blur_state {blur_k!r} is not a step counter (one integer, 0 <= k < 2^31)")
         st.flat.copy_(ck["flat"])
         st.m.copy_(ck["adam_m"])
         st.v.copy_(ck["adam_v"])
@@ -996,6 +1074,13 @@ class EagerTrainer:
                 print(f"{path}: no gradient-guard counters in this checkpoint; they start at zero")
             for i, m in enumerate("GDA"):
                 ops.guard_init(*(guard_cnt[2 * i:2 * i + 2] if guard_cnt is not None else (0, 0)), out=self._guard_rec[m])
+        if self.blur is not None:
+            if blur_k is None:
+                print(f"{path}: no blur step counter in this checkpoint; the fade starts at k = 0")
+            self._blur_k = self._blur_k_step = blur_k or 0
+            ops.blur_init(self._blur_k, out=self.blur_state)
+        elif "blur_state" in ck:
+            print(f"{path}: this run does not blur (blur_init_sigma = 0); the checkpoint's blur step counter is ignored")
         st.bump()
 
     def export_model_checkpoint(self):

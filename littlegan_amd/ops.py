@@ -1971,3 +1971,50 @@ def guard_adam_advance(state, rec, b1, b2):
     """adam_advance unless the record says that this step is skipped."""
     _chk(state, (2,), "state")
     check(_lib.load().gg_adam_advance(_p(state), _p(_chk_guard(rec, "guard_adam_advance")), float(b1), float(b2), _stream()), "gg_adam_advance")
+
+
+# ------------------------------------------------------------------ faded blur of D's inputs (dblur.hip, DESIGN.md §31; include/dblur.h)
+def _chk_blur(t, who):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (4,)):
+        raise ValueError(f"{who}: the blur's state is a contiguous fp32 [4] CUDA tensor {{k, sigma, 0, 0}} (blur_init)")
+    return t
+
+
+def blur_init(k0=0, device="cuda", out=None):
+    """The blur's state {k0, 0, 0, 0} (fp32 [4]: the int32 step counter, fp32 sigma, two reserved words), written by a one-block kernel
+    from a launch scalar: no host-to-device copy."""
+    if out is None:
+        out = torch.empty(4, dtype=torch.float32, device=device)
+    _chk_blur(out, "blur_init")
+    check(_lib.load().dblur_init(_p(out), int(k0), _stream()), "dblur_init")
+    return out
+
+
+def blur_step(state, sigma0, images_per_step, fade_images):
+    """One step of the fade: state[1] = sigma(k) = sigma0 * max(1 - k * images_per_step / fade_images, 0) (fp64, one conversion), then
+    k += 1 (saturating).  See include/dblur.h"""
+    _chk_blur(state, "blur_step")
+    check(_lib.load().dblur_step(_p(state), float(sigma0), int(images_per_step), int(fade_images), _stream()), "dblur_step")
+    return state
+
+
+def blur_read(state):
+    """(k, sigma) on the host.  Synchronises: for logs, checkpoints and tests, not for the step."""
+    _chk_blur(state, "blur_read")
+    host = state.detach().cpu()
+    return int(host.view(torch.int32)[0]), float(host[1])
+
+
+def blur_apply(x, state, out=None):
+    """Blur(x): x [rows, S, S, 3] fp32 filtered with the Gaussian of sigma = state[1] (read on the device; radius min(floor(3 sigma), 30),
+    zero fill), R == 0 a copy.  The operator is its own adjoint: the same call on an image gradient is the backward pass."""
+    _chk(x, name="image")
+    rows, S, W, c = x.shape
+    if W != S or c != 3:
+        raise ValueError(f"dblur_apply: square 3-channel NHWC images only, got {tuple(x.shape)}")
+    _chk_blur(state, "blur_apply")
+    if out is None:
+        out = torch.empty_like(x)
+    _chk(out, x.shape, "out")
+    check(_lib.load().dblur_apply(_p(x), _p(state), _p(out), rows, S, _stream()), "dblur_apply")
+    return out
