@@ -546,7 +546,9 @@ enum D3Tiling { D3_NONE = 0, D3_PLAIN, D3_PAIR, D3_N64 };
 static D3Tiling down3_tiling(int B, int Hm, int Wm, int Cs, int N) {
   static int off = -1;
   if (off < 0) off = lg_env_flag("LG_NO_DOWN3") ? 1 : 0;   // kill switch (cached: per-launch path, the table lookup takes a mutex)
-  if (off || B <= 0 || Cs % KC) return D3_NONE;
+  // LG_NO_HALO takes this kernel out with the halo-tile kernel: asked HERE, so that the entry points that come to this file
+  // without passing lg_conv_igemm_ex (lg_convT_s2_dgrad_nf, the NORM / BWDNORM forms and their _supported queries) follow it too
+  if (off || !lg_halo_enabled() || B <= 0 || Cs % KC) return D3_NONE;
   if ((long long)4 * Hm * Wm * Cs * 2 * 2 >= (1ll << 31)) return D3_NONE;  // buffer descriptor: two samples below the OOB offset
   const bool pair = Hm == 8 && Wm == 8 && B % 2 == 0;  // 8 x 8 maps: a tile = two samples side by side
   if (!pair && (Hm % TH || Wm % TW)) return D3_NONE;

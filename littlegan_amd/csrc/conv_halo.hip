@@ -743,9 +743,12 @@ extern "C" size_t lg_conv_stats_workspace_bytes(int mode, int B, int Hm, int Wm,
   return (size_t)B * (size_t)worst * 3 * sizeof(double) + 256;
 }
 
-// 1 if the halo kernel covers this shape (then the bf16 mirror alone is enough as its source), else 0
+// 1 if the halo kernel covers this shape (then the bf16 mirror alone is enough as its source), else 0.  The answer is what
+// lg_conv_igemm_ex will do: under LG_NO_HALO it never asks lg_conv_halo_try, so no shape is covered and every caller that decides
+// from here which copies of a tensor exist (lg_conv_fwd_stats_fused, the need32 / drop32 routing of model.py) keeps the fp32 one.
 extern "C" int lg_conv_halo_supported(int mode, int dtype, int B, int Hm, int Wm, int Cs, int N) {
   static const int dummy = 0;
+  if (!lg_halo_enabled()) return 0;
   return lg_conv_halo_try(mode, dtype, nullptr, dtype == LG_DT_BF16 ? &dummy : nullptr, &dummy, nullptr, nullptr, nullptr, B,
                           Hm, Wm, Cs, N, 0, nullptr, 0, nullptr, nullptr) == LG_OK ? 1 : 0;
 }

@@ -589,7 +589,8 @@ enum U3Tiling { U3_NONE = 0, U3_N64, U3_N32 };   // 128 -> 64 channels: one 8-wa
 static U3Tiling up3_tiling(int B, int Hm, int Wm, int Cs, int N) {
   static int off = -1;
   if (off < 0) off = lg_env_flag("LG_NO_UP3") ? 1 : 0;   // kill switch (cached: per-launch path, the table lookup takes a mutex)
-  if (off || B <= 0 || Hm % TH || Wm % TW) return U3_NONE;
+  // LG_NO_HALO takes this kernel out too: asked HERE, so that lg_conv2d_s2_dgrad_nf (which does not pass lg_conv_igemm_ex) follows it
+  if (off || !lg_halo_enabled() || B <= 0 || Hm % TH || Wm % TW) return U3_NONE;
   if ((long long)Hm * Wm * Cs * 2 * 2 >= (1ll << 31)) return U3_NONE;  // buffer descriptor: two samples below the OOB offset
   if ((long long)B * 4 * Hm * Wm * N * 2 >= 0xffffff00ll) return U3_NONE;   // the row stores: one descriptor over the whole output
   return (Cs == 128 && N == 64) ? U3_N64 : (Cs == 64 && N == 32) ? U3_N32 : U3_NONE;

@@ -389,7 +389,8 @@ enum U4Tiling { U4_NONE = 0, U4_PLAIN, U4_PAIR };
 static U4Tiling up4_tiling(int B, int Hm, int Wm, int Cs, int N) {
   static int off = -1;
   if (off < 0) off = lg_env_flag("LG_NO_UP4") ? 1 : 0;   // kill switch (cached: per-launch path, the table lookup takes a mutex)
-  if (off || B <= 0 || Cs % KC || N % 128) return U4_NONE;
+  // LG_NO_HALO takes this kernel out too: asked HERE, so that lg_conv2d_s2_dgrad_nf (which does not pass lg_conv_igemm_ex) follows it
+  if (off || !lg_halo_enabled() || B <= 0 || Cs % KC || N % 128) return U4_NONE;
   if ((long long)Hm * Wm * Cs * 2 * 2 >= (1ll << 31)) return U4_NONE;   // two samples below the out-of-range offset of the halo loads
   if (Hm == 8 && Wm == 8 && B % 2 == 0) return U4_PAIR;                 // 8 x 8 maps: a tile = two samples
   return (Hm % TH == 0 && Wm % TW == 0) ? U4_PLAIN : U4_NONE;
