@@ -1,5 +1,6 @@
 """ctypes binding of liblittlegan_hip.so.  The C ABI is every function declared in include/littlegan_*.h; SIGNATURES below is its one
-table (tests/test_abi.py holds it to the headers and to the symbols the library exports).
+table (tests/test_abi.py holds it to the headers and to the symbols the library exports).  A new group is a new
+include/littlegan_<group>.h with `lg<group>_` names: its entries go in SIGNATURES, its rows in tests/test_memory_contract_gpu.py.
 
 The product path has NO fallback: if the shared library is missing this module raises at
 import of the symbol table, and every op raises `LittleGanHipError` on a non-zero return.
@@ -180,30 +181,20 @@ SIGNATURES = {
     "lgadj_instnorm_apply_p_rs": (I, [P, P, I, P, P, P, P, P, P, P, I, L, I, F, P]),
     "lgadj_convT_s2_fwd_ns_supported": (I, [I, I, I, I, I, I]),
     "lgadj_convT_s2_fwd_stats_ns": (I, [P, P, F, P, P, P, P, I, P, P, P, I, I, I, I, I, I, P, Z, P, P]),
-}
-
-
-# Global-norm gradient clipping and the non-finite step guard (include/gradguard.h; gradguard.hip, loss_optim.hip).  A
-# table of its own: the names are not `lg*_` names and their header is not one of include/littlegan_*.h, so SIGNATURES and what holds it
-# to the headers stay as they are; tests/test_grad_guard_cpu.py holds THIS table to its header and to the library's exports.
-GG_SIGNATURES = {
-    "gg_partials_count": (I, [L]),
-    "gg_workspace_bytes": (Z, [L]),
-    "gg_init": (I, [P, I, I, P]),
-    "gg_sumsq_partial": (I, [P, L, P, Z, P]),
-    "gg_finalise": (I, [P, L, P, F, F, I, P]),
-    "gg_clip_adam_update": (I, [P, P, P, P, L, P, P, P, F, F, F, F, P]),
-    "gg_clip_adam_ema_update": (I, [P, P, P, P, P, L, L, L, P, P, P, P, F, F, F, F, F, P]),
-    "gg_adam_advance": (I, [P, P, F, F, P]),
-}
-
-
-# The faded blur of D's inputs (include/dblur.h; dblur.hip).  A table of its own for the same reasons;
-# tests/test_blur_cpu.py holds it to its header and to the library's exports.
-DBLUR_SIGNATURES = {
-    "dblur_init": (I, [P, L, P]),
-    "dblur_step": (I, [P, F, L, L, P]),
-    "dblur_apply": (I, [P, P, P, I, I, P]),
+    # global-norm gradient clipping and the non-finite step guard (include/littlegan_guard.h; gradguard.hip, loss_optim.hip):
+    # the fp64 sum of squares, the record, and the Adam passes that read their scale and skip flag from it
+    "lgg_partials_count": (I, [L]),
+    "lgg_workspace_bytes": (Z, [L]),
+    "lgg_init": (I, [P, I, I, P]),
+    "lgg_sumsq_partial": (I, [P, L, P, Z, P]),
+    "lgg_finalise": (I, [P, L, P, F, F, I, P]),
+    "lgg_clip_adam_update": (I, [P, P, P, P, L, P, P, P, F, F, F, F, P]),
+    "lgg_clip_adam_ema_update": (I, [P, P, P, P, P, L, L, L, P, P, P, P, F, F, F, F, F, P]),
+    "lgg_adam_advance": (I, [P, P, F, F, P]),
+    # the faded blur of D's inputs (include/littlegan_blur.h; dblur.hip): the state, its step, Blur (its own adjoint)
+    "lgblur_init": (I, [P, L, P]),
+    "lgblur_step": (I, [P, F, L, L, P]),
+    "lgblur_apply": (I, [P, P, P, I, I, P]),
 }
 
 
@@ -239,7 +230,7 @@ def load():
     # before torch, the system runtime it links against would come in as a SECOND runtime and its kernels would see no device.
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    for name, (res, args) in list(SIGNATURES.items()) + list(GG_SIGNATURES.items()) + list(DBLUR_SIGNATURES.items()):
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

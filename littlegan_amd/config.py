@@ -387,7 +387,7 @@ def grad_guard_settings(clip_norm=None, skip_nonfinite=False):
 
 
 def grad_guard_restate(g, gscale, clip_norm, skip, sumsq=None):
-    """The record of DESIGN.md §30 as the device computes it (gg_finalise), restated in numpy: S = the fp64 sum of the squares of g (or
+    """The record of DESIGN.md §30 as the device computes it (lgg_finalise), restated in numpy: S = the fp64 sum of the squares of g (or
     `sumsq` when given: the device's own S, ops.grad_sumsq — g is then not read), then the fp32 steps of the definition.  clip_norm 0 = no
     clipping.  -> {S (float64), bad, N, c, eff (float32), skip_now (bool)}.  The order of numpy's additions is not the device's: N agrees
     to 1 fp32 ulp, and c, eff follow bit for bit from a given N.  For the log and the tests."""
@@ -436,7 +436,7 @@ def blur_settings(blur_init_sigma=0.0, blur_fade_kimg=200):
 
 
 def blur_radius(sigma):
-    """R of DESIGN.md §31 as dblur_apply derives it from the fp32 sigma: min((int)floorf(3.0f * sigma), 30), 0 for a sigma that is not
+    """R of DESIGN.md §31 as lgblur_apply derives it from the fp32 sigma: min((int)floorf(3.0f * sigma), 30), 0 for a sigma that is not
     finite or not > 0."""
     import numpy as np
     sigma = np.float32(sigma)
@@ -462,7 +462,7 @@ def blur_taps(sigma):
 
 
 def blur_restate(k, n, settings):
-    """(sigma fp32, R, taps fp32 [R + 1]) of step k as the device computes them (dblur_step, dblur_apply), restated in numpy: k training
+    """(sigma fp32, R, taps fp32 [R + 1]) of step k as the device computes them (lgblur_step, lgblur_apply), restated in numpy: k training
     steps taken before this one, n real images D reads per step over all ranks, settings what blur_settings returned.  sigma is fp64
     basic operations and one conversion, so it agrees bit for bit.  For the host mirror, the log and the tests."""
     import numpy as np

@@ -42,8 +42,7 @@ def build(force=False, verbose=True, variant=None):
     os.makedirs(objdir, exist_ok=True)
     # every source includes lg_internal.h, and through it lg_common.h and the public headers: all headers are every object's dependencies
     inc = os.path.join(os.path.dirname(PKG), "include")
-    headers = sorted(glob.glob(os.path.join(HERE, "*.h"))) + sorted(glob.glob(os.path.join(inc, "littlegan_*.h"))) \
-        + [os.path.join(inc, "gradguard.h"), os.path.join(inc, "dblur.h")]   # (lg_internal.h includes them: the gg_ and dblur_ groups)
+    headers = sorted(glob.glob(os.path.join(HERE, "*.h"))) + sorted(glob.glob(os.path.join(inc, "littlegan_*.h")))
 
     # LG_EXTRA_FLAGS carries the ablation macros of scripts/probe/*.sh ("results wrong, timing only"): the flag set an object
     # was built with is recorded beside it, and an object (hence the library) built with OTHER flags is stale — a probe build

@@ -1,10 +1,10 @@
 // A faded Gaussian blur of every image the Discriminator reads (the reference has none): a separable FIR of up to 61 taps
 // on [rows, S, S, 3] fp32, its sigma read from 16 bytes of device state that one launch at the top of the step advances.  A captured
 // graph bakes launch scalars in; sigma, and with it the radius and the taps, come from the state, so a replayed step blurs by ITS sigma.
-// The operator is its own adjoint, so dblur_apply serves the forward and the backward.  The definition is stated in include/dblur.h and
+// The operator is its own adjoint, so lgblur_apply serves the forward and the backward.  The definition is stated in include/littlegan_blur.h and
 // restated on the host by config.blur_restate.
 //
-// dblur_apply: a workgroup of 256 threads owns a strip of the image TW = 32 pixels wide and walks down it in chunks of CH = 32 rows; per
+// lgblur_apply: a workgroup of 256 threads owns a strip of the image TW = 32 pixels wide and walks down it in chunks of CH = 32 rows; per
 // chunk three phases through LDS:
 //   stage   the chunk's rows of the input, TW + 2R columns widened to whole 4-pixel groups, 16-byte loads, zeros where the row ends
 //   H       LDS -> LDS: a thread owns 4 consecutive pixels of one channel of one row and slides over the 2R + 4 sources they share: one
@@ -203,35 +203,35 @@ __global__ __launch_bounds__(DB_THREADS) void dblur_apply_kernel(const float* __
 
 }  // namespace
 
-extern "C" int dblur_init(float* state, long long k0, void* stream) {
-  LG_CHECK_ARG(state, "dblur_init: null pointer");
-  LG_CHECK_ARG(((uintptr_t)state & 15) == 0, "dblur_init: state must be 16-byte aligned");
-  LG_CHECK_ARG(k0 >= 0 && k0 < (1LL << 31), "dblur_init: k0=%lld outside 0 .. 2^31 - 1", k0);
+extern "C" int lgblur_init(float* state, long long k0, void* stream) {
+  LG_CHECK_ARG(state, "lgblur_init: null pointer");
+  LG_CHECK_ARG(((uintptr_t)state & 15) == 0, "lgblur_init: state must be 16-byte aligned");
+  LG_CHECK_ARG(k0 >= 0 && k0 < (1LL << 31), "lgblur_init: k0=%lld outside 0 .. 2^31 - 1", k0);
   hipLaunchKernelGGL(dblur_init_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, (int)k0);
-  LG_CHECK_LAUNCH("dblur_init");
+  LG_CHECK_LAUNCH("lgblur_init");
   lg_note_kernel("dblur_init_kernel");
   return LG_OK;
 }
 
-extern "C" int dblur_step(float* state, float sigma0, long long images_per_step, long long fade_images, void* stream) {
-  LG_CHECK_ARG(state, "dblur_step: null pointer");
-  LG_CHECK_ARG(((uintptr_t)state & 15) == 0, "dblur_step: state must be 16-byte aligned");
-  LG_CHECK_ARG(sigma0 >= 0.f && sigma0 <= 3.402823466e38f, "dblur_step: sigma0=%g must be finite and >= 0", (double)sigma0);
-  LG_CHECK_ARG(images_per_step >= 1 && images_per_step <= (1LL << 31), "dblur_step: images_per_step=%lld outside 1 .. 2^31",
+extern "C" int lgblur_step(float* state, float sigma0, long long images_per_step, long long fade_images, void* stream) {
+  LG_CHECK_ARG(state, "lgblur_step: null pointer");
+  LG_CHECK_ARG(((uintptr_t)state & 15) == 0, "lgblur_step: state must be 16-byte aligned");
+  LG_CHECK_ARG(sigma0 >= 0.f && sigma0 <= 3.402823466e38f, "lgblur_step: sigma0=%g must be finite and >= 0", (double)sigma0);
+  LG_CHECK_ARG(images_per_step >= 1 && images_per_step <= (1LL << 31), "lgblur_step: images_per_step=%lld outside 1 .. 2^31",
                images_per_step);
-  LG_CHECK_ARG(fade_images >= 1 && fade_images <= (1LL << 40), "dblur_step: fade_images=%lld outside 1 .. 2^40", fade_images);
+  LG_CHECK_ARG(fade_images >= 1 && fade_images <= (1LL << 40), "lgblur_step: fade_images=%lld outside 1 .. 2^40", fade_images);
   hipLaunchKernelGGL(dblur_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, sigma0, images_per_step, fade_images);
-  LG_CHECK_LAUNCH("dblur_step");
+  LG_CHECK_LAUNCH("lgblur_step");
   lg_note_kernel("dblur_step_kernel");
   return LG_OK;
 }
 
-extern "C" int dblur_apply(const float* x, const float* state, float* out, int rows, int S, void* stream) {
-  LG_CHECK_ARG(x && state && out, "dblur_apply: null pointer");
-  LG_CHECK_ARG(x != out, "dblur_apply: in-place call");
-  LG_CHECK_ARG(rows > 0 && rows <= (1 << 20), "dblur_apply: bad row count %d", rows);
-  LG_CHECK_ARG(S >= 8 && S % 8 == 0 && S <= 1024, "dblur_apply: image side %d must be a multiple of 8, at least 8, at most 1024", S);
-  LG_CHECK_ARG((((uintptr_t)x | (uintptr_t)state | (uintptr_t)out) & 15) == 0, "dblur_apply: images and state must be 16-byte aligned");
+extern "C" int lgblur_apply(const float* x, const float* state, float* out, int rows, int S, void* stream) {
+  LG_CHECK_ARG(x && state && out, "lgblur_apply: null pointer");
+  LG_CHECK_ARG(x != out, "lgblur_apply: in-place call");
+  LG_CHECK_ARG(rows > 0 && rows <= (1 << 20), "lgblur_apply: bad row count %d", rows);
+  LG_CHECK_ARG(S >= 8 && S % 8 == 0 && S <= 1024, "lgblur_apply: image side %d must be a multiple of 8, at least 8, at most 1024", S);
+  LG_CHECK_ARG((((uintptr_t)x | (uintptr_t)state | (uintptr_t)out) & 15) == 0, "lgblur_apply: images and state must be 16-byte aligned");
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dblur_apply_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -241,7 +241,7 @@ extern "C" int dblur_apply(const float* x, const float* state, float* out, int r
   const long long total = (long long)rows * ((S + DB_TW - 1) / DB_TW);   // strips
   const int blocks = (int)(total < 65536 ? total : 65536);
   hipLaunchKernelGGL(dblur_apply_kernel, dim3(blocks), dim3(DB_THREADS), DB_LDS_BYTES, (hipStream_t)stream, x, state, out, rows, S);
-  LG_CHECK_LAUNCH("dblur_apply");
+  LG_CHECK_LAUNCH("lgblur_apply");
   lg_note_kernel("dblur_apply_kernel");
   return LG_OK;
 }

@@ -1,8 +1,8 @@
 // Global-norm gradient clipping and the non-finite step guard (the reference has neither): one fp64 sum of squares over
 // the gradient range a network trains this step, finished into a 32-byte record on the device that the Adam pass of that network reads
-// (gg_clip_adam_*, loss_optim.hip).  A captured graph bakes launch scalars in; the scale, the skip flag and the counters come from the
+// (lgg_clip_adam_*, loss_optim.hip).  A captured graph bakes launch scalars in; the scale, the skip flag and the counters come from the
 // record, so a replayed step clips by the norm of ITS gradient.  The definition, the order of the additions and the record are stated in
-// include/gradguard.h and restated on the host by config.grad_guard_restate.
+// include/littlegan_guard.h and restated on the host by config.grad_guard_restate.
 #include "lg_internal.h"
 
 namespace {
@@ -80,32 +80,32 @@ long long chunks_of(long long n) { return (n + GG_CHUNK - 1) / GG_CHUNK; }
 
 }  // namespace
 
-extern "C" int gg_partials_count(long long n) {
+extern "C" int lgg_partials_count(long long n) {
   if (n < 1) return 0;
   const long long ck = chunks_of(n);
   return ck < GG_MAX_PARTIALS ? (int)ck : GG_MAX_PARTIALS;
 }
 
-extern "C" size_t gg_workspace_bytes(long long n) { return (size_t)gg_partials_count(n) * sizeof(double); }
+extern "C" size_t lgg_workspace_bytes(long long n) { return (size_t)lgg_partials_count(n) * sizeof(double); }
 
-extern "C" int gg_init(void* rec, int skipped0, int nonfinite0, void* stream) {
-  LG_CHECK_ARG(rec, "gg_init: null pointer");
-  LG_CHECK_ARG(((uintptr_t)rec & 15) == 0, "gg_init: rec must be 16-byte aligned");
-  LG_CHECK_ARG(skipped0 >= 0 && nonfinite0 >= 0, "gg_init: counter below 0 (skipped0=%d nonfinite0=%d)", skipped0, nonfinite0);
+extern "C" int lgg_init(void* rec, int skipped0, int nonfinite0, void* stream) {
+  LG_CHECK_ARG(rec, "lgg_init: null pointer");
+  LG_CHECK_ARG(((uintptr_t)rec & 15) == 0, "lgg_init: rec must be 16-byte aligned");
+  LG_CHECK_ARG(skipped0 >= 0 && nonfinite0 >= 0, "lgg_init: counter below 0 (skipped0=%d nonfinite0=%d)", skipped0, nonfinite0);
   hipLaunchKernelGGL(gg_init_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (float*)rec, skipped0, nonfinite0);
-  LG_CHECK_LAUNCH("gg_init");
+  LG_CHECK_LAUNCH("lgg_init");
   lg_note_kernel("gg_init_kernel");
   return LG_OK;
 }
 
-extern "C" int gg_sumsq_partial(const float* g, long long n, void* partial, size_t partial_bytes, void* stream) {
-  LG_CHECK_ARG(g && partial, "gg_sumsq_partial: null pointer");
-  LG_CHECK_ARG(n >= 1, "gg_sumsq_partial: n=%lld below 1", n);
+extern "C" int lgg_sumsq_partial(const float* g, long long n, void* partial, size_t partial_bytes, void* stream) {
+  LG_CHECK_ARG(g && partial, "lgg_sumsq_partial: null pointer");
+  LG_CHECK_ARG(n >= 1, "lgg_sumsq_partial: n=%lld below 1", n);
   LG_CHECK_ARG(((uintptr_t)g & 3) == 0 && ((uintptr_t)partial & 7) == 0,
-               "gg_sumsq_partial: g must be 4-byte, partial 8-byte aligned");
-  LG_CHECK_ARG(partial_bytes >= gg_workspace_bytes(n), "gg_sumsq_partial: partial_bytes=%zu below gg_workspace_bytes(%lld)=%zu",
-               partial_bytes, n, gg_workspace_bytes(n));
-  const int P = gg_partials_count(n);
+               "lgg_sumsq_partial: g must be 4-byte, partial 8-byte aligned");
+  LG_CHECK_ARG(partial_bytes >= lgg_workspace_bytes(n), "lgg_sumsq_partial: partial_bytes=%zu below lgg_workspace_bytes(%lld)=%zu",
+               partial_bytes, n, lgg_workspace_bytes(n));
+  const int P = lgg_partials_count(n);
   const bool vec = ((uintptr_t)g & 15) == 0;
   if (vec) {
     hipLaunchKernelGGL(gg_sumsq_partial_kernel<true>, dim3(P), dim3(GG_THREADS), 0, (hipStream_t)stream, g, n, chunks_of(n),
@@ -114,22 +114,22 @@ extern "C" int gg_sumsq_partial(const float* g, long long n, void* partial, size
     hipLaunchKernelGGL(gg_sumsq_partial_kernel<false>, dim3(P), dim3(GG_THREADS), 0, (hipStream_t)stream, g, n, chunks_of(n),
                        (double*)partial);
   }
-  LG_CHECK_LAUNCH("gg_sumsq_partial");
+  LG_CHECK_LAUNCH("lgg_sumsq_partial");
   lg_note_kernel(vec ? "gg_sumsq_partial_kernel<vec>" : "gg_sumsq_partial_kernel<scalar>");
   return LG_OK;
 }
 
-extern "C" int gg_finalise(const void* partial, long long n, void* rec, float gscale, float clip_norm, int skip, void* stream) {
-  LG_CHECK_ARG(partial && rec, "gg_finalise: null pointer");
-  LG_CHECK_ARG(n >= 1, "gg_finalise: n=%lld below 1", n);
-  LG_CHECK_ARG(((uintptr_t)partial & 7) == 0 && ((uintptr_t)rec & 15) == 0, "gg_finalise: partial must be 8-byte, rec 16-byte aligned");
-  LG_CHECK_ARG(gscale > 0.f && gscale <= 3.402823466e38f, "gg_finalise: gscale=%g must be finite and > 0", (double)gscale);
-  LG_CHECK_ARG(clip_norm >= 0.f && clip_norm <= 3.402823466e38f, "gg_finalise: clip_norm=%g must be finite and >= 0 (0 = off)",
+extern "C" int lgg_finalise(const void* partial, long long n, void* rec, float gscale, float clip_norm, int skip, void* stream) {
+  LG_CHECK_ARG(partial && rec, "lgg_finalise: null pointer");
+  LG_CHECK_ARG(n >= 1, "lgg_finalise: n=%lld below 1", n);
+  LG_CHECK_ARG(((uintptr_t)partial & 7) == 0 && ((uintptr_t)rec & 15) == 0, "lgg_finalise: partial must be 8-byte, rec 16-byte aligned");
+  LG_CHECK_ARG(gscale > 0.f && gscale <= 3.402823466e38f, "lgg_finalise: gscale=%g must be finite and > 0", (double)gscale);
+  LG_CHECK_ARG(clip_norm >= 0.f && clip_norm <= 3.402823466e38f, "lgg_finalise: clip_norm=%g must be finite and >= 0 (0 = off)",
                (double)clip_norm);
-  LG_CHECK_ARG(skip == 0 || skip == 1, "gg_finalise: skip=%d must be 0 or 1", skip);
+  LG_CHECK_ARG(skip == 0 || skip == 1, "lgg_finalise: skip=%d must be 0 or 1", skip);
   hipLaunchKernelGGL(gg_finalise_kernel, dim3(1), dim3(GG_THREADS), 0, (hipStream_t)stream, (const double*)partial,
-                     gg_partials_count(n), (float*)rec, gscale, clip_norm, skip);
-  LG_CHECK_LAUNCH("gg_finalise");
+                     lgg_partials_count(n), (float*)rec, gscale, clip_norm, skip);
+  LG_CHECK_LAUNCH("lgg_finalise");
   lg_note_kernel("gg_finalise_kernel");
   return LG_OK;
 }

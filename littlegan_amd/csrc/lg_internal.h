@@ -6,8 +6,8 @@
 // Convention of the *_try functions: LG_OK = launched, LG_ERR_UNSUPPORTED = the shape is not this kernel's, the caller takes the next one.
 #pragma once
 #include "lg_common.h"
-#include "../../include/gradguard.h"   // the gg_ group: public, bound from _lib.GG_SIGNATURES, declared outside littlegan_*.h
-#include "../../include/dblur.h"       // the dblur_ group: public, bound from _lib.DBLUR_SIGNATURES, in the same way
+#include "../../include/littlegan_guard.h"   // the lgg_ group: public; defined in gradguard.hip and loss_optim.hip
+#include "../../include/littlegan_blur.h"    // the lgblur_ group: public; defined in dblur.hip
 
 // Contraction forms of the implicit-GEMM convs (conv_igemm.hip, conv_halo.hip; chosen by capi.hip):
 //   DOWN : src [B,2Hm,2Wm,Cs] -> out [B,Hm,Wm,N]

@@ -195,7 +195,7 @@ __global__ __launch_bounds__(256) void clip_adam_ema_lrp_kernel(float* __restric
                      clip, gscale);
 }
 
-// ... with the gradient scale and the skip flag read from the guard's record (include/gradguard.h): rec[1] = eff where
+// ... with the gradient scale and the skip flag read from the guard's record (include/littlegan_guard.h): rec[1] = eff where
 // the launch scalar gscale stands above, the rate from device memory as in the _lrp twin; a skipped step returns before any access
 __global__ __launch_bounds__(256) void clip_adam_gg_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
                                                            float* __restrict__ v, long long n, const float* __restrict__ state,
@@ -364,49 +364,49 @@ extern "C" int lgsch_clip_adam_ema_update(float* w, const float* g, float* m, fl
   return LG_OK;
 }
 
-// lgsch_clip_adam_update with the scale and the skip flag in device memory (include/gradguard.h): the same grid, the same pass
-extern "C" int gg_clip_adam_update(float* w, const float* g, float* m, float* v, long long n, const float* adam_state, const float* lr,
+// lgsch_clip_adam_update with the scale and the skip flag in device memory (include/littlegan_guard.h): the same grid, the same pass
+extern "C" int lgg_clip_adam_update(float* w, const float* g, float* m, float* v, long long n, const float* adam_state, const float* lr,
                                    const void* rec, float b1, float b2, float eps, float clip, void* stream) {
-  LG_CHECK_ARG(w && g && m && v && adam_state && lr && rec, "gg_clip_adam_update: null pointer");
-  LG_CHECK_ARG(((uintptr_t)lr & 3) == 0 && ((uintptr_t)rec & 15) == 0, "gg_clip_adam_update: lr must be 4-byte, rec 16-byte aligned");
-  LG_CHECK_ARG(n > 0, "gg_clip_adam_update: n=%lld", n);
+  LG_CHECK_ARG(w && g && m && v && adam_state && lr && rec, "lgg_clip_adam_update: null pointer");
+  LG_CHECK_ARG(((uintptr_t)lr & 3) == 0 && ((uintptr_t)rec & 15) == 0, "lgg_clip_adam_update: lr must be 4-byte, rec 16-byte aligned");
+  LG_CHECK_ARG(n > 0, "lgg_clip_adam_update: n=%lld", n);
   long long nb = (n + 255) / 256;
   if (nb > 4096) nb = 4096;
   hipLaunchKernelGGL(clip_adam_gg_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, w, g, m, v, n, adam_state, lr,
                      (const float*)rec, b1, b2, eps, clip);
-  LG_CHECK_LAUNCH("gg_clip_adam_update");
+  LG_CHECK_LAUNCH("lgg_clip_adam_update");
   lg_note_kernel("clip_adam_gg_kernel");
   return LG_OK;
 }
 
 // lgsch_clip_adam_ema_update with the scale and the skip flag in device memory
-extern "C" int gg_clip_adam_ema_update(float* w, const float* g, float* m, float* v, float* ema, long long n, long long lo, long long hi,
+extern "C" int lgg_clip_adam_ema_update(float* w, const float* g, float* m, float* v, float* ema, long long n, long long lo, long long hi,
                                        const float* adam_state, const int* ema_state, const float* lr, const void* rec, float b1,
                                        float b2, float eps, float clip, float decay, void* stream) {
-  LG_CHECK_ARG(w && g && m && v && ema && adam_state && ema_state && lr && rec, "gg_clip_adam_ema_update: null pointer");
-  LG_CHECK_ARG(n > 0 && n % 4 == 0, "gg_clip_adam_ema_update: n=%lld must be a positive multiple of 4", n);
+  LG_CHECK_ARG(w && g && m && v && ema && adam_state && ema_state && lr && rec, "lgg_clip_adam_ema_update: null pointer");
+  LG_CHECK_ARG(n > 0 && n % 4 == 0, "lgg_clip_adam_ema_update: n=%lld must be a positive multiple of 4", n);
   LG_CHECK_ARG(lo >= 0 && lo <= hi && hi <= n && lo % 4 == 0 && hi % 4 == 0,
-               "gg_clip_adam_ema_update: need 0 <= lo <= hi <= n, both multiples of 4 (lo=%lld hi=%lld n=%lld)", lo, hi, n);
+               "lgg_clip_adam_ema_update: need 0 <= lo <= hi <= n, both multiples of 4 (lo=%lld hi=%lld n=%lld)", lo, hi, n);
   LG_CHECK_ARG(((uintptr_t)w | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema | (uintptr_t)rec) % 16 == 0 &&
                    ((uintptr_t)lr & 3) == 0,
-               "gg_clip_adam_ema_update: w, g, m, v, ema, rec must be 16-byte, lr 4-byte aligned");
-  LG_CHECK_ARG(decay >= 0.f && decay < 1.f, "gg_clip_adam_ema_update: decay=%g outside [0, 1)", (double)decay);
+               "lgg_clip_adam_ema_update: w, g, m, v, ema, rec must be 16-byte, lr 4-byte aligned");
+  LG_CHECK_ARG(decay >= 0.f && decay < 1.f, "lgg_clip_adam_ema_update: decay=%g outside [0, 1)", (double)decay);
   const long long n4 = n / 4;
   long long nb = (n4 + 255) / 256;
   if (nb > 4096) nb = 4096;
   hipLaunchKernelGGL(clip_adam_ema_gg_kernel, dim3((int)nb), dim3(256), 0, (hipStream_t)stream, w, g, m, v, ema, n4, lo / 4, hi / 4,
                      adam_state, ema_state, lr, (const float*)rec, b1, b2, eps, clip, decay);
-  LG_CHECK_LAUNCH("gg_clip_adam_ema_update");
+  LG_CHECK_LAUNCH("lgg_clip_adam_ema_update");
   lg_note_kernel("clip_adam_ema_gg_kernel");
   return LG_OK;
 }
 
 // lg_adam_advance unless the record says that this step is skipped
-extern "C" int gg_adam_advance(float* adam_state, const void* rec, float b1, float b2, void* stream) {
-  LG_CHECK_ARG(adam_state && rec, "gg_adam_advance: null pointer");
-  LG_CHECK_ARG(((uintptr_t)rec & 15) == 0, "gg_adam_advance: rec must be 16-byte aligned");
+extern "C" int lgg_adam_advance(float* adam_state, const void* rec, float b1, float b2, void* stream) {
+  LG_CHECK_ARG(adam_state && rec, "lgg_adam_advance: null pointer");
+  LG_CHECK_ARG(((uintptr_t)rec & 15) == 0, "lgg_adam_advance: rec must be 16-byte aligned");
   hipLaunchKernelGGL(adam_advance_gg_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, adam_state, (const float*)rec, b1, b2);
-  LG_CHECK_LAUNCH("gg_adam_advance");
+  LG_CHECK_LAUNCH("lgg_adam_advance");
   lg_note_kernel("adam_advance_gg_kernel");
   return LG_OK;
 }

@@ -162,7 +162,7 @@ class EagerTrainer:
         # step; None = the rates are constants.  No host mirror: nothing on the host depends on k
         self.lr_state = ops.sched_init(0, device=self.device) if self.lr_sched["device"] else None
         # global-norm clipping and the non-finite step guard (the reference has neither): None = off, no state and no
-        # launch of its own; else three 32-byte records {N, eff, skip_now, skipped, nonfinite, c, 0, 0} on the device (G, D, A; gg_init:
+        # launch of its own; else three 32-byte records {N, eff, skip_now, skipped, nonfinite, c, 0, 0} on the device (G, D, A; lgg_init:
         # written from launch scalars), one partials workspace sized for the largest network, and, without a schedule, the three base
         # rates on the device (filled once, here: the guarded Adam passes always read their rate through a pointer)
         self.guard = grad_guard_settings(getattr(args, "clip_norm", None), getattr(args, "skip_nonfinite", False))
@@ -177,7 +177,7 @@ class EagerTrainer:
             if self.lr_state is None:
                 self._guard_lr = torch.tensor([self.opt_cfg[m][0] for m in "GDA"], dtype=torch.float32, device=self.device)
         # blur of D's inputs (the reference has none): None = off, no state and no launch of its own; else {k, sigma, 0, 0}
-        # on the device (dblur_init: written from a launch scalar), advanced by dblur_step on every step whose restated radius is >= 1.
+        # on the device (lgblur_init: written from a launch scalar), advanced by lgblur_step on every step whose restated radius is >= 1.
         # _blur_k mirrors k on the host (every rank walks the same counter: no collective): it decides, before anything is enqueued,
         # whether a step blurs at all.  sigma never rises, so once the radius is 0 the step is the one without the key
         self.blur = blur_settings(getattr(args, "blur_init_sigma", 0.0), getattr(args, "blur_fade_kimg", 200))

@@ -927,12 +927,30 @@ def l1_tanh_loss(t, img, g_in, dpre, loss, lam, accumulate):
                                       float(lam), int(accumulate), _stream()), "lg_l1_tanh_loss_fwd_bwd")
 
 
-def clip_adam_update(w, g, m, v, state, lr, b1, b2, eps, clip, gscale=1.0):
-    n = w.numel()
-    for t, nm in ((w, "w"), (g, "g"), (m, "m"), (v, "v")):
+def _chk_counter(t, name):
+    if not (t.is_cuda and t.dtype == torch.int32 and t.numel() == 1):
+        raise ValueError(f"{name}: need a 1-element int32 CUDA tensor, got {t.dtype} {t.device} numel={t.numel()}")
+    return t
+
+
+def _chk_adam(who, state, *operands, ema_state=None):
+    """The operand check of the six Adam wrappers (plain, sched_, guard_, each with and without the weight average) -> n.  operands: w, g,
+    m, v and, for the passes that also update the average, ema (then ema_state is its counter).  state None: not checked, which is what
+    clip_adam_update and sched_clip_adam_update, the two on the default step, have always done (DESIGN.md §33 has the cost of checking)."""
+    n = operands[0].numel()
+    for t, nm in zip(operands, ("w", "g", "m", "v", "ema")):
         _chk(t, name=nm)
         if t.numel() != n:
-            raise ValueError("clip_adam_update: size mismatch")
+            raise ValueError(f"{who}: size mismatch")
+    if state is not None:
+        _chk(state, (2,), "state")
+    if len(operands) == 5:
+        _chk_counter(ema_state, "ema_state")
+    return n
+
+
+def clip_adam_update(w, g, m, v, state, lr, b1, b2, eps, clip, gscale=1.0):
+    n = _chk_adam("clip_adam_update", None, w, g, m, v)
     check(_lib.load().lg_clip_adam_update(_p(w), _p(g), _p(m), _p(v), n, _p(state), float(lr), float(b1), float(b2),
                                           float(eps), float(clip), float(gscale), _stream()), "lg_clip_adam_update")
 
@@ -941,22 +959,10 @@ def adam_advance(state, b1, b2):
     check(_lib.load().lg_adam_advance(_p(state), float(b1), float(b2), _stream()), "lg_adam_advance")
 
 
-def _chk_counter(t, name):
-    if not (t.is_cuda and t.dtype == torch.int32 and t.numel() == 1):
-        raise ValueError(f"{name}: need a 1-element int32 CUDA tensor, got {t.dtype} {t.device} numel={t.numel()}")
-    return t
-
-
 def clip_adam_ema_update(w, g, m, v, ema, lo, hi, state, ema_state, lr, b1, b2, eps, clip, gscale, decay):
     """clip + Adam on [lo, hi) of one model's weights `w` and the weight average `ema` over all of them (lo == hi: the average
     alone): ema -= (1 - d_t)(ema - w), d_t = min(decay, (1 + k) / (10 + k)), k = ema_state[0] (lg_clip_adam_ema_update)."""
-    n = w.numel()
-    for t, nm in ((w, "w"), (g, "g"), (m, "m"), (v, "v"), (ema, "ema")):
-        _chk(t, name=nm)
-        if t.numel() != n:
-            raise ValueError("clip_adam_ema_update: size mismatch")
-    _chk(state, (2,), "state")
-    _chk_counter(ema_state, "ema_state")
+    n = _chk_adam("clip_adam_ema_update", state, w, g, m, v, ema, ema_state=ema_state)
     check(_lib.load().lg_clip_adam_ema_update(_p(w), _p(g), _p(m), _p(v), _p(ema), n, int(lo), int(hi), _p(state), _p(ema_state),
                                               float(lr), float(b1), float(b2), float(eps), float(clip), float(gscale),
                                               float(decay), _stream()), "lg_clip_adam_ema_update")
@@ -1836,30 +1842,20 @@ def _chk_rate(lr):
 
 def sched_clip_adam_update(w, g, m, v, state, lr, b1, b2, eps, clip, gscale=1.0):
     """clip_adam_update with the rate read on the device: lr is a 1-element fp32 tensor (a view of the schedule's state)."""
-    n = w.numel()
-    for t, nm in ((w, "w"), (g, "g"), (m, "m"), (v, "v")):
-        _chk(t, name=nm)
-        if t.numel() != n:
-            raise ValueError("sched_clip_adam_update: size mismatch")
+    n = _chk_adam("sched_clip_adam_update", None, w, g, m, v)
     check(_lib.load().lgsch_clip_adam_update(_p(w), _p(g), _p(m), _p(v), n, _p(state), _p(_chk_rate(lr)), float(b1), float(b2),
                                              float(eps), float(clip), float(gscale), _stream()), "lgsch_clip_adam_update")
 
 
 def sched_clip_adam_ema_update(w, g, m, v, ema, lo, hi, state, ema_state, lr, b1, b2, eps, clip, gscale, decay):
     """clip_adam_ema_update with the rate read on the device: lr is a 1-element fp32 tensor (a view of the schedule's state)."""
-    n = w.numel()
-    for t, nm in ((w, "w"), (g, "g"), (m, "m"), (v, "v"), (ema, "ema")):
-        _chk(t, name=nm)
-        if t.numel() != n:
-            raise ValueError("sched_clip_adam_ema_update: size mismatch")
-    _chk(state, (2,), "state")
-    _chk_counter(ema_state, "ema_state")
+    n = _chk_adam("sched_clip_adam_ema_update", state, w, g, m, v, ema, ema_state=ema_state)
     check(_lib.load().lgsch_clip_adam_ema_update(_p(w), _p(g), _p(m), _p(v), _p(ema), n, int(lo), int(hi), _p(state), _p(ema_state),
                                                  _p(_chk_rate(lr)), float(b1), float(b2), float(eps), float(clip), float(gscale),
                                                  float(decay), _stream()), "lgsch_clip_adam_ema_update")
 
 
-# ------------------------------------------------------------------ global-norm gradient clipping and the non-finite step guard (gradguard.hip, loss_optim.hip, DESIGN.md §30; include/gradguard.h)
+# ------------------------------------------------------------------ global-norm gradient clipping and the non-finite step guard (gradguard.hip, loss_optim.hip, DESIGN.md §30; include/littlegan_guard.h)
 GUARD_CHUNK, GUARD_MAX_PARTIALS = 16384, 1024      # GG_CHUNK, GG_MAX_PARTIALS
 
 
@@ -1882,13 +1878,13 @@ def _chk_partial(p, who):
 
 
 def guard_partials_count(n):
-    """P(n) = min(1024, ceil(n / 16384)): the fp64 partials of a sum of squares over n elements (gg_partials_count)."""
-    return int(_lib.load().gg_partials_count(int(n)))
+    """P(n) = min(1024, ceil(n / 16384)): the fp64 partials of a sum of squares over n elements (lgg_partials_count)."""
+    return int(_lib.load().lgg_partials_count(int(n)))
 
 
 def guard_workspace_bytes(n):
-    """8 P(n): the bytes of those partials (gg_workspace_bytes)."""
-    return int(_lib.load().gg_workspace_bytes(int(n)))
+    """8 P(n): the bytes of those partials (lgg_workspace_bytes)."""
+    return int(_lib.load().lgg_workspace_bytes(int(n)))
 
 
 def guard_init(skipped=0, nonfinite=0, device="cuda", out=None):
@@ -1897,28 +1893,28 @@ def guard_init(skipped=0, nonfinite=0, device="cuda", out=None):
     if out is None:
         out = torch.empty(8, dtype=torch.float32, device=device)
     _chk_guard(out, "guard_init")
-    check(_lib.load().gg_init(_p(out), int(skipped), int(nonfinite), _stream()), "gg_init")
+    check(_lib.load().lgg_init(_p(out), int(skipped), int(nonfinite), _stream()), "lgg_init")
     return out
 
 
 def guard_sumsq_partial(g, partial):
-    """partial[:P(n)] (fp64) = the per-workgroup sums of squares of g, in the order include/gradguard.h states; partial holds at least
+    """partial[:P(n)] (fp64) = the per-workgroup sums of squares of g, in the order include/littlegan_guard.h states; partial holds at least
     guard_workspace_bytes(n) bytes."""
     _chk_grad(g, "guard_sumsq_partial")
     _chk_partial(partial, "guard_sumsq_partial")
-    check(_lib.load().gg_sumsq_partial(_p(g), g.numel(), _p(partial), partial.numel() * partial.element_size(), _stream()),
-          "gg_sumsq_partial")
+    check(_lib.load().lgg_sumsq_partial(_p(g), g.numel(), _p(partial), partial.numel() * partial.element_size(), _stream()),
+          "lgg_sumsq_partial")
     return partial
 
 
 def guard_finalise(partial, n, rec, gscale, clip_norm, skip):
     """The record of the n elements whose partials `partial` holds: S in index order, then N, c, eff, skip_now and the counters
-    (gg_finalise).  clip_norm 0 = no clipping."""
+    (lgg_finalise).  clip_norm 0 = no clipping."""
     _chk_partial(partial, "guard_finalise")
     _chk_guard(rec, "guard_finalise")
     if partial.numel() * partial.element_size() < guard_workspace_bytes(n):
         raise ValueError(f"guard_finalise: {partial.numel() * partial.element_size()} bytes of partials, n = {n} has {guard_workspace_bytes(n)}")
-    check(_lib.load().gg_finalise(_p(partial), int(n), _p(rec), float(gscale), float(clip_norm), int(bool(skip)), _stream()), "gg_finalise")
+    check(_lib.load().lgg_finalise(_p(partial), int(n), _p(rec), float(gscale), float(clip_norm), int(bool(skip)), _stream()), "lgg_finalise")
     return rec
 
 
@@ -1943,37 +1939,26 @@ def grad_sumsq(g):
 
 def guard_clip_adam_update(w, g, m, v, state, lr, rec, b1, b2, eps, clip):
     """sched_clip_adam_update with the gradient scale (rec word 1) and the skip flag (rec word 2) read on the device."""
-    n = w.numel()
-    for t, nm in ((w, "w"), (g, "g"), (m, "m"), (v, "v")):
-        _chk(t, name=nm)
-        if t.numel() != n:
-            raise ValueError("guard_clip_adam_update: size mismatch")
-    _chk(state, (2,), "state")
-    check(_lib.load().gg_clip_adam_update(_p(w), _p(g), _p(m), _p(v), n, _p(state), _p(_chk_rate(lr)), _p(_chk_guard(rec, "guard_clip_adam_update")),
-                                          float(b1), float(b2), float(eps), float(clip), _stream()), "gg_clip_adam_update")
+    n = _chk_adam("guard_clip_adam_update", state, w, g, m, v)
+    check(_lib.load().lgg_clip_adam_update(_p(w), _p(g), _p(m), _p(v), n, _p(state), _p(_chk_rate(lr)), _p(_chk_guard(rec, "guard_clip_adam_update")),
+                                          float(b1), float(b2), float(eps), float(clip), _stream()), "lgg_clip_adam_update")
 
 
 def guard_clip_adam_ema_update(w, g, m, v, ema, lo, hi, state, ema_state, lr, rec, b1, b2, eps, clip, decay):
     """sched_clip_adam_ema_update with the gradient scale and the skip flag read on the device; a skipped step takes the average alone."""
-    n = w.numel()
-    for t, nm in ((w, "w"), (g, "g"), (m, "m"), (v, "v"), (ema, "ema")):
-        _chk(t, name=nm)
-        if t.numel() != n:
-            raise ValueError("guard_clip_adam_ema_update: size mismatch")
-    _chk(state, (2,), "state")
-    _chk_counter(ema_state, "ema_state")
-    check(_lib.load().gg_clip_adam_ema_update(_p(w), _p(g), _p(m), _p(v), _p(ema), n, int(lo), int(hi), _p(state), _p(ema_state),
+    n = _chk_adam("guard_clip_adam_ema_update", state, w, g, m, v, ema, ema_state=ema_state)
+    check(_lib.load().lgg_clip_adam_ema_update(_p(w), _p(g), _p(m), _p(v), _p(ema), n, int(lo), int(hi), _p(state), _p(ema_state),
                                               _p(_chk_rate(lr)), _p(_chk_guard(rec, "guard_clip_adam_ema_update")), float(b1), float(b2),
-                                              float(eps), float(clip), float(decay), _stream()), "gg_clip_adam_ema_update")
+                                              float(eps), float(clip), float(decay), _stream()), "lgg_clip_adam_ema_update")
 
 
 def guard_adam_advance(state, rec, b1, b2):
     """adam_advance unless the record says that this step is skipped."""
     _chk(state, (2,), "state")
-    check(_lib.load().gg_adam_advance(_p(state), _p(_chk_guard(rec, "guard_adam_advance")), float(b1), float(b2), _stream()), "gg_adam_advance")
+    check(_lib.load().lgg_adam_advance(_p(state), _p(_chk_guard(rec, "guard_adam_advance")), float(b1), float(b2), _stream()), "lgg_adam_advance")
 
 
-# ------------------------------------------------------------------ faded blur of D's inputs (dblur.hip, DESIGN.md §31; include/dblur.h)
+# ------------------------------------------------------------------ faded blur of D's inputs (dblur.hip, DESIGN.md §31; include/littlegan_blur.h)
 def _chk_blur(t, who):
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (4,)):
         raise ValueError(f"{who}: the blur's state is a contiguous fp32 [4] CUDA tensor {{k, sigma, 0, 0}} (blur_init)")
@@ -1986,15 +1971,15 @@ def blur_init(k0=0, device="cuda", out=None):
     if out is None:
         out = torch.empty(4, dtype=torch.float32, device=device)
     _chk_blur(out, "blur_init")
-    check(_lib.load().dblur_init(_p(out), int(k0), _stream()), "dblur_init")
+    check(_lib.load().lgblur_init(_p(out), int(k0), _stream()), "lgblur_init")
     return out
 
 
 def blur_step(state, sigma0, images_per_step, fade_images):
     """One step of the fade: state[1] = sigma(k) = sigma0 * max(1 - k * images_per_step / fade_images, 0) (fp64, one conversion), then
-    k += 1 (saturating).  See include/dblur.h"""
+    k += 1 (saturating).  See include/littlegan_blur.h"""
     _chk_blur(state, "blur_step")
-    check(_lib.load().dblur_step(_p(state), float(sigma0), int(images_per_step), int(fade_images), _stream()), "dblur_step")
+    check(_lib.load().lgblur_step(_p(state), float(sigma0), int(images_per_step), int(fade_images), _stream()), "lgblur_step")
     return state
 
 
@@ -2011,10 +1996,10 @@ def blur_apply(x, state, out=None):
     _chk(x, name="image")
     rows, S, W, c = x.shape
     if W != S or c != 3:
-        raise ValueError(f"dblur_apply: square 3-channel NHWC images only, got {tuple(x.shape)}")
+        raise ValueError(f"lgblur_apply: square 3-channel NHWC images only, got {tuple(x.shape)}")
     _chk_blur(state, "blur_apply")
     if out is None:
         out = torch.empty_like(x)
     _chk(out, x.shape, "out")
-    check(_lib.load().dblur_apply(_p(x), _p(state), _p(out), rows, S, _stream()), "dblur_apply")
+    check(_lib.load().lgblur_apply(_p(x), _p(state), _p(out), rows, S, _stream()), "lgblur_apply")
     return out

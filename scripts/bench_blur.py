@@ -1,4 +1,4 @@
-"""Times the training step with the blur of D's inputs off and live (blur_init_sigma), and dblur_apply alone, and records
+"""Times the training step with the blur of D's inputs off and live (blur_init_sigma), and lgblur_apply alone, and records
 the result in profiles/blur_bench.json.  `python scripts/bench_blur.py [--workload c3|c2] [--pairs P] [--block K] [--out FILE]`:
 C3 = bf16, B = 256, G + D + Adjuster; C2 = exact f32, B = 64, G + D; synthetic data (bench.synthetic_inputs).
 
@@ -9,11 +9,11 @@ workload, each P pairs of alternating off / on blocks timed with HIP events:
   r3     off = the default step;  on = blur_init_sigma 1 (R = 3, 7 taps a pass)
   r30    off = the default step;  on = blur_init_sigma 10 (R = 30, 61 taps a pass: the largest filter there is)
 A fade moves sigma every step, and with it R; to time ONE radius the on side puts its counter back to 0 before every step (the host
-mirror, and the device state by one dblur_init launch: a tiny launch per step, as the key draw of bench_geom.py is), so every step runs
+mirror, and the device state by one lgblur_init launch: a tiny launch per step, as the key draw of bench_geom.py is), so every step runs
 at sigma = blur_init_sigma.
 Reported, not gated: every block's ms per step, the mean difference on - off, and the spread (max - min) of the off blocks — the
 yardstick a difference has to exceed to mean anything.
---apply times dblur_apply alone at 2B = 512 rows, S = 128 under sigma 0.2 / 1 / 4 / 10 (R = 0, 3, 12, 30) and, in the same process,
+--apply times lgblur_apply alone at 2B = 512 rows, S = 128 under sigma 0.2 / 1 / 4 / 10 (R = 0, 3, 12, 30) and, in the same process,
 lgeo_fwd on identity records — a plain copy of the same bytes — as the yardstick for how far each case is from a copy: HIP events around
 REPS back-to-back launches after a warm-up, ms per launch and achieved GB/s (the bytes the operator needs: the batch read once and
 written once).
@@ -115,7 +115,7 @@ def time_launches(fn, reps=REPS):
 
 
 def time_apply(rows=512, S=128):
-    """ms per launch and GB/s of dblur_apply per radius, and of lgeo_fwd on identity records (a plain copy), three rounds alternating"""
+    """ms per launch and GB/s of lgblur_apply per radius, and of lgeo_fwd on identity records (a plain copy), three rounds alternating"""
     from littlegan_amd import config, ops
     x = torch.rand(rows, S, S, 3, device="cuda") * 2 - 1
     out = torch.empty_like(x)
@@ -147,7 +147,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--block", type=int, default=30, help="steps per timed block (a multiple of 15 holds every step kind in proportion)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "blur_bench.json"))
-    ap.add_argument("--apply", action="store_true", help="time dblur_apply alone against a copy instead of whole steps")
+    ap.add_argument("--apply", action="store_true", help="time lgblur_apply alone against a copy instead of whole steps")
     ap.add_argument("--parent", default=None, help="JSON file with bench.py figures of the parent commit and of this tree (see the module docstring)")
     a = ap.parse_args()
     if a.pairs < 3:

@@ -1,5 +1,5 @@
 """Times the training step with the gradient guard on (clip_norm + skip_nonfinite; DESIGN.md §30: two more launches per trained network,
-gg_sumsq_partial and gg_finalise, one more read of the trained gradient bytes, and the Adam passes reading their scale, skip flag and
+lgg_sumsq_partial and lgg_finalise, one more read of the trained gradient bytes, and the Adam passes reading their scale, skip flag and
 rate from device memory) against the guard off, in ONE process, and writes profiles/grad_guard_bench.json.
 `python scripts/bench_grad_guard.py [--workload c3|c2] [--pairs P] [--block K] [--out FILE] [--defaults LABEL=FILE ...]`: C3 = bf16,
 B = 256, G + D + Adjuster; C2 = exact f32, B = 64, G + D; synthetic data (bench.synthetic_inputs).

@@ -14,7 +14,7 @@ import re
 import torch
 
 # What a name of the C ABI looks like, for every check that has to tell one from anything else (tests/test_abi.py, the recorder below):
-# `lg`, any number of lower-case letters, `_`.  The letters group names for the reader (`lgx_`, `lgeo_`, `lgadj_`, ...: one group per
+# `lg`, any number of lower-case letters, `_`.  The letters group names for the reader (`lgx_`, `lgeo_`, `lgadj_`, `lgg_`, `lgblur_`, ...: one group per
 # header); no check keys off them.
 ABI_NAME = r"lg[a-z]*_\w+"
 

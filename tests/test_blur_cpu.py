@@ -1,6 +1,5 @@
-"""The faded blur of D's inputs (blur_init_sigma, blur_fade_kimg) without a GPU: the header include/dblur.h against its
-own ctypes table (_lib.DBLUR_SIGNATURES) and the library's exports, which is what tests/test_abi.py does for include/littlegan_*.h; every
-host-side refusal of the three entry points; the configuration keys; the host restatement config.blur_restate; the numpy restatement of
+"""The faded blur of D's inputs (blur_init_sigma, blur_fade_kimg) without a GPU: the names of the header
+include/littlegan_blur.h; every host-side refusal of its three entry points; the configuration keys; the host restatement config.blur_restate; the numpy restatement of
 the operator (blur_np, which tests/test_blur_gpu.py holds the device to) and its symmetry; a trainer built without a device.
 
 The definition (this project's): k steps taken before this one, n real images D reads per step, F = round(blur_fade_kimg * 1000):
@@ -11,53 +10,20 @@ import ctypes as C
 import json
 import os
 import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_abi import ROOT, _ctype  # noqa: E402
+from guards import called  # noqa: E402
+from test_abi import ROOT, _protos  # noqa: E402
 from test_diffaug_cpu import _cpu_trainer  # noqa: E402
 
-HEADER = os.path.join(ROOT, "include", "dblur.h")
-NAME = r"dblur_\w+"
-ENTRY_POINTS = ("dblur_init", "dblur_step", "dblur_apply")
+BLUR_HEADER = os.path.join(ROOT, "include", "littlegan_blur.h")
+ENTRY_POINTS = ("lgblur_init", "lgblur_step", "lgblur_apply")
 F32, F64 = np.float32, np.float64
 SIGMAS = ((0.2, 0), (0.34, 1), (1.0, 3), (2.7, 8), (10.0, 30))   # (sigma, its R)
-
-
-def protos():
-    """name -> (return type, [parameter declarations]) of the prototypes of include/dblur.h (test_abi._protos for the dblur_ names)"""
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"(?:^|\n)\s*(const char\*|int|size_t)\s+(" + NAME + r")\s*\((.*?)\)\s*;", src, flags=re.S):
-        ret, name, args = m.group(1), m.group(2), " ".join(m.group(3).split())
-        assert name not in out, f"{name} is declared twice"
-        out[name] = (ret, [] if args in ("", "void") else [a.strip() for a in args.split(",")])
-    return out
-
-
-class BlurRecorder:
-    """What guards.called does for the `lg*_` names, for the dblur_ ones: wraps ops._lib.load so that the handle records every dblur_
-    name fetched from it, in order, in .names"""
-
-    def __init__(self, monkeypatch, ops):
-        self.names = names = []
-        real = ops._lib.load
-
-        class Handle:
-            def __init__(self, h):
-                object.__setattr__(self, "_h", h)
-
-            def __getattr__(self, name):
-                if re.fullmatch(NAME, name):
-                    names.append(name)
-                return getattr(self._h, name)
-
-        monkeypatch.setattr(ops._lib, "load", lambda *a, **k: Handle(real(*a, **k)))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -94,48 +60,20 @@ def lib():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the header include/dblur.h, its table and the library
-def test_header_is_bound_with_the_right_types(lib):
-    handle = lib.load()
-    ps = protos()
-    assert set(ps) == set(ENTRY_POINTS) == set(lib.DBLUR_SIGNATURES)
-    for name, (ret, plist) in ps.items():
-        res, args = lib.DBLUR_SIGNATURES[name]
-        assert len(args) == len(plist), f"{name}: ctypes table has {len(args)} params, header {len(plist)}"
-        for a, decl in zip(args, plist):
-            assert a is _ctype(decl), f"{name}: param '{decl}' bound as {a}"
-        assert res is C.c_int and ret == "int", name
-        fn = getattr(handle, name)
-        assert fn.argtypes == args and fn.restype is res, f"{name}: load() did not bind it"
+# the header include/littlegan_blur.h
+def test_blur_header_declares_the_entry_points(lib):
+    assert set(_protos(BLUR_HEADER)) == set(ENTRY_POINTS) == {n for n in lib.SIGNATURES if n.startswith("lgblur_")}
 
 
-def test_exported_dblur_symbols_are_the_declared_ones(lib):
-    nm = os.path.join("/opt/rocm/lib/llvm/bin", "llvm-nm")
-    nm = nm if os.path.exists(nm) else (shutil.which("llvm-nm") or shutil.which("nm"))
-    if not nm:
-        pytest.skip("nm not found")
-    lib.load()
-    out = subprocess.run([nm, "-D", "--defined-only", os.path.join(ROOT, "littlegan_amd", "liblittlegan_hip.so")],
-                         stdout=subprocess.PIPE, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if line.split() and re.fullmatch(NAME, line.split()[-1])}
-    assert exported == set(ENTRY_POINTS), exported ^ set(ENTRY_POINTS)
-
-
-def test_the_one_abi_table_is_unchanged(lib):
-    """the group is bound beside SIGNATURES, not in it; its header is outside the littlegan_*.h glob; the version stays 1"""
-    assert not [n for n in lib.SIGNATURES if n.startswith("dblur_")] and len(lib.SIGNATURES) == 144
-    assert not (set(lib.SIGNATURES) | set(lib.GG_SIGNATURES)) & set(lib.DBLUR_SIGNATURES)
+def test_the_sources_include_the_header_and_are_built(lib):
+    """the header reaches every source through lg_internal.h"""
     assert lib.load().lg_abi_version() == 1
-    assert not re.fullmatch(r"littlegan_.*\.h", os.path.basename(HEADER))
-    from guards import ABI_NAME
-    assert not [n for n in ENTRY_POINTS if re.fullmatch(ABI_NAME, n)]
     from littlegan_amd.csrc import build as B
     assert "dblur.hip" in B.SOURCES
     csrc = os.path.join(ROOT, "littlegan_amd", "csrc")
-    assert "dblur.h" in open(os.path.join(csrc, "lg_internal.h")).read()
-    assert "dblur.h" in open(os.path.join(csrc, "build.py")).read()
+    assert "littlegan_blur.h" in open(os.path.join(csrc, "lg_internal.h")).read()
     assert re.search(r'^#include "lg_internal\.h"', open(os.path.join(csrc, "dblur.hip")).read(), flags=re.M)
-    assert "#define DBLUR_MAX_RADIUS 30" in open(HEADER).read()
+    assert "#define DBLUR_MAX_RADIUS 30" in open(BLUR_HEADER).read()
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -146,28 +84,28 @@ def test_argument_validation_without_gpu(lib):
     nan, inf = float("nan"), float("inf")
     st, x, out = C.c_void_p(4096), C.c_void_p(1 << 20), C.c_void_p(2 << 20)
 
-    who = b"dblur_init"
-    assert h.dblur_init(None, 0, None) == -1 and b"null pointer" in err() and who in err()
+    who = b"lgblur_init"
+    assert h.lgblur_init(None, 0, None) == -1 and b"null pointer" in err() and who in err()
     for p in (4097, 4100, 4104):
-        assert h.dblur_init(C.c_void_p(p), 0, None) == -1 and b"aligned" in err() and who in err(), p
+        assert h.lgblur_init(C.c_void_p(p), 0, None) == -1 and b"aligned" in err() and who in err(), p
     for k0 in (-1, -(1 << 40), 1 << 31, 1 << 40):
-        assert h.dblur_init(st, k0, None) == -1 and b"k0" in err() and who in err(), k0
+        assert h.lgblur_init(st, k0, None) == -1 and b"k0" in err() and who in err(), k0
 
-    who = b"dblur_step"
-    assert h.dblur_step(None, 1.0, 64, 1000, None) == -1 and b"null pointer" in err() and who in err()
+    who = b"lgblur_step"
+    assert h.lgblur_step(None, 1.0, 64, 1000, None) == -1 and b"null pointer" in err() and who in err()
     for p in (4097, 4100, 4104):
-        assert h.dblur_step(C.c_void_p(p), 1.0, 64, 1000, None) == -1 and b"aligned" in err() and who in err(), p
+        assert h.lgblur_step(C.c_void_p(p), 1.0, 64, 1000, None) == -1 and b"aligned" in err() and who in err(), p
     for bad in (-1.0, -1e-30, nan, inf, -inf):
-        assert h.dblur_step(st, bad, 64, 1000, None) == -1 and b"sigma0" in err() and who in err(), bad
+        assert h.lgblur_step(st, bad, 64, 1000, None) == -1 and b"sigma0" in err() and who in err(), bad
     for bad in (0, -1, (1 << 31) + 1):
-        assert h.dblur_step(st, 1.0, bad, 1000, None) == -1 and b"images_per_step" in err() and who in err(), bad
+        assert h.lgblur_step(st, 1.0, bad, 1000, None) == -1 and b"images_per_step" in err() and who in err(), bad
     for bad in (0, -5, (1 << 40) + 1):
-        assert h.dblur_step(st, 1.0, 64, bad, None) == -1 and b"fade_images" in err() and who in err(), bad
+        assert h.lgblur_step(st, 1.0, 64, bad, None) == -1 and b"fade_images" in err() and who in err(), bad
 
-    who = b"dblur_apply"
+    who = b"lgblur_apply"
 
     def apply(x=x, st=st, out=out, rows=2, S=16):
-        return h.dblur_apply(x, st, out, rows, S, None)
+        return h.lgblur_apply(x, st, out, rows, S, None)
 
     for kw in (dict(x=None), dict(st=None), dict(out=None)):
         assert apply(**kw) == -1 and b"null pointer" in err() and who in err(), kw
@@ -278,7 +216,8 @@ def test_the_restated_operator_is_symmetric():
 # a trainer without a device
 def test_the_default_path_knows_nothing_of_the_blur(monkeypatch):
     from littlegan_amd import ops
-    rec = BlurRecorder(monkeypatch, ops)
+    names = called(monkeypatch, ops)
+    blur_names = lambda: [n for n in names if n.startswith("lgblur_")]   # noqa: E731
     base, _ = _cpu_trainer()
     assert base.blur is None and base.blur_sigma_now() is None and not base.blur_live() and not base.blur_live(0)
     assert not hasattr(base, "blur_state") and not hasattr(base, "_blur_k")
@@ -287,13 +226,13 @@ def test_the_default_path_knows_nothing_of_the_blur(monkeypatch):
     assert off.blur is None and not hasattr(off, "blur_state") and "blur_state" not in off.checkpoint_state()
     assert [off.step_kind(b) for b in range(40)] == [base.step_kind(b) for b in range(40)]
     assert base.step_kind(11) == (-1, True, False)
-    assert not rec.names, rec.names
+    assert not blur_names(), names
     for kw, what in ((dict(use_gp=True), "use_gp"), (dict(dropout_train=True), "dropout_train"), (dict(image_channel=1), "3-channel")):
         with pytest.raises(ValueError, match=what):
             _cpu_trainer(blur_init_sigma=2.0, **kw)
     # the blurring path owns a state on the device: without one its construction reaches the wrapper and goes no further
     with pytest.raises(ValueError, match="blur's state"):
         _cpu_trainer(blur_init_sigma=2.0)
-    assert not rec.names      # refused before the library was asked
-    ops._lib.load().dblur_init(None, 0, None)
-    assert rec.names == ["dblur_init"]      # the recorder does record
+    assert not blur_names()      # refused before the library was asked
+    ops._lib.load().lgblur_init(None, 0, None)
+    assert blur_names() == ["lgblur_init"]      # the recorder does record

@@ -1,13 +1,13 @@
 """The faded blur of D's inputs (blur_init_sigma, blur_fade_kimg) on the GPU.
 
-Kernels: dblur_apply against blur_np of tests/test_blur_cpu.py (the fp32 taps of config.blur_taps, float64 sums) within
+Kernels: lgblur_apply against blur_np of tests/test_blur_cpu.py (the fp32 taps of config.blur_taps, float64 sums) within
 8 (R + 2) 2^-24 max|x| — two passes of 2R + 1 terms whose weights sum to at most 1, one rounding per product and per add, plus the
 rounding of the device's own taps, with a factor of two over it — at (rows, S) = (1, 8), (3, 16), (2, 24), (2, 40), (1, 136) and
 sigma = 0.2, 0.34, 1, 2.7, 10 (R = 0, 1, 3, 8, 30; S = 8 under R = 30 puts most taps outside the image; 24 and 40 are no multiple of the
 32-pixel tile, 40 and 136 take more than one tile a side), and once at (1, 1024); R = 0 bit for bit; the impulse response bit-symmetric
 and within 4 ulp of the product of the restated taps; <Blur x, g> = <x, Blur g> on the device's own outputs within the same bound; row
-slices and repeated calls bit for bit; dblur_step against config.blur_restate bit for bit; unusable sigmas; every pointer-taking call
-inside guard bands.
+slices and repeated calls bit for bit; lgblur_step against config.blur_restate bit for bit; unusable sigmas.  (Every pointer-taking call
+inside guard bands: the blur-* rows of tests/test_memory_contract_gpu.py, on this module's data.)
 Whole steps at SMALL of tests/test_diffaug_gpu.py (S = 32, B = 3), batch_no 1 and 12, with the blur alone and on top of geom_augment +
 diff_augment: against oracle.np_oracle whose discriminator reads the restated Blur (then Geo, then T) and whose backward blurs the
 image gradient, at the tolerances of tests/test_geom_gpu.py; the key off; the fade-out; eager against graph replay across the fade;
@@ -21,8 +21,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from oracle import np_oracle as O  # noqa: E402
-from guards import Guarded, describe  # noqa: E402
-from test_blur_cpu import SIGMAS, BlurRecorder, blur_np  # noqa: E402
+from guards import called  # noqa: E402
+from test_blur_cpu import SIGMAS, blur_np  # noqa: E402
 from test_diffaug_cpu import diffaug_adjoint_np, diffaug_np  # noqa: E402
 from test_diffaug_gpu import FULL as DIFF_FULL, SMALL, _same_state, dev, dev_key  # noqa: E402
 from test_geom_cpu import FULL as GEOM_FULL, geom_adjoint_np, geom_np, key_of  # noqa: E402
@@ -63,6 +63,11 @@ def images(rows, S, seed=0):
     if (rows, S, seed) not in _X:
         _X[(rows, S, seed)] = np.random.default_rng(1000 * S + rows + seed).uniform(-1, 1, (rows, S, S, 3)).astype(F32)
     return _X[(rows, S, seed)]
+
+
+def blur_names(fetched):
+    """the lgblur_ names among the ABI names guards.called recorded, in order"""
+    return [n for n in fetched if n.startswith("lgblur_")]
 
 
 def bits(t):
@@ -183,35 +188,6 @@ def test_state_follows_the_restatement_and_unusable_sigmas_copy(ops):
         ops.blur_apply(x, state, out=x)
     with pytest.raises(LittleGanHipError, match="image side"):
         ops.blur_apply(torch.zeros(1, 12, 12, 3, device="cuda"), state)
-
-
-@pytest.mark.parametrize("S", [8, 40])
-def test_memory_contract_under_guard_bands(ops, S):
-    """Every pointer-taking dblur_* call on buffers inside guard bands, zone bytes 0xFF / 0x00 / 0x3F, the same arbitrary state bits
-    (k and the reserved words hold junk, sigma = 10: R = 30): no red-zone byte changes and the result does not depend on the zone."""
-    x = torch.tensor(images(2, S))
-    words = torch.tensor(state_words(10.0, 0x12345678, 0x7FC00001, -7), dtype=torch.int32)
-    outs, steps = [], []
-    for zone in (0xFF, 0x00, 0x3F):
-        gx = Guarded(x.shape, torch.float32, "cuda", fill=x.cuda(), zone=zone)
-        gs = Guarded((4,), torch.float32, "cuda", fill=words.cuda().view(torch.float32), zone=zone)
-        go = Guarded(x.shape, torch.float32, "cuda", fill=zone, zone=zone)
-        ops.blur_apply(gx.t, gs.t, out=go.t)
-        torch.cuda.synchronize()
-        for what, g in (("x", gx), ("state", gs), ("out", go)):
-            bad = g.intact()
-            assert not bad, f"dblur_apply S={S} zone {zone:#x}: {what}: {describe(bad)}"
-        assert torch.equal(gx.t.cpu(), x) and torch.equal(gs.t.view(torch.int32).cpu(), words)      # read, never written
-        outs.append(go.t.clone())
-        g2 = Guarded((4,), torch.float32, "cuda", fill=zone, zone=zone)
-        ops.blur_init(5, out=g2.t)
-        ops.blur_step(g2.t, 10.0, 3, 100)
-        torch.cuda.synchronize()
-        assert not g2.intact(), f"dblur_init / dblur_step zone {zone:#x}: {describe(g2.intact())}"
-        steps.append(g2.t.view(torch.int32).cpu().tolist())
-    assert torch.equal(bits(outs[0]), bits(outs[1])) and torch.equal(bits(outs[0]), bits(outs[2]))
-    assert steps[0] == steps[1] == steps[2] and steps[0][0] == 6 and steps[0][2:] == [0, 0]
-    assert np.abs(outs[0].cpu().numpy().astype(F64) - blur_np(x.numpy(), 10.0)).max() <= bound(30, 1.0)
 
 
 # ---------------------------------------------------------------------------------------------------------------------- whole steps
@@ -338,11 +314,11 @@ def ops_read_sigma(tr):
 
 
 def test_key_off_is_the_step_without_the_key(ops, monkeypatch):
-    """blur_init_sigma 0: bit-identical to a trainer built without the key, and no dblur_ function is fetched from the library"""
+    """blur_init_sigma 0: bit-identical to a trainer built without the key, and no lgblur_ function is fetched from the library"""
     cfg = O.Cfg(**SMALL)
     W = perturbed(cfg, 1)
     inp = dev_inputs(f32_round(O.make_inputs(cfg, cfg.batch_size, seed=5)))
-    rec = BlurRecorder(monkeypatch, ops)
+    fetched = called(monkeypatch, ops)
     off, never = build_blur(cfg, W, "f32", sigma0=0.0), build(cfg, W, "f32")
     assert not hasattr(make_args(cfg, "f32"), "blur_init_sigma") and off.blur is None and not hasattr(off, "blur_state")
     for b in (1, 12):
@@ -350,11 +326,12 @@ def test_key_off_is_the_step_without_the_key(ops, monkeypatch):
         ra, rb = off.train_step_from_inputs(b, inp), never.train_step_from_inputs(b, inp)
         torch.cuda.synchronize()
         assert all((u is None and v is None) or torch.equal(u, v) for u, v in zip(ra, rb)) and _same_state(off, never), b
-    assert not rec.names, rec.names
+    assert not blur_names(fetched), fetched
     build_blur(cfg, W, "f32").train_step_from_inputs(12, inp)
     torch.cuda.synchronize()
-    assert rec.names[:2] == ["dblur_init", "dblur_step"] and rec.names.count("dblur_step") == 1
-    assert rec.names.count("dblur_apply") == 4      # D's two inputs and the two image gradients
+    names = blur_names(fetched)
+    assert names[:2] == ["lgblur_init", "lgblur_step"] and names.count("lgblur_step") == 1
+    assert names.count("lgblur_apply") == 4      # D's two inputs and the two image gradients
 
 
 def copy_training_state(dst, src):
@@ -367,7 +344,7 @@ def copy_training_state(dst, src):
 
 
 def test_fade_out_is_the_step_without_the_key(ops, monkeypatch):
-    """F = 3 n: k = 0, 1, 2 blur (sigma 2, 4/3, 2/3), k = 3 has sigma 0.  From there on no dblur_ name is fetched, the steps are those of
+    """F = 3 n: k = 0, 1, 2 blur (sigma 2, 4/3, 2/3), k = 3 has sigma 0.  From there on no lgblur_ name is fetched, the steps are those of
     a trainer without the key started from the same weights and Adam state, bit for bit, and D hands its maps to the Adjuster again."""
     from littlegan_amd import config
     cfg = O.Cfg(**SMALL)
@@ -388,13 +365,13 @@ def test_fade_out_is_the_step_without_the_key(ops, monkeypatch):
     never = build(cfg, W, "bf16")
     copy_training_state(never, tr)
     del kept[:]
-    rec = BlurRecorder(monkeypatch, ops)
+    fetched = called(monkeypatch, ops)
     for b in (13, 14, 6):
         assert tr.step_kind(b) == never.step_kind(b) + (False,)
         ra, rb = tr.train_step_from_inputs(b, data(b)), never.train_step_from_inputs(b, data(b))
         torch.cuda.synchronize()
         assert all((u is None and v is None) or torch.equal(u, v) for u, v in zip(ra, rb)) and _same_state(tr, never), b
-    assert not rec.names, rec.names
+    assert not blur_names(fetched), fetched
     assert kept == [True, False, True, False, False]      # 13, 14: D keeps the maps of `fake` for the Adjuster; D on the Adjuster's output; 6
     assert tr._blur_k == 6 and ops.blur_read(tr.blur_state)[0] == 3      # the host mirror walks on; the device state rests
     assert tr.checkpoint_state()["blur_state"] == 6

@@ -1,6 +1,5 @@
 """Global-norm gradient clipping and the non-finite step guard (clip_norm, skip_nonfinite) without a GPU: the configuration
-keys; the header include/gradguard.h against its own ctypes table (_lib.GG_SIGNATURES) and the library's exports, which is what
-tests/test_abi.py does for include/littlegan_*.h; every host-side refusal of the eight entry points; gg_partials_count; the host
+keys; the names of the header include/littlegan_guard.h; every host-side refusal of its eight entry points; lgg_partials_count; the host
 restatement config.grad_guard_restate that tests/test_grad_guard_gpu.py holds the device to; and a trainer built without a device, whose
 default path knows nothing of the guard.
 
@@ -11,54 +10,21 @@ import ctypes as C
 import json
 import os
 import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_abi import ROOT, _ctype  # noqa: E402
+from guards import called  # noqa: E402
+from test_abi import ROOT, _protos  # noqa: E402
 from test_diffaug_cpu import _cpu_trainer  # noqa: E402
 
-GG_HEADER = os.path.join(ROOT, "include", "gradguard.h")
-GG_NAME = r"gg_\w+"
-ENTRY_POINTS = ("gg_partials_count", "gg_workspace_bytes", "gg_init", "gg_sumsq_partial", "gg_finalise", "gg_clip_adam_update",
-                "gg_clip_adam_ema_update", "gg_adam_advance")
+GUARD_HEADER = os.path.join(ROOT, "include", "littlegan_guard.h")
+ENTRY_POINTS = ("lgg_partials_count", "lgg_workspace_bytes", "lgg_init", "lgg_sumsq_partial", "lgg_finalise", "lgg_clip_adam_update",
+                "lgg_clip_adam_ema_update", "lgg_adam_advance")
 CH, PMAX = 16384, 1024
 F32 = np.float32
-
-
-def gg_protos():
-    """name -> (return type, [parameter declarations]) of the prototypes of include/gradguard.h (test_abi._protos for the gg_ names)"""
-    src = re.sub(r"/\*.*?\*/", "", open(GG_HEADER).read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"(?:^|\n)\s*(const char\*|int|size_t)\s+(" + GG_NAME + r")\s*\((.*?)\)\s*;", src, flags=re.S):
-        ret, name, args = m.group(1), m.group(2), " ".join(m.group(3).split())
-        assert name not in out, f"{name} is declared twice"
-        out[name] = (ret, [] if args in ("", "void") else [a.strip() for a in args.split(",")])
-    return out
-
-
-class GgRecorder:
-    """What guards.called does for the `lg*_` names, for the gg_ ones: wraps ops._lib.load so that the handle records every gg_ name
-    fetched from it, in order, in .names"""
-
-    def __init__(self, monkeypatch, ops):
-        self.names = names = []
-        real = ops._lib.load
-
-        class Handle:
-            def __init__(self, h):
-                object.__setattr__(self, "_h", h)
-
-            def __getattr__(self, name):
-                if re.fullmatch(GG_NAME, name):
-                    names.append(name)
-                return getattr(self._h, name)
-
-        monkeypatch.setattr(ops._lib, "load", lambda *a, **k: Handle(real(*a, **k)))
 
 
 @pytest.fixture(scope="module")
@@ -70,43 +36,18 @@ def lib():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the header include/gradguard.h, its table and the library
-def test_header_is_bound_with_the_right_types(lib):
-    handle = lib.load()
-    protos = gg_protos()
-    assert set(protos) == set(ENTRY_POINTS) == set(lib.GG_SIGNATURES)
-    for name, (ret, plist) in protos.items():
-        res, args = lib.GG_SIGNATURES[name]
-        assert len(args) == len(plist), f"{name}: ctypes table has {len(args)} params, header {len(plist)}"
-        for a, decl in zip(args, plist):
-            assert a is _ctype(decl), f"{name}: param '{decl}' bound as {a}"
-        assert res is {"int": C.c_int, "size_t": C.c_size_t}[ret], f"{name}: returns {ret}, bound as {res}"
-        fn = getattr(handle, name)
-        assert fn.argtypes == args and fn.restype is res, f"{name}: load() did not bind it"
+# the header include/littlegan_guard.h
+def test_guard_header_declares_the_entry_points(lib):
+    assert set(_protos(GUARD_HEADER)) == set(ENTRY_POINTS) == {n for n in lib.SIGNATURES if n.startswith("lgg_")}
 
 
-def test_exported_gg_symbols_are_the_declared_ones(lib):
-    nm = os.path.join("/opt/rocm/lib/llvm/bin", "llvm-nm")
-    nm = nm if os.path.exists(nm) else (shutil.which("llvm-nm") or shutil.which("nm"))
-    if not nm:
-        pytest.skip("nm not found")
-    lib.load()
-    out = subprocess.run([nm, "-D", "--defined-only", os.path.join(ROOT, "littlegan_amd", "liblittlegan_hip.so")],
-                         stdout=subprocess.PIPE, text=True, check=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if line.split() and re.fullmatch(GG_NAME, line.split()[-1])}
-    assert exported == set(ENTRY_POINTS), exported ^ set(ENTRY_POINTS)
-
-
-def test_the_one_abi_table_is_unchanged(lib):
-    """the group is bound beside SIGNATURES, not in it; its header is outside the littlegan_*.h glob; the version stays 1"""
-    assert not [n for n in lib.SIGNATURES if n.startswith("gg_")] and len(lib.SIGNATURES) == 144
-    assert not set(lib.SIGNATURES) & set(lib.GG_SIGNATURES)
+def test_the_sources_include_the_header_and_are_built(lib):
+    """the header reaches every source through lg_internal.h; the guarded Adam kernels call the one pass, which calls the one element"""
     assert lib.load().lg_abi_version() == 1
-    assert not re.fullmatch(r"littlegan_.*\.h", os.path.basename(GG_HEADER))
     from littlegan_amd.csrc import build as B
     assert "gradguard.hip" in B.SOURCES
     csrc = os.path.join(ROOT, "littlegan_amd", "csrc")
-    assert "gradguard.h" in open(os.path.join(csrc, "lg_internal.h")).read()
+    assert "littlegan_guard.h" in open(os.path.join(csrc, "lg_internal.h")).read()
     assert re.search(r'^#include "lg_internal\.h"', open(os.path.join(csrc, "gradguard.hip")).read(), flags=re.M)
     lo = open(os.path.join(csrc, "loss_optim.hip")).read()
     assert len(re.findall(r"\bfloat clip_adam_element\(", lo)) == 1 and len(re.findall(r"sqrtf\(vv\) \+ eps", lo)) == 1
@@ -122,17 +63,17 @@ def test_argument_validation_without_gpu(lib):
     nan, inf = float("nan"), float("inf")
     rec, part, g = C.c_void_p(4096), C.c_void_p(8192), C.c_void_p(16384)
 
-    who = b"gg_init"
-    assert h.gg_init(None, 0, 0, None) == -1 and b"null pointer" in err() and who in err()
+    who = b"lgg_init"
+    assert h.lgg_init(None, 0, 0, None) == -1 and b"null pointer" in err() and who in err()
     for p in (4097, 4100, 4104):
-        assert h.gg_init(C.c_void_p(p), 0, 0, None) == -1 and b"aligned" in err() and who in err(), p
+        assert h.lgg_init(C.c_void_p(p), 0, 0, None) == -1 and b"aligned" in err() and who in err(), p
     for a, b in ((-1, 0), (0, -1), (-(1 << 31), 0)):
-        assert h.gg_init(rec, a, b, None) == -1 and b"below 0" in err() and who in err(), (a, b)
+        assert h.lgg_init(rec, a, b, None) == -1 and b"below 0" in err() and who in err(), (a, b)
 
-    who = b"gg_sumsq_partial"
+    who = b"lgg_sumsq_partial"
 
     def partial(g=g, n=5, part=part, nbytes=None):
-        return h.gg_sumsq_partial(g, n, part, h.gg_workspace_bytes(n) if nbytes is None else nbytes, None)
+        return h.lgg_sumsq_partial(g, n, part, h.lgg_workspace_bytes(n) if nbytes is None else nbytes, None)
 
     for kw in (dict(g=None), dict(part=None)):
         assert partial(**kw) == -1 and b"null pointer" in err() and who in err(), kw
@@ -143,14 +84,14 @@ def test_argument_validation_without_gpu(lib):
     for p in (8193, 8194, 8196):
         assert partial(part=C.c_void_p(p)) == -1 and b"aligned" in err() and who in err(), p
     for n in (1, CH, CH + 1, 5 * CH, 1024 * CH + 5):
-        need = h.gg_workspace_bytes(n)
+        need = h.lgg_workspace_bytes(n)
         for nb in (0, need - 8, need - 1):
             assert partial(n=n, nbytes=nb) == -1 and b"partial_bytes" in err() and who in err(), (n, nb)
 
-    who = b"gg_finalise"
+    who = b"lgg_finalise"
 
     def final(part=part, n=5, rec=rec, gscale=1.0, clip=1.0, skip=1):
-        return h.gg_finalise(part, n, rec, gscale, clip, skip, None)
+        return h.lgg_finalise(part, n, rec, gscale, clip, skip, None)
 
     for kw in (dict(part=None), dict(rec=None)):
         assert final(**kw) == -1 and b"null pointer" in err() and who in err(), kw
@@ -167,12 +108,12 @@ def test_argument_validation_without_gpu(lib):
     for bad in (-1, 2, 1 << 20):
         assert final(skip=bad) == -1 and b"skip" in err() and who in err(), bad
 
-    who = b"gg_clip_adam_update"
+    who = b"lgg_clip_adam_update"
     w, gr, m, v, s, lr = (C.c_void_p(1024 * (i + 1)) for i in range(6))
     rc = C.c_void_p(7168)
 
     def plain(w=w, g=gr, m=m, v=v, s=s, lr=lr, rec=rc, n=8):
-        return h.gg_clip_adam_update(w, g, m, v, n, s, lr, rec, 0.5, 0.9, 1e-8, 0.5, None)
+        return h.lgg_clip_adam_update(w, g, m, v, n, s, lr, rec, 0.5, 0.9, 1e-8, 0.5, None)
 
     for kw in (dict(w=None), dict(g=None), dict(m=None), dict(v=None), dict(s=None), dict(lr=None), dict(rec=None)):
         assert plain(**kw) == -1 and b"null pointer" in err() and who in err(), kw
@@ -183,11 +124,11 @@ def test_argument_validation_without_gpu(lib):
     for n in (0, -1, -(1 << 40)):
         assert plain(n=n) == -1 and b"n=" in err() and who in err(), n
 
-    who = b"gg_clip_adam_ema_update"
+    who = b"lgg_clip_adam_ema_update"
     ema, es = C.c_void_p(9216), C.c_void_p(10240)
 
     def fused(w=w, g=gr, m=m, v=v, ema=ema, s=s, es=es, lr=lr, rec=rc, n=16, lo=4, hi=12, decay=0.99):
-        return h.gg_clip_adam_ema_update(w, g, m, v, ema, n, lo, hi, s, es, lr, rec, 0.5, 0.9, 1e-8, 0.5, decay, None)
+        return h.lgg_clip_adam_ema_update(w, g, m, v, ema, n, lo, hi, s, es, lr, rec, 0.5, 0.9, 1e-8, 0.5, decay, None)
 
     for kw in (dict(w=None), dict(g=None), dict(m=None), dict(v=None), dict(ema=None), dict(s=None), dict(es=None), dict(lr=None),
                dict(rec=None)):
@@ -204,27 +145,27 @@ def test_argument_validation_without_gpu(lib):
     for d in (-0.1, 1.0, 1.5, nan):
         assert fused(decay=d) == -1 and b"decay" in err() and who in err(), d
 
-    who = b"gg_adam_advance"
-    assert h.gg_adam_advance(None, rc, 0.5, 0.9, None) == -1 and b"null pointer" in err() and who in err()
-    assert h.gg_adam_advance(s, None, 0.5, 0.9, None) == -1 and b"null pointer" in err() and who in err()
+    who = b"lgg_adam_advance"
+    assert h.lgg_adam_advance(None, rc, 0.5, 0.9, None) == -1 and b"null pointer" in err() and who in err()
+    assert h.lgg_adam_advance(s, None, 0.5, 0.9, None) == -1 and b"null pointer" in err() and who in err()
     for p in (7169, 7172, 7176):
-        assert h.gg_adam_advance(s, C.c_void_p(p), 0.5, 0.9, None) == -1 and b"aligned" in err() and who in err(), p
+        assert h.lgg_adam_advance(s, C.c_void_p(p), 0.5, 0.9, None) == -1 and b"aligned" in err() and who in err(), p
 
 
 def test_partials_count(lib):
     h = lib.load()
     ns = [1, 2, 255, CH - 1, CH, CH + 1, 2 * CH, 2 * CH + 7, 100 * CH, 1023 * CH, 1023 * CH + 1, 1024 * CH, 1024 * CH + 5, 5000 * CH,
           (1 << 40) + 3]
-    got = [h.gg_partials_count(n) for n in ns]
+    got = [h.lgg_partials_count(n) for n in ns]
     assert got == [min(PMAX, -(-n // CH)) for n in ns]                       # a pure function of n
     assert got == sorted(got) and max(got) == PMAX and got[-3:] == [PMAX] * 3  # monotone, capped at 1024
-    assert all(h.gg_partials_count(n) == 1 for n in (1, 7, CH - 1, CH)) and h.gg_partials_count(CH + 1) == 2
-    assert [h.gg_partials_count(n) for n in ns] == got                       # equal on repeated calls
-    assert [h.gg_workspace_bytes(n) for n in ns] == [8 * p for p in got]
-    assert h.gg_partials_count(0) == 0 and h.gg_partials_count(-5) == 0 and h.gg_workspace_bytes(0) == 0
+    assert all(h.lgg_partials_count(n) == 1 for n in (1, 7, CH - 1, CH)) and h.lgg_partials_count(CH + 1) == 2
+    assert [h.lgg_partials_count(n) for n in ns] == got                       # equal on repeated calls
+    assert [h.lgg_workspace_bytes(n) for n in ns] == [8 * p for p in got]
+    assert h.lgg_partials_count(0) == 0 and h.lgg_partials_count(-5) == 0 and h.lgg_workspace_bytes(0) == 0
     from littlegan_amd import ops
     assert (ops.GUARD_CHUNK, ops.GUARD_MAX_PARTIALS) == (CH, PMAX)
-    hdr = open(GG_HEADER).read()
+    hdr = open(GUARD_HEADER).read()
     assert f"#define GG_CHUNK {CH}" in hdr and f"#define GG_MAX_PARTIALS {PMAX}" in hdr
 
 
@@ -308,7 +249,8 @@ def test_host_restatement():
 # a trainer without a device
 def test_the_default_path_knows_nothing_of_the_guard(monkeypatch):
     from littlegan_amd import ops
-    rec = GgRecorder(monkeypatch, ops)
+    names = called(monkeypatch, ops)
+    guard_names = lambda: [n for n in names if n.startswith("lgg_")]   # noqa: E731
     base, _ = _cpu_trainer()
     assert base.guard is None and base.grad_norm_now() is None and base.guard_counts() is None
     assert not hasattr(base, "guard_state") and not hasattr(base, "_guard_ws") and not hasattr(base, "_guard_lr")
@@ -316,12 +258,12 @@ def test_the_default_path_knows_nothing_of_the_guard(monkeypatch):
     off, _ = _cpu_trainer(clip_norm=None, skip_nonfinite=False)
     assert off.guard is None and not hasattr(off, "guard_state")
     assert [off.step_kind(b) for b in range(40)] == [base.step_kind(b) for b in range(40)]
-    assert not rec.names, rec.names
+    assert not guard_names(), names
     # the guarded path owns records on the device: without one its construction reaches the wrapper and goes no further
     for kw in (dict(clip_norm=1.0), dict(skip_nonfinite=True)):
         with pytest.raises(ValueError, match="guard's record"):
             _cpu_trainer(**kw)
-    assert not rec.names      # refused by the wrapper, before the library was asked
+    assert not guard_names()      # refused by the wrapper, before the library was asked
     h = ops._lib.load()
-    h.gg_partials_count(5)
-    assert rec.names == ["gg_partials_count"]      # the recorder does record
+    h.lgg_partials_count(5)
+    assert guard_names() == ["lgg_partials_count"]      # the recorder does record

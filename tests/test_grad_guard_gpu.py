@@ -1,9 +1,9 @@
 """Global-norm gradient clipping and the non-finite step guard on the device: the fp64 sum of squares at every edge of
 its launch geometry (one group, one wave, one chunk, many chunks, the stride over chunks), exact on integer inputs and within the bound
 of any fp64 summation on random ones, independent of the address; the record against the host restatement (config.grad_guard_restate);
-the two Adam passes that read their scale and skip flag from the record against the existing ones, bit for bit; the memory contract of
-every pointer-taking gg_* entry point with guard bands (tests/guards.py: what tests/test_memory_contract_gpu.py does for the `lg*_`
-names); and whole training steps: with a threshold nothing reaches, against a trainer whose gradients the test scales itself, with a
+the two Adam passes that read their scale and skip flag from the record against the existing ones, bit for bit (the memory contract
+of every pointer-taking lgg_* entry point: the guard-* rows of tests/test_memory_contract_gpu.py, on this module's data); and whole
+training steps: with a threshold nothing reaches, against a trainer whose gradients the test scales itself, with a
 NaN planted in one gradient, through replayed graphs, across a checkpoint, with the weight average, under a schedule, on two ranks."""
 import math
 import os
@@ -16,11 +16,10 @@ import torch.multiprocessing as mp
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from oracle import np_oracle as O  # noqa: E402
-from guards import describe, exact_workspaces  # noqa: E402
+from guards import called  # noqa: E402
 from test_dp_gpu import CFG as DP_CFG, _free_port, _join_all  # noqa: E402
-from test_grad_guard_cpu import CH, PMAX, GgRecorder  # noqa: E402
+from test_grad_guard_cpu import CH, PMAX  # noqa: E402
 from test_lr_schedule_gpu import B1, B2, EPS, SCHED_KW, SMALL, STEPS, _build, _same, _snapshot, _step_inputs, _t  # noqa: E402
-from test_memory_contract_gpu import Alloc, _diff, _stale  # noqa: E402
 from test_step_gpu import dev_inputs, f32_round, perturbed  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -34,6 +33,11 @@ NS = [1, 3, 4, 5, 255, 256, 257, 1023, 1024, 1025, CH - 1, CH, CH + 1, 2 * CH + 
 def ops():
     from littlegan_amd import ops as _ops
     return _ops
+
+
+def _guard_names(fetched):
+    """the lgg_ names among the ABI names guards.called recorded, in order"""
+    return [n for n in fetched if n.startswith("lgg_")]
 
 
 def _ulps(a, b):
@@ -325,18 +329,7 @@ def test_a_bad_gradient_without_skip_is_the_step_as_it_is(ops, n):
 
 
 # ---------------------------------------------------------------------------------------------------------------- memory contract
-class GRow:
-    def __init__(self, id, covers, run, check, sizing=()):
-        self.id, self.covers, self.run, self.check, self.sizing = id, tuple(covers), run, check, list(sizing)
-
-    def __repr__(self):
-        return self.id
-
-
-ROWS = []
-I32, F64 = torch.int32, torch.float64
-
-
+# (the guard-* rows of tests/test_memory_contract_gpu.py, which imports these two and _ulps, _c_from above)
 def _rec_np(eff=0.0, skip_now=0, skipped=0, nonfinite=0):
     w = np.zeros(8, np.float32)
     w[1] = eff
@@ -347,157 +340,6 @@ def _rec_np(eff=0.0, skip_now=0, skipped=0, nonfinite=0):
 def _data(n, seed):
     r = np.random.default_rng(seed)
     return [r.standard_normal(n).astype(np.float32) for _ in range(4)] + [(r.random(n) * 0.1).astype(np.float32)]
-
-
-def init_row():
-    def run(ops, alloc):
-        return dict(rec=ops.guard_init(3, 7, out=alloc.out("rec", (8,))))
-
-    def check(res):
-        assert res["rec"].cpu().view(I32).tolist() == [0, 0, 0, 3, 7, 0, 0, 0]
-
-    ROWS.append(GRow("gg-init", ("gg_init",), run, check))
-
-
-def sumsq_row(n, poison):
-    """partials of exactly P(n) doubles, the record from them, and ops.grad_sumsq through a workspace of exactly gg_workspace_bytes(n)"""
-    def data():
-        g = _data(n, 100 + n)[0]
-        if poison:
-            g[n - 1] = np.nan
-        return g
-
-    def run(ops, alloc):
-        g = alloc.inp("g", data())
-        part = alloc.out("partial", (ops.guard_partials_count(n),), F64)
-        ops.guard_sumsq_partial(g, part)
-        route = ops.last_kernel()
-        rec = alloc.state("rec", _rec_np(skipped=2, nonfinite=4))
-        ops.guard_finalise(part, n, rec, 0.5, 1e-2, 1)
-        S = ops.grad_sumsq(g)
-        return dict(partial=part, rec=rec, S=repr(S), _route=route + ";" + ops.last_kernel())
-
-    def check(res):
-        from littlegan_amd import config
-        want = config.grad_guard_restate(data(), 0.5, float(F32(1e-2)), True)
-        words = res["rec"].cpu().view(I32).tolist()
-        assert _ulps(res["rec"][0].item(), want["N"]) <= 1 or poison
-        assert words[2:5] == ([1, 3, 5] if poison else [0, 2, 4]) and words[6:] == [0, 0]
-        assert res["rec"][5].item() == (1.0 if poison else float(_c_from(res["rec"][0].item(), F32(1e-2), False)))
-        S = float(res["S"])
-        assert (math.isnan(S) if poison else abs(S - float(want["S"])) <= n * 2.0 ** -52 * float(want["S"]))
-
-    ROWS.append(GRow(f"gg-sumsq-{n}{'-nan' if poison else ''}", ("gg_sumsq_partial", "gg_finalise", "gg_workspace_bytes", "gg_partials_count"),
-                     run, check, sizing=[("gg_workspace_bytes", (n,))]))
-
-
-def adam_row(n, skip_now):
-    eff = float(F32(0.5) * F32(0.3713))
-
-    def run(ops, alloc):
-        w0, g0, m0, _, v0 = _data(n, 200 + n)
-        w, m, v = alloc.state("w", w0), alloc.state("m", 0.1 * m0), alloc.state("v", v0)
-        state = alloc.state("adam_state", np.array([B1 ** 3, B2 ** 3], np.float32))
-        rec, lr = alloc.inp("rec", _rec_np(eff, skip_now)), alloc.inp("lr", np.array([1e-2], np.float32))
-        ops.guard_clip_adam_update(w, alloc.inp("g", g0), m, v, state, lr, rec, B1, B2, EPS, 0.5)
-        ops.guard_adam_advance(state, rec, B1, B2)
-        wr, mr, vr = alloc.state("w_ref", w0), alloc.state("m_ref", 0.1 * m0), alloc.state("v_ref", v0)
-        sr = alloc.state("state_ref", np.array([B1 ** 3, B2 ** 3], np.float32))
-        if not skip_now:
-            ops.clip_adam_update(wr, alloc.inp("g_ref", g0), mr, vr, sr, 1e-2, B1, B2, EPS, 0.5, eff)
-            ops.adam_advance(sr, B1, B2)
-        return dict(w=w, m=m, v=v, state=state, wr=wr, mr=mr, vr=vr, sr=sr)
-
-    def check(res):
-        for a, b in (("w", "wr"), ("m", "mr"), ("v", "vr"), ("state", "sr")):
-            assert torch.equal(_t(res[a]), _t(res[b])), a
-        assert (res["state"].tolist() == [float(F32(B1 ** 3)), float(F32(B2 ** 3))]) == bool(skip_now)
-
-    ROWS.append(GRow(f"gg-adam-{n}{'-skip' if skip_now else ''}", ("gg_clip_adam_update", "gg_adam_advance"), run, check))
-
-
-def ema_adam_row(n, lo, hi, skip_now):
-    eff = float(F32(0.5) * F32(0.3713))
-
-    def data():
-        w, g, m, e, v = _data(n, 300 + n)
-        for t in (g, m, v):       # outside the range: whatever is read there poisons the result
-            t[:lo], t[hi:] = np.nan, np.nan
-        return w, g, 0.1 * m, v, e
-
-    def run(ops, alloc):
-        w0, g0, m0, v0, e0 = data()
-        w, m, v, ema = alloc.state("w", w0), alloc.state("m", m0), alloc.state("v", v0), alloc.state("ema", e0)
-        state = alloc.inp("adam_state", np.array([B1 ** 3, B2 ** 3], np.float32))
-        count = alloc.inp("counter", torch.tensor([5], dtype=I32))
-        rec, lr = alloc.inp("rec", _rec_np(eff, skip_now)), alloc.inp("lr", np.array([1e-2], np.float32))
-        ops.guard_clip_adam_ema_update(w, alloc.inp("g", g0), m, v, ema, lo, hi, state, count, lr, rec, B1, B2, EPS, 0.5, 0.99)
-        wr, mr, vr, er = alloc.state("w_ref", w0), alloc.state("m_ref", m0), alloc.state("v_ref", v0), alloc.state("ema_ref", e0)
-        ops.clip_adam_ema_update(wr, alloc.inp("g_ref", g0), mr, vr, er, lo, lo if skip_now else hi, state, count, 1e-2, B1, B2, EPS, 0.5,
-                                 eff, 0.99)
-        return dict(w=w, m=m, v=v, ema=ema, wr=wr, mr=mr, vr=vr, er=er)
-
-    def check(res):
-        for a, b in (("w", "wr"), ("m", "mr"), ("v", "vr"), ("ema", "er")):
-            assert torch.equal(_t(res[a]), _t(res[b])), a
-        assert torch.isfinite(res["ema"]).all() and torch.isfinite(res["w"]).all()
-        assert torch.equal(res["w"].cpu(), torch.from_numpy(data()[0])) == bool(skip_now)
-
-    ROWS.append(GRow(f"gg-adam-ema-{n}{'-skip' if skip_now else ''}", ("gg_clip_adam_ema_update",), run, check))
-
-
-init_row()
-for _n in (5, CH + 1):
-    sumsq_row(_n, False)
-    adam_row(_n, 0)
-sumsq_row(5, True)
-adam_row(5, 1)
-ema_adam_row(1028, 4, 1024, 0)
-ema_adam_row(1028, 4, 1024, 1)
-
-
-def _once(row_, ops, monkeypatch, mode, byte=0xFF):
-    alloc = Alloc(mode, byte)
-    with monkeypatch.context() as mp_:
-        ws = exact_workspaces(mp_, ops, fill=byte) if mode == "guard" else None
-        names = GgRecorder(mp_, ops).names
-        ops._lib.load().lg_clear_kernel()
-        res = dict(row_.run(ops, alloc))
-        route = str(res.pop("_route")) if "_route" in res else ops.last_kernel()
-        torch.cuda.synchronize()
-    return res, route, alloc, ws, set(names)
-
-
-def test_every_pointer_taking_entry_point_has_a_row():
-    from littlegan_amd import _lib
-    takes_pointer = {n for n, (_, args) in _lib.GG_SIGNATURES.items() if sum(a is _lib.P for a in args) > 1}   # beyond the stream
-    assert takes_pointer == {"gg_init", "gg_sumsq_partial", "gg_finalise", "gg_clip_adam_update", "gg_clip_adam_ema_update", "gg_adam_advance"}
-    assert takes_pointer <= {n for r in ROWS for n in r.covers}
-
-
-@pytest.mark.parametrize("case", ROWS, ids=lambda r: r.id)
-def test_memory_contract(case, ops, monkeypatch):
-    """the body of tests/test_memory_contract_gpu.py::test_memory_contract for the gg_ rows: plain twice, then inside 0xFF, 0x00 and 0x3F
-    guard bands with outputs pre-filled and every workspace of exactly the advertised size"""
-    plain, route, _, _, names = _once(case, ops, monkeypatch, "plain")
-    assert not set(case.covers) - names, f"the row claims entry points it never fetched: {sorted(set(case.covers) - names)}"
-    plain2, route2, _, _, _ = _once(case, ops, monkeypatch, "plain")
-    d = _diff("two plain runs differ", plain, plain2)
-    assert not d and route == route2, d or (route, route2)
-    for tag, byte in (("A (0xFF)", 0xFF), ("B (0x00)", 0x00), ("C (0x3F)", 0x3F)):
-        got, route_g, alloc, ws, _ = _once(case, ops, monkeypatch, "guard", byte)
-        assert route_g == route, (tag, route_g, route)
-        bad = alloc.problems() + [f"{what}: written outside its advertised size: {describe(offs)}" for what, offs in ws.damaged()]
-        assert not bad, f"run {tag}: " + " | ".join(bad)
-        handed = sorted(nb for _, nb, _ in ws.handed)
-        sized = sorted(int(getattr(ops._lib.load(), fn)(*args)) for fn, args in case.sizing)
-        assert handed == sized, f"run {tag}: workspaces of {handed} bytes handed over, the sizing entries give {sized}"
-        if byte == 0xFF:
-            stale = _stale(plain, got)
-            assert not stale, f"run {tag}: " + " | ".join(stale)
-        d = _diff(f"run {tag} differs from the plain run", plain, got)
-        assert not d, d
-    case.check(plain)
 
 
 # ---------------------------------------------------------------------------------------------------------------- whole steps
@@ -593,9 +435,9 @@ def _clipped(ema=False):
 def test_a_threshold_nothing_reaches_is_the_default_step(ops, monkeypatch):
     """(a) clip_norm = 1e30 with skip_nonfinite: every weight, Adam slot and beta power of eight steps as with the keys at their defaults"""
     with monkeypatch.context() as mp_:
-        recorder = GgRecorder(mp_, ops)
+        fetched = called(mp_, ops)
         cfg, W, default_snaps, snaps, recs, tr = _base()
-        names = list(recorder.names)
+        names = _guard_names(fetched)
     assert tr.guard == {"clip_norm": float(F32(1e30)), "skip": True} and tr.grad_norm_now().shape == (3,)
     assert cfg.partition_interval == 4 and tr.step_kind(10)[0] >= 0 and not tr.step_kind(10)[1] and tr.step_kind(11) == (-1, True, False)
     for k, b in enumerate(STEPS):
@@ -603,7 +445,7 @@ def test_a_threshold_nothing_reaches_is_the_default_step(ops, monkeypatch):
         rows = recs[k].view(np.int32)
         for i, m in enumerate("GDA"):
             if m == "A" and b <= 10:
-                assert not rows[i].any()                                  # the Adjuster has not trained yet: the record as gg_init left it
+                assert not rows[i].any()                                  # the Adjuster has not trained yet: the record as lgg_init left it
                 continue
             N, eff, c = recs[k][i, 0], recs[k][i, 1], recs[k][i, 5]
             assert np.isfinite(N) and N > 0 and c == 1.0 and eff == 1.0 and rows[i, 2:5].tolist() == [0, 0, 0], (b, m)
@@ -612,12 +454,12 @@ def test_a_threshold_nothing_reaches_is_the_default_step(ops, monkeypatch):
     assert len({float(r[1, 0]) for r in recs}) == len(STEPS)              # D's norm: another one on every step
     if names:       # (empty when another test of this module ran the shared steps first)
         per_net = 2 * 4 + 3 * 4                                           # D and G on 7..10, all three from 11 on
-        assert names.count("gg_init") == 3
-        for fn in ("gg_sumsq_partial", "gg_finalise", "gg_clip_adam_update", "gg_adam_advance"):
+        assert names.count("lgg_init") == 3
+        for fn in ("lgg_sumsq_partial", "lgg_finalise", "lgg_clip_adam_update", "lgg_adam_advance"):
             assert names.count(fn) == per_net, (fn, names.count(fn))
-        names = [x for x in names if x != "gg_workspace_bytes"]           # (the wrapper of gg_finalise asks it for the size it checks)
-        at = names.index("gg_sumsq_partial")
-        assert names[at:at + 4] == ["gg_sumsq_partial", "gg_finalise", "gg_clip_adam_update", "gg_adam_advance"]
+        names = [x for x in names if x != "lgg_workspace_bytes"]           # (the wrapper of lgg_finalise asks it for the size it checks)
+        at = names.index("lgg_sumsq_partial")
+        assert names[at:at + 4] == ["lgg_sumsq_partial", "lgg_finalise", "lgg_clip_adam_update", "lgg_adam_advance"]
 
 
 def test_clipping_equals_gradients_scaled_by_the_test(ops):
@@ -694,9 +536,10 @@ def test_graph_replay_clips_by_its_own_gradient(ops, monkeypatch):
     replayed = []
     for k, b in enumerate(STEPS):
         with monkeypatch.context() as mp_:
-            names = GgRecorder(mp_, ops).names
+            fetched = called(mp_, ops)
             tg.graph_step(b, dev_inputs(_step_inputs(cfg, b)))
             torch.cuda.synchronize()
+        names = _guard_names(fetched)
         assert bool(names) == (kinds.index(kinds[k]) == k or kinds[:k].count(kinds[k]) == 1), (b, len(names))   # a replay fetches nothing
         if not names:
             replayed.append(k)
@@ -744,10 +587,10 @@ def test_clipping_with_the_weight_average(ops, monkeypatch):
     """(f) with ema_decay the fused variant is taken, and (b) holds for the weights, the slots and the average"""
     cfg, W = _base()[:2]
     with monkeypatch.context() as mp_:
-        names = GgRecorder(mp_, ops).names
+        fetched = called(mp_, ops)
         snaps, recs, tr = _clipped(ema=True)
-        names = list(names)
-    assert names.count("gg_clip_adam_ema_update") == 2 * 4 + 3 * 4 and "gg_clip_adam_update" not in names
+        names = _guard_names(fetched)
+    assert names.count("lgg_clip_adam_ema_update") == 2 * 4 + 3 * 4 and "lgg_clip_adam_update" not in names
     assert tr.store.ema is not None and len(snaps[0]) == 7
     ref = _wrap_scaling(_build(cfg, W, ema_decay=0.99), ops, _clip(), [])
     for k, b in enumerate(STEPS):

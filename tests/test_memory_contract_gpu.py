@@ -22,6 +22,7 @@ Each row names the entry points it covers; tests/test_guards_cpu.py checks that 
 include/littlegan_*.h) is named by a row or listed in EXEMPT with its reason, so a new entry point fails there until it gets a row."""
 import ctypes
 import functools
+import math
 import os
 import sys
 
@@ -56,8 +57,12 @@ from test_geom_cpu import FULL as GEOM_FULL, extreme_records as geom_extreme_rec
 from test_rel_cpu import EXACT_LOSS0 as PAIR_LOSS0, EXACT_W_PR as PAIR_W_PR, KIND_NO as PAIR_KIND_NO, SIDE_OTHER, SIDE_SELF, exact_pair_case  # noqa: E402
 from test_rel_gpu import W_FAKE, _seed_halves  # noqa: E402
 from test_lr_schedule_cpu import settings as sched_settings  # noqa: E402
-from test_lr_schedule_gpu import B1, B2, EPS, RATES  # noqa: E402
+from test_lr_schedule_gpu import B1, B2, EPS, RATES, _t as as_i32  # noqa: E402
 from test_adj_fused_gpu import hand_moments  # noqa: E402
+from test_grad_guard_cpu import CH  # noqa: E402
+from test_grad_guard_gpu import _c_from, _data as guard_data, _rec_np, _ulps  # noqa: E402
+from test_blur_cpu import blur_np  # noqa: E402
+from test_blur_gpu import bound as blur_bound, images as blur_images, state_words as blur_state_words  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -2248,3 +2253,149 @@ adj_fused_row(128, 64, 8, 16)       # both tilings of conv_up3's normalising for
 adj_fused_row(64, 32, 8, 32)
 adj_apply_row(2, 8 * 1029, 0)       # a sample length that is no multiple of the block's unroll
 adj_apply_row(2, 8 * 1029, 5)
+
+
+# ------------------------------------------------------------------------------------------------------------------ gradient guard
+def guard_init_row():
+    def run(ops, alloc):
+        return dict(rec=ops.guard_init(3, 7, out=alloc.out("rec", (8,))))
+
+    def check(res):
+        assert res["rec"].cpu().view(I32).tolist() == [0, 0, 0, 3, 7, 0, 0, 0]
+
+    row("guard-init", ("lgg_init",), run, check, exact_sizing=True)
+
+
+def guard_sumsq_row(n, poison):
+    """partials of exactly P(n) doubles, the record from them, and ops.grad_sumsq through a workspace of exactly lgg_workspace_bytes(n)"""
+    def data():
+        g = guard_data(n, 100 + n)[0]
+        if poison:
+            g[n - 1] = np.nan
+        return g
+
+    def run(ops, alloc):
+        g = alloc.inp("g", data())
+        part = alloc.out("partial", (ops.guard_partials_count(n),), F64)
+        ops.guard_sumsq_partial(g, part)
+        route = ops.last_kernel()
+        rec = alloc.state("rec", _rec_np(skipped=2, nonfinite=4))
+        ops.guard_finalise(part, n, rec, 0.5, 1e-2, 1)
+        S = ops.grad_sumsq(g)
+        return dict(partial=part, rec=rec, S=repr(S), _route=route + ";" + ops.last_kernel())
+
+    def check(res):
+        from littlegan_amd import config
+        want = config.grad_guard_restate(data(), 0.5, float(np.float32(1e-2)), True)
+        words_ = res["rec"].cpu().view(I32).tolist()
+        assert _ulps(res["rec"][0].item(), want["N"]) <= 1 or poison
+        assert words_[2:5] == ([1, 3, 5] if poison else [0, 2, 4]) and words_[6:] == [0, 0]
+        assert res["rec"][5].item() == (1.0 if poison else float(_c_from(res["rec"][0].item(), np.float32(1e-2), False)))
+        S = float(res["S"])
+        assert (math.isnan(S) if poison else abs(S - float(want["S"])) <= n * 2.0 ** -52 * float(want["S"]))
+
+    row(f"guard-sumsq-{n}{'-nan' if poison else ''}", ("lgg_sumsq_partial", "lgg_finalise", "lgg_workspace_bytes", "lgg_partials_count"),
+        run, check, sizing=[("lgg_workspace_bytes", (n,))], exact_sizing=True)
+
+
+def guard_adam_row(n, skip_now):
+    eff = float(np.float32(0.5) * np.float32(0.3713))
+
+    def run(ops, alloc):
+        w0, g0, m0, _, v0 = guard_data(n, 200 + n)
+        w, m, v = alloc.state("w", w0), alloc.state("m", 0.1 * m0), alloc.state("v", v0)
+        state = alloc.state("adam_state", np.array([B1 ** 3, B2 ** 3], np.float32))
+        rec, lr = alloc.inp("rec", _rec_np(eff, skip_now)), alloc.inp("lr", np.array([1e-2], np.float32))
+        ops.guard_clip_adam_update(w, alloc.inp("g", g0), m, v, state, lr, rec, B1, B2, EPS, 0.5)
+        ops.guard_adam_advance(state, rec, B1, B2)
+        wr, mr, vr = alloc.state("w_ref", w0), alloc.state("m_ref", 0.1 * m0), alloc.state("v_ref", v0)
+        sr = alloc.state("state_ref", np.array([B1 ** 3, B2 ** 3], np.float32))
+        if not skip_now:
+            ops.clip_adam_update(wr, alloc.inp("g_ref", g0), mr, vr, sr, 1e-2, B1, B2, EPS, 0.5, eff)
+            ops.adam_advance(sr, B1, B2)
+        return dict(w=w, m=m, v=v, state=state, wr=wr, mr=mr, vr=vr, sr=sr)
+
+    def check(res):
+        for a, b in (("w", "wr"), ("m", "mr"), ("v", "vr"), ("state", "sr")):
+            assert torch.equal(as_i32(res[a]), as_i32(res[b])), a
+        assert (res["state"].tolist() == [float(np.float32(B1 ** 3)), float(np.float32(B2 ** 3))]) == bool(skip_now)
+
+    row(f"guard-adam-{n}{'-skip' if skip_now else ''}", ("lgg_clip_adam_update", "lgg_adam_advance"), run, check, exact_sizing=True)
+
+
+def guard_ema_adam_row(n, lo, hi, skip_now):
+    eff = float(np.float32(0.5) * np.float32(0.3713))
+
+    def data():
+        w, g, m, e, v = guard_data(n, 300 + n)
+        for t in (g, m, v):       # outside the range: whatever is read there poisons the result
+            t[:lo], t[hi:] = np.nan, np.nan
+        return w, g, 0.1 * m, v, e
+
+    def run(ops, alloc):
+        w0, g0, m0, v0, e0 = data()
+        w, m, v, ema = alloc.state("w", w0), alloc.state("m", m0), alloc.state("v", v0), alloc.state("ema", e0)
+        state = alloc.inp("adam_state", np.array([B1 ** 3, B2 ** 3], np.float32))
+        count = alloc.inp("counter", torch.tensor([5], dtype=I32))
+        rec, lr = alloc.inp("rec", _rec_np(eff, skip_now)), alloc.inp("lr", np.array([1e-2], np.float32))
+        ops.guard_clip_adam_ema_update(w, alloc.inp("g", g0), m, v, ema, lo, hi, state, count, lr, rec, B1, B2, EPS, 0.5, 0.99)
+        wr, mr, vr, er = alloc.state("w_ref", w0), alloc.state("m_ref", m0), alloc.state("v_ref", v0), alloc.state("ema_ref", e0)
+        ops.clip_adam_ema_update(wr, alloc.inp("g_ref", g0), mr, vr, er, lo, lo if skip_now else hi, state, count, 1e-2, B1, B2, EPS, 0.5,
+                                 eff, 0.99)
+        return dict(w=w, m=m, v=v, ema=ema, wr=wr, mr=mr, vr=vr, er=er)
+
+    def check(res):
+        for a, b in (("w", "wr"), ("m", "mr"), ("v", "vr"), ("ema", "er")):
+            assert torch.equal(as_i32(res[a]), as_i32(res[b])), a
+        assert torch.isfinite(res["ema"]).all() and torch.isfinite(res["w"]).all()
+        assert torch.equal(res["w"].cpu(), torch.from_numpy(data()[0])) == bool(skip_now)
+
+    row(f"guard-adam-ema-{n}{'-skip' if skip_now else ''}", ("lgg_clip_adam_ema_update",), run, check, exact_sizing=True)
+
+
+guard_init_row()
+for _n in (5, CH + 1):      # one group of four and a tail; one element past a chunk: two workgroups
+    guard_sumsq_row(_n, False)
+    guard_adam_row(_n, 0)
+guard_sumsq_row(5, True)
+guard_adam_row(5, 1)
+guard_ema_adam_row(1028, 4, 1024, 0)
+guard_ema_adam_row(1028, 4, 1024, 1)
+
+
+# ------------------------------------------------------------------------------------------------------------------ faded blur of D's inputs
+def blur_apply_row(S):
+    """2 images under sigma = 10 (R = 30; at S = 8 most taps lie outside the image, S = 40 takes two tiles a side), the state's k and
+    reserved words holding junk: sigma is the only word the kernel may read.  Against blur_np at the bound of tests/test_blur_gpu.py"""
+    def run(ops, alloc):
+        x = alloc.inp("x", blur_images(2, S))
+        state = alloc.inp("state", blur_state_words(10.0, 0x12345678, 0x7FC00001, -7).view(np.float32))
+        return dict(out=ops.blur_apply(x, state, out=alloc.out("out", (2, S, S, 3))))
+
+    def check(res):
+        assert np.abs(f64(res["out"]) - blur_np(blur_images(2, S), 10.0)).max() <= blur_bound(30, 1.0)
+
+    row(f"blur-apply-2x{S}", ("lgblur_apply",), run, check, route="dblur_apply_kernel", exact_sizing=True)
+
+
+def blur_init_step_row():
+    """init(5) into a state that holds junk, then one step: k = 6, the reserved words zero"""
+    def run(ops, alloc):
+        tr = Trace(ops)
+        state = ops.blur_init(5, out=alloc.out("state", (4,)))
+        tr("init")
+        ops.blur_step(state, 10.0, 3, 100)
+        tr("step")
+        return dict(state=state, _route=tr)
+
+    def check(res):
+        got = i32(res["state"]).tolist()
+        assert got[0] == 6 and got[2:] == [0, 0]      # (sigma against the restatement: tests/test_blur_gpu.py)
+
+    row("blur-init-step", ("lgblur_init", "lgblur_step"), run, check, route=("init=dblur_init_kernel", "step=dblur_step_kernel"),
+        exact_sizing=True)
+
+
+blur_apply_row(8)
+blur_apply_row(40)
+blur_init_step_row()
